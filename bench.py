@@ -8,7 +8,16 @@ make_model-style init, synthetic x ~ N(0,1), seeded d_out / d_re_At.
 A step = forward + backward of one batch through the HIP library (+ the RCCL
 all-reduce of the parameter gradients when --gpus > 1: data parallel, weak scaling).
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel family, the GEMMs
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps, writes
+the last timed step's outputs when --dump-outputs DIR is given, and prints the headline
+(`value`, `ms_per_step`, ...).  Everything else below is measured only with --full.
+
+--dump-outputs DIR: what the last timed step handed its caller, as float32 DIR/<name>.npy
+(rank 0): `out`, `re_at`, and `grad.<parameter>` for every parameter gradient the backward
+wrote.  Inputs, init and the dropout seeds are seeded, so the same arguments give the same
+inputs in every run and two builds can be compared output for output.
+
+--full: `roofline` is for the dominant kernel family, the GEMMs
 (every dense contraction of the step: 27 gemm_f32 calls with their split-K folds): summed
 algorithmic FLOP over summed durations, each call bracketed by HIP events on the stream it
 runs on (dstagnn::prof_start/stop, serialised steps); `hot_kernel` keeps round 1's single
@@ -256,6 +265,26 @@ def cpu_baseline(budget_s=12.0, warmup=2, min_iters=5, max_iters=20):
                       f"min / max {B / max(times):.1f} / {B / min(times):.1f} samples/s"}
 
 
+DUMP_MAX_BYTES = 60 << 20  # all files together stay under 64 MB (headers included)
+
+
+def dump_outputs(dirname, arrays):
+    """Write {name: tensor} as float32 dirname/<name>.npy.  When everything together would pass
+    DUMP_MAX_BYTES, every array larger than an equal share is cut to a fixed, seeded sample of
+    its flattened elements (the same indices in every run)."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in arrays.items()}
+    if sum(a.nbytes for a in host.values()) > DUMP_MAX_BYTES:
+        share = DUMP_MAX_BYTES // (4 * len(host))
+        for k, a in host.items():
+            if a.size > share:
+                idx = np.sort(np.random.RandomState(0).choice(a.size, share, replace=False))
+                host[k] = a.reshape(-1)[idx]
+    for k, a in host.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(a))
+    return sorted(host)
+
+
 def _free_port():
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
         s.bind(("127.0.0.1", 0))
@@ -322,7 +351,15 @@ def main():
     ap.add_argument("--prof-steps", type=int, default=5, help="serialised steps for the GEMM-family event timing")
     ap.add_argument("--no-extras", action="store_true", help="skip the first-block / full-model lines")
     ap.add_argument("--launch-probe", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the hot kernel, the GEMM-family roofline, the bf16 "
+                         "variant, the CPU baseline and the first-block / full-model extras "
+                         "(--hot-iters, --prof-steps, --no-cpu-baseline and --no-extras apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs and parameter gradients as float32 DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -356,6 +393,7 @@ def main():
         torch.autograd.backward([out, re_at], [g_out, g_re])
         if reducer is not None:  # the DP exchange step: bucketed RCCL all-reduce (mean)
             reducer.all_reduce()
+        return out, re_at
 
     log(f"rank {rank}/{world}: block built, warmup {args.warmup}")
     for _ in range(args.warmup):
@@ -366,7 +404,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     t_issue = time.perf_counter() - t0  # host time to issue the steps (launch-bound if ~ elapsed)
     torch.cuda.synchronize()
     if world > 1:
@@ -380,6 +418,37 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     log(f"timed {args.steps} steps: {ms_per_step:.3f} ms/step (host issue {t_issue / args.steps * 1e3:.3f} ms/step)")
     value = world * B * args.steps / elapsed
+
+    if args.dump_outputs and rank == 0:  # before anything below runs the step again
+        arrays = {"out": last[0], "re_at": last[1]}
+        arrays.update({"grad." + n: p.grad for n, p in blk.named_parameters() if p.grad is not None})
+        written = dump_outputs(args.dump_outputs, arrays)
+        log(f"dumped {len(written)} arrays of the last timed step to {args.dump_outputs}")
+    del last
+
+    stamp = _lib.build_stamp()
+    # whole-block roofline (SURVEY.md §8(d)): 758.8 MFLOP per sample fwd+bwd, compute-bound
+    # (arithmetic intensity ~460 flop/B vs the fp32 ridge ~20): peak samples/s = 157.3 TF / F_alg
+    f_alg = algorithmic_flops_per_sample()
+    peak_sps = PEAK_FP32_TFLOPS * 1e12 / f_alg
+    block_roof = {"bound": "mfma", "alg_flop_per_sample": round(f_alg / 1e6, 1), "unit_flop": "MFLOP",
+                  "peak_samples_per_s_per_gpu": round(peak_sps, 0),
+                  "frac": round(value / (world * peak_sps), 4)}
+    line = {
+        "metric": "DSTAGNN_block fwd+bwd samples/sec (B,N=170,T=12) @1/2/4/8 GPU; %HBM roofline",
+        "value": round(value, 2), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "fp32", "data": "synthetic", "full": args.full,
+        "config": {"workload": "PEMS08 inner DSTAGNN_block fwd+bwd (train mode, dropout 0.05)",
+                   "global_batch": B * world, "per_gpu_batch": B, "N": c["N"], "T": c["T"], "F": c["C"],
+                   "K": c["K"], "n_heads": c["n_heads"], "d_model": c["d_model"], "d_k": c["d_k"],
+                   "parallelism": f"dp{world}"},
+        "algorithmic_tflops": round(f_alg * value / 1e12, 3),
+        "block_roofline": block_roof,
+        "build": stamp,
+    }
+    if not args.full:  # a plain run ends here: the headline only
+        return finish(rank, world, line)
 
     ops = _lib.load()
     names, ps, slots = blk._param_list()
@@ -409,7 +478,6 @@ def main():
         dominant = dominant_kernel(ops.prof_records(), P)
     else:
         dominant = None
-    stamp = _lib.build_stamp()
     pmc = load_pmc(stamp)
     rocprof_fam = load_family_rocprof(stamp)
     fresh = pmc is not None and not pmc["stale"]
@@ -471,8 +539,6 @@ def main():
     if rank == 0 and world == 1 and not args.no_extras:
         log("extras: first block, full model step")
         ext = extras(dev, max(5, args.steps // 2), 3)
-    # whole-block roofline (SURVEY.md §8(d)): 758.8 MFLOP per sample fwd+bwd, compute-bound
-    # (arithmetic intensity ~460 flop/B vs the fp32 ridge ~20): peak samples/s = 157.3 TF / F_alg
     # the metric's "%HBM roofline": memory-side bytes of one step (rocprofv3 FETCH_SIZE /
     # WRITE_SIZE passes, width-corrected: profiles/block_pmc.json) over this run's step time
     hbm_roof = None
@@ -485,35 +551,19 @@ def main():
                     "stale": pmc["stale"], "pmc_build": pmc.get("build")}
         if pmc["stale"]:  # counters of another build: no fraction is claimed from them
             hbm_roof["frac"] = None
-    f_alg = algorithmic_flops_per_sample()
-    peak_sps = PEAK_FP32_TFLOPS * 1e12 / f_alg
-    block_roof = {"bound": "mfma", "alg_flop_per_sample": round(f_alg / 1e6, 1), "unit_flop": "MFLOP",
-                  "peak_samples_per_s_per_gpu": round(peak_sps, 0),
-                  "frac": round(value / (world * peak_sps), 4)}
 
+    line.update({"roofline": roof, "dominant_kernel": dominant, "hot_kernel": hot, "hbm_roofline": hbm_roof,
+                 "cpu_baseline": cpu})
+    if bf16 is not None:
+        line["variant_bf16_gemm"] = bf16
+    if ext is not None:
+        line["extras"] = ext
+    finish(rank, world, line)
+
+
+def finish(rank, world, line):
+    """Rank 0 prints the one JSON result line; every rank leaves the process group."""
     if rank == 0:
-        line = {
-            "metric": "DSTAGNN_block fwd+bwd samples/sec (B,N=170,T=12) @1/2/4/8 GPU; %HBM roofline",
-            "value": round(value, 2), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "fp32", "data": "synthetic",
-            "config": {"workload": "PEMS08 inner DSTAGNN_block fwd+bwd (train mode, dropout 0.05)",
-                       "global_batch": B * world, "per_gpu_batch": B, "N": c["N"], "T": c["T"], "F": c["C"],
-                       "K": c["K"], "n_heads": c["n_heads"], "d_model": c["d_model"], "d_k": c["d_k"],
-                       "parallelism": f"dp{world}"},
-            "algorithmic_tflops": round(algorithmic_flops_per_sample() * value / 1e12, 3),
-            "roofline": roof,
-            "dominant_kernel": dominant,
-            "hot_kernel": hot,
-            "block_roofline": block_roof,
-            "hbm_roofline": hbm_roof,
-            "cpu_baseline": cpu,
-            "build": stamp,
-        }
-        if bf16 is not None:
-            line["variant_bf16_gemm"] = bf16
-        if ext is not None:
-            line["extras"] = ext
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

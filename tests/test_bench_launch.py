@@ -26,6 +26,17 @@ def test_self_launch_two_ranks():
     assert rec["n_gpus"] == 2 and rec["ranks_seen"] == 2 and rec["rank_sum"] == 1
 
 
+def test_full_and_dump_options_parse(tmp_path):
+    """--full and --dump-outputs exist (the probe ends before any GPU work, so nothing is
+    written); --steps 0 is refused: the result line divides by the number of timed steps."""
+    r = _run(["--gpus", "1", "--launch-probe", "--full", "--dump-outputs", str(tmp_path / "dump")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout.splitlines()[-1])["probe"] is True
+    assert not (tmp_path / "dump").exists()
+    r = _run(["--gpus", "1", "--launch-probe", "--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 def test_world_size_mismatch_fails_loudly():
     e = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--launch-probe"], cwd=ROOT,

@@ -27,7 +27,7 @@ for s in "${S[@]}"; do
   case $s in
     pytest) DSTAGNN_PROFILE_OUT=gpurun_out run pytest_gpu 900 python -u -m pytest tests -m gpu --maxfail=8 -q -rf --timeout 180 --timeout-method thread ;;
     smoke)  run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)  run bench 600 python bench.py --steps 20 --warmup 5 ;;
+    bench)  run bench 600 python bench.py --full --steps 20 --warmup 5 ;;
     prof)   run prof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline ;;
     cfgab)  # same-box A/B of one env knob on BASELINE configs: CFGAB_ENV="K=V", CFGAB_CONFIGS="SYN GAMBIA"
             for r in 1 2; do
@@ -36,7 +36,7 @@ for s in "${S[@]}"; do
               grep -h "ms_per_step" gpurun_out/cfgab_base_$r.log gpurun_out/cfgab_knob_$r.log | grep configs
             done ;;
     mstep)  run mstep 300 rocprofv3 --kernel-trace --stats -d gpurun_out/mstep -o run --output-format csv -- python3 tools/model_step_prof.py --steps 5 ;;
-    dp2)    DSTAGNN_DIST_BACKEND=gloo DSTAGNN_DEVICE_MOD=1 run dp2 300 python bench.py --gpus 2 --steps 5 --warmup 2 --no-extras ;;
+    dp2)    DSTAGNN_DIST_BACKEND=gloo DSTAGNN_DEVICE_MOD=1 run dp2 300 python bench.py --full --gpus 2 --steps 5 --warmup 2 --no-extras ;;
     pmcs)   echo "== pmcs ($(date +%T))"; bash tools/pmc_step.sh || exit $? ;;
     pmcsum) # summarise the PMC passes on the box so the bench below reads this build's traffic
             python3 tools/pmc_step_summary.py gpurun_out/pmcs profiles/block_pmc.json > gpurun_out/pmcsum.log 2>&1 \

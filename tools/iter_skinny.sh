@@ -6,4 +6,4 @@ for e in "DSTAGNN_GEMM_SKINNY=0" "DSTAGNN_SKINNY_FOLD1_KB=512" "DSTAGNN_SKINNY_F
   env $e timeout -k 10 60 python tools/skinny_probe.py theta || exit 1
 done
 timeout -k 10 60 python tools/skinny_probe.py || exit 1
-timeout -k 10 300 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-extras > gpurun_out/bench_q.log 2>&1; rc=$?; grep -E "timed|hot" gpurun_out/bench_q.log; exit $rc
+log=$(mktemp); timeout -k 10 300 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-extras > "$log" 2>&1; rc=$?; grep -E "timed|hot" "$log"; rm -f "$log"; exit $rc
