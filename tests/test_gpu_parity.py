@@ -268,7 +268,9 @@ def _scaled_laplacian_fixed_start(W):
     return (2.0 * Lap) / lam - np.eye(W.shape[0])
 
 
-def _oracle_case(B, N, T, K, h, D, dk, C, first, res_kind, seed, train=False):
+def _oracle_case(B, N, T, K, h, D, dk, C, first, res_kind, seed, train=False, hub=0):
+    """hub=H > 0: node 0 gets H in-edges and node 1 H out-edges in both graphs, i.e. one column
+    and one row of the supports longer than the 64-entry chunk the kernels walk them in."""
     from oracle import dstagnn_ref as ref
     import dstagnn_drought_amd as D_
     gen = torch.Generator().manual_seed(seed)
@@ -278,6 +280,9 @@ def _oracle_case(B, N, T, K, h, D, dk, C, first, res_kind, seed, train=False):
     for i in range(N):
         tmd[i, rs.choice(N, 2, replace=False)] = 1.0
         pa[i, rs.choice(N, 4, replace=False)] = 1.0
+    if hub:
+        tmd[:hub, 0] = pa[:hub, 0] = 1.0
+        tmd[1, :hub] = pa[1, :hub] = 1.0
     Lt = _scaled_laplacian_fixed_start(tmd)
     cheb = [torch.from_numpy(c).float() for c in D_.cheb_polynomial(Lt, K)][:K]
     F = 1 if first else C
@@ -387,6 +392,42 @@ CONFIGS = {
     # templates (KM = 2: 8 dot products a batch; KM = 5: 20, reduced as 32)
     "k2t12": (64, 12, 2, 3, 64, 32, 32),
     "k5t8": (40, 8, 5, 3, 64, 32, 32),
+    # --- the geometries of PINNED_CASES below (tests/kernel_coverage.py maps each to its templates)
+    # N in (384, 512]: 4 score tiles per wave in the small-graph flash kernels (fwd<4>, dqk<4,1>);
+    # n385: one node in the last tile; n401: odd N, 13 tiles, 17 nodes in the last; n512: 16 full
+    # tiles, the forward's LDS image 67,584 B (the raised dynamic-LDS limit)
+    "n385": (385, 12, 3, 3, 64, 32, 32),
+    "n401": (401, 12, 3, 3, 64, 32, 32),
+    "n512": (512, 12, 3, 3, 64, 32, 32),
+    # N in (192, 256]: 7 tiles (the last 8 nodes), 2 per wave, past the two-strip kernel: dqk<2,4>
+    "n200": (200, 12, 3, 3, 64, 32, 32),
+    # just past the small-graph limit: the streamed flash kernels at 17 strips, the last 8 nodes
+    "n520": (520, 12, 3, 3, 64, 32, 32),
+    # sample-pair aggregate-first kernels (T <= 16), F = C = 32: (NQ, KM) by row length F T and K
+    "k1t12": (40, 12, 1, 3, 64, 32, 32),   # (6,2), K < KM; the support is the diagonal
+    "k4t12": (40, 12, 4, 3, 64, 32, 32),   # (6,5), K < KM
+    "k5t16": (40, 16, 5, 3, 64, 32, 32),   # (8,5)
+    "k2t16": (40, 16, 2, 3, 64, 32, 32),   # (8,2)
+    "k6t8": (40, 8, 6, 3, 64, 32, 32),     # (4,8), K < KM
+    "k2t8": (40, 8, 2, 3, 64, 32, 32),     # (4,2)
+    "k8t12": (40, 12, 8, 3, 64, 32, 32),   # (6,8)
+    "k8t16": (40, 16, 8, 3, 64, 32, 32),   # (8,8)
+    # C = 16 (F = 16 inner): NQ = 4 and NQ = 2 rows, 16-float operand rows
+    "c16t12": (40, 12, 3, 3, 64, 32, 16),
+    "c16k8t8": (40, 8, 8, 3, 64, 32, 16),
+    # single-sample aggregate-first kernels (T > 16), 32-step time chunks
+    "k8t24": (48, 24, 8, 2, 64, 32, 32),   # (12,8)
+    "k2t24": (48, 24, 2, 2, 64, 32, 32),   # (12,2); first block: the SDDMM's NQ = 1 at KM = 2
+    "k3t32": (48, 32, 3, 2, 64, 32, 32),   # (16,3), exactly one time chunk
+    "k4t48": (48, 48, 4, 2, 64, 32, 32),   # (16,5), K < KM, chunks 32 + 16
+    "k8t40": (48, 40, 8, 2, 64, 32, 32),   # (16,8), chunks 32 + 8; SDDMM LDS image exactly 160 KB
+    "k8t41": (48, 41, 8, 2, 64, 32, 32),   # one step past the LDS gate (inner block): Theta-first
+    # T that is odd / no multiple of 4 (VALU TAt, no float4 rows), and the minimum T = 7 (the
+    # kernel-7 GTU branch yields one step, fcmy sees 3 T - 12 = 9)
+    "t7": (40, 7, 3, 3, 64, 32, 32),
+    "t7h2": (40, 7, 3, 2, 64, 32, 32),
+    "t10": (40, 10, 3, 3, 64, 32, 32),
+    "t13": (40, 13, 3, 3, 64, 32, 32),
 }
 RELU_EPS = 1e-5  # ReLU decisions may differ from the fp64 oracle's only where |z| <= RELU_EPS * max|z|
 
@@ -463,15 +504,17 @@ def _train_seed():
 
 
 def _run_config_vs_oracle(name, first, B, seed=3, flash=None, tol=TOL, relu_eps=RELU_EPS, errs=None, normwise=False,
-                          train=False, owns=None, res_kind=None, paths=None):
+                          train=False, owns=None, res_kind=None, paths=None, hub=0, stats=None):
     """paths: a set of block_fn.PATH_BITS names the library must take for this case (asserted
-    before the comparison), or a (must, must_not) pair of sets."""
+    before the comparison), or a (must, must_not) pair of sets.  hub: see _oracle_case.
+    stats (dict, optional) receives "mask_elems", the number of ReLU decisions compared."""
     import dstagnn_drought_amd as D_
     from dstagnn_drought_amd.block_fn import dropout_masks, block_paths
     N, T, K, h, D, dk, C = CONFIGS[name]
     if res_kind is None:
         res_kind = 0 if first else 1
-    ref, p, x, res, cheb, apa, dims, gen = _oracle_case(B, N, T, K, h, D, dk, C, first, res_kind, seed=seed)
+    ref, p, x, res, cheb, apa, dims, gen = _oracle_case(B, N, T, K, h, D, dk, C, first, res_kind, seed=seed,
+                                                            hub=hub)
     g_out = torch.randn(B, N, C, T, generator=gen)
     g_re = torch.randn(B, x.shape[2], h, T, T, generator=gen)
     F = x.shape[2]
@@ -497,6 +540,8 @@ def _run_config_vs_oracle(name, first, B, seed=3, flash=None, tol=TOL, relu_eps=
         dm = (m0.cpu(), m1.cpu().permute(0, 2, 1, 3).contiguous())
     masks = hip_relu_masks(blk, xg, rg, train=train, seed=dseed)  # all three ReLUs (:133, :247, :252)
     flips = relu_aware_mask(ref, p, x, res, cheb, apa, dims, masks, name, eps=relu_eps, drop_masks=dm)
+    if stats is not None:
+        stats["mask_elems"] = sum(int(m.numel()) for m in masks)
     d64 = lambda t: t.double() if torch.is_tensor(t) else t  # noqa: E731
     out_r, re_r, gx_r, gra_r, grads_r = ref.block_forward_backward(
         {k: d64(v) for k, v in p.items()}, d64(x), d64(res), [d64(c) for c in cheb], d64(apa), dims, d64(g_out),
@@ -543,7 +588,7 @@ def _run_config_vs_oracle(name, first, B, seed=3, flash=None, tol=TOL, relu_eps=
     return flips
 
 
-@pytest.mark.parametrize("name,first,B,flash", [
+CONFIG_CASES = [  # (name, first, B, flash)
     ("pems04", False, 1, None), ("pems07", False, 1, None), ("gambia", True, 1, None), ("gambia", False, 1, None),
     ("syn", False, 1, None), ("t24", True, 1, None), ("t24", False, 1, None), ("pems08", False, 32, None),
     # the fused (flash) Chebyshev attention is automatic on the sparse path: N <= 512 the
@@ -554,7 +599,12 @@ def _run_config_vs_oracle(name, first, B, seed=3, flash=None, tol=TOL, relu_eps=
     ("t24", False, 2, False), ("gambia", False, 1, False), ("t144k3", False, 2, None), ("t144k3", True, 1, None),
     ("t8", False, 3, None), ("t16", False, 2, None), ("t16", True, 2, None),
     ("n150", False, 3, None), ("n150", True, 2, None), ("k2t12", False, 3, None), ("k2t12", True, 2, None),
-    ("k5t8", False, 3, None), ("k5t8", True, 2, None)])
+    ("k5t8", False, 3, None), ("k5t8", True, 2, None)]
+# the path a case's comment names, asserted (block_fn.block_paths) before the comparison
+CONFIG_PATHS = {"k2t12": {"cheb_agg"}, "k5t8": {"cheb_agg"}}
+
+
+@pytest.mark.parametrize("name,first,B,flash", CONFIG_CASES)
 def test_block_vs_oracle_configs(name, first, B, flash):
     """Held against the oracle evaluated in float64 (pems08 at B=32: the bench configuration
     itself).  Bound per tensor: the stated 1e-4 (scaled by max(1, max|ref|)), or twice the
@@ -565,14 +615,14 @@ def test_block_vs_oracle_configs(name, first, B, flash):
     from the fp64 oracle's only where |z| <= 1e-5 * max|z| (checked, counted); the oracle then
     takes the HIP's decisions, so such a flip cannot fail the value checks."""
     _need_gpu()
-    flips = _run_config_vs_oracle(name, first, B, flash=flash)
+    flips = _run_config_vs_oracle(name, first, B, flash=flash, paths=CONFIG_PATHS.get(name))
     print(f"{name} B={B} flash={flash}: {flips} ReLU decision(s) within rounding of 0")
 
 
 TF_FWD, TF_BWD = "tat_fused_fwd", "tat_fused_bwd"
 
 
-@pytest.mark.parametrize("name,first,res_kind,B,train,fwd,bwd", [
+TAT_FUSED_CASES = [  # (name, first, res_kind, B, train, fused forward, fused backward)
     # T = 8 / 16 (the other row tilings of the 48-row tile: 6 / 3 problems per workgroup)
     ("t8h3", True, 0, 2, False, True, True), ("t8h3", False, 2, 2, False, True, True),
     ("t8h3", False, 2, 3, True, True, True), ("t8h3", True, 0, 7, True, True, True),
@@ -584,7 +634,10 @@ TF_FWD, TF_BWD = "tat_fused_fwd", "tat_fused_bwd"
     # T = 12 at the LDS bound N = 320 and at an odd N (scalar row loads, partial node tile)
     ("n320", False, 1, 2, False, True, True), ("n320", True, 0, 2, True, True, True),
     ("n101", False, 1, 2, False, True, True), ("n101", False, 2, 2, True, True, True),
-    ("n101", True, 0, 3, False, True, True)])
+    ("n101", True, 0, 3, False, True, True)]
+
+
+@pytest.mark.parametrize("name,first,res_kind,B,train,fwd,bwd", TAT_FUSED_CASES)
 def test_tat_fused_variants_vs_oracle(name, first, res_kind, B, train, fwd, bwd):
     """every fused temporal-attention instantiation the gate admits
     (tat_fused_fwd_ok: h = 3, d_k = 32, T in {8, 12, 16}, N <= 320) held to the fp64 oracle,
@@ -596,8 +649,11 @@ def test_tat_fused_variants_vs_oracle(name, first, res_kind, B, train, fwd, bwd)
     print(f"{name} first={first} res={res_kind} B={B} train={train}: {flips} ReLU decision(s) within rounding of 0")
 
 
-@pytest.mark.parametrize("name,first,B,flash", [("pems08", False, 32, None), ("pems08", True, 32, None),
-                                                ("pems08", False, 4, False), ("pems07", False, 2, None)])
+TRAIN_CASES = [("pems08", False, 32, None), ("pems08", True, 32, None),  # (name, first, B, flash)
+               ("pems08", False, 4, False), ("pems07", False, 2, None)]
+
+
+@pytest.mark.parametrize("name,first,B,flash", TRAIN_CASES)
 def test_block_train_mode_vs_oracle_configs(name, first, B, flash):
     """TRAIN mode at the bench's own size (PEMS08 inner block, B=32: the timed path of
     bench.py, both Dropout(0.05) of model/DSTAGNN_my.py:218,221 active at :234,:243): the
@@ -610,7 +666,10 @@ def test_block_train_mode_vs_oracle_configs(name, first, B, flash):
     print(f"train {name} first={first} B={B} flash={flash}: {flips} ReLU decision(s) within rounding of 0")
 
 
-@pytest.mark.parametrize("name,B,flash", [("pems08", 96, True), ("pems07", 66, True)])
+FLASH_LARGE_BATCH_CASES = [("pems08", 96, True), ("pems07", 66, True)]  # (name, B, flash); inner block
+
+
+@pytest.mark.parametrize("name,B,flash", FLASH_LARGE_BATCH_CASES)
 def test_flash_large_batch_vs_oracle(name, B, flash):
     """The fused Chebyshev attention at a batch in (64, 128] against the fp64 oracle: the
     large-graph mask-gradient kernel gives every lane two batch elements there (b and b + 64),
@@ -621,6 +680,86 @@ def test_flash_large_batch_vs_oracle(name, B, flash):
     _need_gpu()
     flips = _run_config_vs_oracle(name, False, B, flash=flash)
     print(f"{name} B={B} flash={flash}: {flips} ReLU decision(s) within rounding of 0")
+
+
+def _pin(name, first, B, must, must_not=(), train=False, flash=None, hub=0):
+    """One PINNED_CASES row; the fused temporal-attention bits are added from the gates'
+    conditions (tat_fused.hip tat_fused_fwd_ok / tat_fused_bwd_ok: h = 3, d_k = 32, N <= 320,
+    T in {8, 12, 16}; the backward with broadcast res_att — the inner-block default here —
+    only where F T is a multiple of the 48-row tile), so both presence and absence are asserted."""
+    N, T, K, h, D, dk, C = CONFIGS[name]
+    fwd = h == 3 and dk == 32 and N <= 320 and T in (8, 12, 16)
+    bwd = fwd and (first or (C * T) % 48 == 0)
+    must, must_not = set(must), set(must_not)
+    (must if fwd else must_not).add(TF_FWD)
+    (must if bwd else must_not).add(TF_BWD)
+    return (name, first, B, train, flash, hub, frozenset(must), frozenset(must_not))
+
+
+def _pin_id(c):
+    name, first, B, train, flash, hub = c[:6]
+    return f"{name}-{'first' if first else 'inner'}-B{B}" + ("-train" if train else "") + \
+        ("-noflash" if flash is False else "") + (f"-hub{hub}" if hub else "")
+
+
+_AGG = {"sparse", "cheb_agg"}
+_FSMALL = _AGG | {"flash", "flash_small"}
+_GTU = {"gtu_fused_fwd", "gtu_fused_bwd"}
+# (name, first, B, train, flash, hub, paths that must be taken, paths that must not).  Inner
+# blocks at B = 3 where sample pairs are formed (the last pair holds one sample).
+PINNED_CASES = (
+    # small-graph flash at 4 tiles per wave, and dqk<2,4> (N in (192, 256])
+    [_pin(n, False, 3, _FSMALL) for n in ("n401", "n512")] +
+    [_pin(n, False, 2, _FSMALL, train=True) for n in ("n401", "n512")] +
+    [_pin(n, True, 2, _FSMALL) for n in ("n401", "n512")] +
+    [_pin("n385", False, 1, _FSMALL), _pin("n200", False, 2, _FSMALL)] +
+    # streamed flash just above the limit
+    [_pin("n520", False, 2, _AGG | {"flash"}, {"flash_small"}), _pin("n520", True, 1, _AGG | {"flash"}, {"flash_small"})] +
+    # sample-pair aggregate-first order templates
+    [_pin(n, first, B, _AGG) for n in ("k1t12", "k4t12", "k5t16", "k2t16", "k6t8", "k2t8", "k8t12", "k8t16")
+     for first, B in ((False, 3), (True, 2))] +
+    [_pin("k8t16", False, 2, _AGG, train=True)] +
+    # C = 16
+    [_pin(n, first, B, _AGG, _GTU) for n in ("c16t12", "c16k8t8") for first, B in ((False, 3), (True, 2))] +
+    # single-sample aggregate-first kernels (T > 16)
+    [_pin(n, first, B, _AGG) for n in ("k8t24", "k2t24", "k3t32", "k4t48", "k8t40") for first, B in ((False, 2), (True, 1))] +
+    # one step past the LDS gate: the inner block (F = 32) is refused, the first block (F = 1) is not
+    [_pin("k8t41", False, 2, {"sparse"}, {"cheb_agg"}), _pin("k8t41", True, 1, _AGG)] +
+    # T edges
+    [_pin(n, first, B, _AGG, _GTU) for n in ("t7", "t7h2", "t10", "t13") for first, B in ((False, 3), (True, 2))] +
+    # hub graph: support columns / rows of more than one 64-entry chunk (n150: column 0 has 100
+    # entries, row 1 has 101 = 64 + 37, a partial last batch of 4; n401: 132, three chunks; n520:
+    # the streamed walks, column 103 = 64 + 39; t24: one chunk of 50 on the single-sample kernels)
+    [_pin(n, first, B, must, mn, train=tr, hub=H)
+     for n, H, must, mn in (("n150", 100, _FSMALL, ()), ("n401", 130, _FSMALL, ()),
+                            ("n520", 100, _AGG | {"flash"}, {"flash_small"}), ("t24", 50, _FSMALL, ()))
+     for first, B, tr in ((False, 3, False), (True, 2, False), (False, 2, True))] +
+    # ... and with the fused attention off: the dense-softmax path's cheb_agg walks alone
+    [_pin("n150", False, 3, _AGG, {"flash"}, flash=False, hub=100)] +
+    # a 32-node strip holding more support entries than flash_small_dqk stages in LDS (kStripE =
+    # 512; column 0 and row 1 alone have 450): its branch that reads the entries from HBM
+    [_pin("n512", False, 2, _FSMALL, hub=450)])
+FLIP_CAP = 1e-3  # ReLU decisions within rounding of 0: at most this fraction of all decisions compared
+
+
+@pytest.mark.parametrize("case", PINNED_CASES, ids=_pin_id)
+def test_pinned_templates_vs_oracle(case):
+    """Every cheb_agg / flash_small template and support-walk edge the gates admit, each pinned
+    by a case whose path is asserted first (tests/kernel_coverage.py names the templates;
+    tests/test_parity_coverage_cpu.py fails when a gate admits one that no case here reaches).
+    Same bound as test_block_vs_oracle_configs: 1e-4 * max(1, max|ref|) or twice the fp32
+    oracle's own error against fp64, ReLU-aware.  In addition the decisions that differ from the
+    fp64 oracle's (each already held to |z| <= 1e-5 max|z|) are capped at 0.1 % of the decisions
+    compared, so a wrong kernel cannot pass as many tiny flips (the fp32 oracle against the fp64
+    one flips at most 0.0001 % at these geometries and seeds)."""
+    _need_gpu()
+    name, first, B, train, flash, hub, must, must_not = case
+    errs, stats = {}, {}
+    flips = _run_config_vs_oracle(name, first, B, flash=flash, train=train, hub=hub, paths=(set(must), set(must_not)),
+                                  errs=errs, stats=stats)
+    worst = max(errs, key=errs.get)
+    print(f"PINNED {_pin_id(case)}: flips {flips} / {stats['mask_elems']}, worst err/scale {errs[worst]:.3e} on {worst}")
+    assert flips <= FLIP_CAP * stats["mask_elems"], f"{name}: {flips} ReLU decisions of {stats['mask_elems']} differ"
 
 
 BF16_TOL = 3e-2      # bf16-operand GEMM variant: normwise ||err||_2 / ||ref||_2 <= BF16_TOL per tensor
