@@ -74,7 +74,7 @@ Dims mkdims(const dstagnn_block_dims& d) {
   m.flash = m.sparse && d.cheb_flash != 0;
   m.nnz = m.flash ? d.cheb_nnz : 0;
   m.fsmall = m.flash && flash_small(m.N);
-  static const bool agg_env = !getenv("DSTAGNN_CHEB_AGG") || atoi(getenv("DSTAGNN_CHEB_AGG")) != 0;
+  static const bool agg_env = env_flag("DSTAGNN_CHEB_AGG", true);
   m.agg = agg_env && m.sparse && cheb_agg_ok(m.F, m.C, m.K, m.T);
   m.apa_nnz = m.fsmall ? std::max(d.cheb_apa_nnz, 0) : 0;
   m.tfused = tat_fused_fwd_ok(m.N, m.T, m.h, m.dk, m.dv);
@@ -88,7 +88,7 @@ Dims mkdims(const dstagnn_block_dims& d) {
 }
 
 struct SaveBufs {
-  // parameters re-laid once per forward (side stream) and reused by the backward:
+  // parameters re-laid once per forward (Fwd::stage_params) and reused by the backward:
   // stacked projections [Wq; Wk; Wv] (QW, N) and [W_Q'; W_K'] (2KD, D), pre_conv as
   // (D, F*T), Theta_cat (F, K*C), GTU conv weights (o, j, c) fwd and (j', o, c) flipped bwd
   float *Wqkv, *Wqk, *Wp, *thcat, *Wgf[3], *Wgb[3];
@@ -485,8 +485,6 @@ struct SideStream {
   uint32_t* flags = nullptr;
   std::atomic<uint32_t> gseq{0};
   std::atomic<uint32_t> fnext{0};
-  bool use_flags = true;
-  bool side_flags = false;  // DSTAGNN_SYNC_EVENTS=2: flags for the side stream's signals too
   bool ksig = true;         // fork flags written by the next main-stream kernel (DSTAGNN_KSIG=0: off)
   bool ok = false;
 };
@@ -544,7 +542,7 @@ int flush_stream_sig() {
 
 // DSTAGNN_DEBUG_STREAMS=1: the fork invariant check (Bwd::sq)
 static bool stream_debug() {
-  static const bool on = getenv("DSTAGNN_DEBUG_STREAMS") && atoi(getenv("DSTAGNN_DEBUG_STREAMS")) != 0;
+  static const bool on = env_flag("DSTAGNN_DEBUG_STREAMS", false);
   return on;
 }
 // a fork signal for `side` is pending: its writer (and so the side's wait) is not queued yet
@@ -561,8 +559,8 @@ __global__ void debug_delay_kernel(uint64_t ticks) {
   while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
 }
 int debug_delay(hipStream_t q, bool on_main) {
-  static const int us_main = getenv("DSTAGNN_DEBUG_MAIN_DELAY_US") ? atoi(getenv("DSTAGNN_DEBUG_MAIN_DELAY_US")) : 0;
-  static const int us_side = getenv("DSTAGNN_DEBUG_SIDE_DELAY_US") ? atoi(getenv("DSTAGNN_DEBUG_SIDE_DELAY_US")) : 0;
+  static const int us_main = env_int("DSTAGNN_DEBUG_MAIN_DELAY_US", 0);
+  static const int us_side = env_int("DSTAGNN_DEBUG_SIDE_DELAY_US", 0);
   const int us = std::min(on_main ? us_main : us_side, 20000);
   if (us <= 0) return 0;
   static const int rate_khz = [] {
@@ -584,8 +582,7 @@ struct SigFlushGuard {
 SideStream* side_stream_for_device() {
   static std::mutex mu;
   static SideStream cache[64];
-  static const bool enabled = !getenv("DSTAGNN_SIDE_STREAM") || atoi(getenv("DSTAGNN_SIDE_STREAM")) != 0;
-  static const bool events = getenv("DSTAGNN_SYNC_EVENTS") && atoi(getenv("DSTAGNN_SYNC_EVENTS")) != 0;
+  static const bool enabled = env_flag("DSTAGNN_SIDE_STREAM", true);
   if (!enabled) return nullptr;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
@@ -600,7 +597,7 @@ SideStream* side_stream_for_device() {
     // (hipExtStreamCreateWithCUMask takes no flags: that stream is BLOCKING, so with a caller on
     // the legacy null stream it also serialises with it — measurements under this knob include
     // that serialisation)
-    const char* cm = getenv("DSTAGNN_SIDE_CUMASK");
+    static const char* const cm = env_str("DSTAGNN_SIDE_CUMASK");
     if (cm && *cm) {
       const uint32_t pat = (uint32_t)strtoul(cm, nullptr, 0);
       int ncu = 0;
@@ -613,15 +610,11 @@ SideStream* side_stream_for_device() {
     }
     for (auto& e : s.ev)
       if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr;
-    s.use_flags = !events || atoi(getenv("DSTAGNN_SYNC_EVENTS")) == 2;
-    s.side_flags = events && atoi(getenv("DSTAGNN_SYNC_EVENTS")) == 2;
-    s.ksig = s.use_flags && (!getenv("DSTAGNN_KSIG") || atoi(getenv("DSTAGNN_KSIG")) != 0);
-    if (s.use_flags) {
-      if (hipMalloc(&s.flags, sizeof(uint32_t) * SideStream::kSlots) != hipSuccess ||
-          hipMemset(s.flags, 0, sizeof(uint32_t) * SideStream::kSlots) != hipSuccess ||
-          hipDeviceSynchronize() != hipSuccess)
-        return nullptr;
-    }
+    s.ksig = env_flag("DSTAGNN_KSIG", true);
+    if (hipMalloc(&s.flags, sizeof(uint32_t) * SideStream::kSlots) != hipSuccess ||
+        hipMemset(s.flags, 0, sizeof(uint32_t) * SideStream::kSlots) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess)
+      return nullptr;
     s.ok = true;
   }
   return &s;
@@ -647,8 +640,7 @@ struct SyncTok {
 // stream (fork) is a flag write on main + a flag wait on the side; one made by the side stream
 // (join, dx_ready) is an event recorded on the side, usually complete by the time the main
 // stream waits for it.  Flag words rotate over kSlots; numbers only grow, so a wait can only
-// be released by its own write or a later one issued behind it.  DSTAGNN_SYNC_EVENTS=1: events
-// both ways; =2: flags both ways.
+// be released by its own write or a later one issued behind it.
 // Kernel-written fork flags (fork_k; default, DSTAGNN_KSIG=0 for the hipStreamWriteValue32
 // above): the flag is stored by workgroup 0 of the next kernel the main stream launches that
 // carries the signal (common.hpp) — every earlier kernel of the stream has completed when it
@@ -680,13 +672,13 @@ struct Streams {
   int signal(hipStream_t from, SyncTok* t) {
     *t = SyncTok{};
     if (!ss) return 0;
-    if (ss->use_flags && (from != ss->side || ss->side_flags)) {
+    if (from != ss->side) {  // made by the main stream: a flag write
       t->slot = (int)(ss->fnext.fetch_add(1, std::memory_order_relaxed) % SideStream::kSlots);
       t->seq = ss->gseq.fetch_add(1, std::memory_order_relaxed) + 1;
       const hipError_t r = hipStreamWriteValue32(from, ss->flags + t->slot, t->seq, 0);
       return r == hipSuccess ? 0 : fail(r);
     }
-    t->ev = ss->ev[ss->next.fetch_add(1, std::memory_order_relaxed) % 64];
+    t->ev = ss->ev[ss->next.fetch_add(1, std::memory_order_relaxed) % 64];  // by the side stream: an event
     const hipError_t r = hipEventRecord(t->ev, from);
     return r == hipSuccess ? 0 : fail(r);
   }
@@ -741,7 +733,6 @@ struct Fwd {
   Scratch& w;
   hipStream_t st;
   Streams ks;
-  bool params_forked = false;
   bool e_side = false;           // E = x transposed is issued on the side stream (token e_ready)
   SyncTok e_ready;
   ChebFl fl;
@@ -801,7 +792,6 @@ struct Fwd {
       DS_TRY(op_transpose(x, s.E, m.N, (int)m.FT, m.B, N * m.FT, m.FT * N, 0.f, st));
     }
     // Q | K | V projections (MultiHeadAttention :92-94) as ONE GEMM over the stacked weights
-    if (params_forked) DS_TRY(ks.join());  // the re-laid parameters (stage_params on the side stream)
     if (m.tfused) return stage_tat_fused();
     {
       Gemm g;
@@ -857,22 +847,18 @@ struct Fwd {
 
   int stage_preconv() { return run_gemm(preconv_gemm(), w.gemm_ws, kGemmWs, st); }
 
-  // every parameter re-layout, on the side stream while the main chain starts
+  // every parameter re-layout, as one launch on the caller's stream (a fork / join pair to the
+  // side stream costs more host time, ~15 us, than these small copies cost GPU time)
   int stage_params() {
-    // on the caller's stream by default: the fork/join pair costs more host time (~15 us)
-    // than these six small launches cost GPU time; DSTAGNN_PARAMS_SIDE=1 moves them
-    static const bool on_side = getenv("DSTAGNN_PARAMS_SIDE") && atoi(getenv("DSTAGNN_PARAMS_SIDE")) != 0;
-    if (on_side) DS_TRY(ks.fork());
-    params_forked = on_side;
-    hipStream_t q = on_side ? ks.sd : st;
     ParamPrep pp;
     bool full = false;
     PrepSeg spare;  // (a segment past the capacity lands here; the call then fails below)
     auto add = [&](int kind, const float* src, float* dst, int64_t n, int p0 = 0, int p1 = 0, int p2 = 0,
-                   int64_t off = 0) {
+                   int64_t off = 0) -> PrepSeg& {
       full = full || pp.nseg >= kPrepSegsHost;
       PrepSeg& g = full ? spare : pp.seg[pp.nseg++];
       g.kind = kind; g.src = src; g.dst = dst; g.n = n; g.p0 = p0; g.p1 = p1; g.p2 = p2; g.dst_off = off;
+      return g;
     };
     add(0, p.tat_wq, s.Wqkv, m.HQ * m.N, 0, 0, 0, 0);
     add(0, p.tat_wk, s.Wqkv, m.HQ * m.N, 0, 0, 0, m.HQ * m.N);
@@ -883,22 +869,16 @@ struct Fwd {
       add(8, p.tat_wv, s.Wqkv_p, m.HV * m.NP, m.N, m.NP, 0, 2 * m.HQ * m.NP);
     }
     if (m.tfused_bwd) {  // the fused backward's B operands (zero-padded transposes, kind 9)
-      add(9, p.tat_fc, s.WfcT, m.HV * m.NP, m.NP, (int)m.HV, m.NP, 0);
-      pp.seg[pp.nseg - 1].p3 = m.N;
-      add(9, p.tat_wq, s.WqT, m.NP * m.HQ, (int)m.HQ, m.N, (int)m.QW, 0);
-      pp.seg[pp.nseg - 1].p3 = (int)m.HQ;
-      add(9, p.tat_wk, s.WqT, m.NP * m.HQ, (int)m.HQ, m.N, (int)m.QW, m.HQ);
-      pp.seg[pp.nseg - 1].p3 = (int)m.HQ;
-      add(9, p.tat_wv, s.WqT, m.NP * m.HV, (int)m.HV, m.N, (int)m.QW, 2 * m.HQ);
-      pp.seg[pp.nseg - 1].p3 = (int)m.HV;
+      add(9, p.tat_fc, s.WfcT, m.HV * m.NP, m.NP, (int)m.HV, m.NP, 0).p3 = m.N;
+      add(9, p.tat_wq, s.WqT, m.NP * m.HQ, (int)m.HQ, m.N, (int)m.QW, 0).p3 = (int)m.HQ;
+      add(9, p.tat_wk, s.WqT, m.NP * m.HQ, (int)m.HQ, m.N, (int)m.QW, m.HQ).p3 = (int)m.HQ;
+      add(9, p.tat_wv, s.WqT, m.NP * m.HV, (int)m.HV, m.N, (int)m.QW, 2 * m.HQ).p3 = (int)m.HV;
     }
     add(0, p.sat_wq, s.Wqk, m.KD * m.D, 0, 0, 0, 0);
     add(0, p.sat_wk, s.Wqk, m.KD * m.D, 0, 0, 0, m.KD * m.D);
     if (m.sfused) {  // [W_Q'; W_K']^T (D, 2 KD): WqkT[d][k] = W[k][d]
-      add(9, p.sat_wq, s.WqkT, m.D * m.KD, (int)m.KD, m.D, (int)(2 * m.KD), 0);
-      pp.seg[pp.nseg - 1].p3 = (int)m.KD;
-      add(9, p.sat_wk, s.WqkT, m.D * m.KD, (int)m.KD, m.D, (int)(2 * m.KD), m.KD);
-      pp.seg[pp.nseg - 1].p3 = (int)m.KD;
+      add(9, p.sat_wq, s.WqkT, m.D * m.KD, (int)m.KD, m.D, (int)(2 * m.KD), 0).p3 = (int)m.KD;
+      add(9, p.sat_wk, s.WqkT, m.D * m.KD, (int)m.KD, m.D, (int)(2 * m.KD), m.KD).p3 = (int)m.KD;
     }
     add(1, p.pre_conv_w, s.Wp, (int64_t)m.D * m.FT, m.F, m.T);  // Wp[d][f][t] = W[d][t][0][f]
     for (int k = 0; k < m.K; ++k) add(2, p.theta[k], s.thcat, (int64_t)m.F * m.C, m.C, (int)m.KC, k);
@@ -910,16 +890,14 @@ struct Fwd {
     }
     if (m.fsmall)  // the dense A_pa o M_k of the small-graph attention kernels (:122)
       for (int k = 0; k < m.K; ++k) {
-        add(5, p.mask[k], s.am + (int64_t)k * m.NN, m.NN);
-        pp.seg[pp.nseg - 1].src2 = gr.adj_pa;
-        add(6, p.mask[k], s.amt + (int64_t)k * m.NN, m.NN, m.N);
-        pp.seg[pp.nseg - 1].src2 = gr.adj_pa;
+        add(5, p.mask[k], s.am + (int64_t)k * m.NN, m.NN).src2 = gr.adj_pa;
+        add(6, p.mask[k], s.amt + (int64_t)k * m.NN, m.NN, m.N).src2 = gr.adj_pa;
       }
     if (full) {
       set_last_error("param_prep: more parameter re-layouts than kPrepSegsHost");
       return DSTAGNN_E_ARG;
     }
-    DS_TRY(op_param_prep(pp, q));
+    DS_TRY(op_param_prep(pp, st));
     return 0;
   }
 
@@ -990,7 +968,7 @@ struct Fwd {
   // 0.701 ms/step same box) — with only k x 16 MFMAs per wave the window staging and weight
   // loads are not amortised, while the GEMM's DMA pipeline overlaps them
   static bool gconv_on() {
-    static const bool on = getenv("DSTAGNN_GTU_GCONV") && atoi(getenv("DSTAGNN_GTU_GCONV")) != 0;
+    static const bool on = env_flag("DSTAGNN_GTU_GCONV", false);
     return on;
   }
 
@@ -1029,12 +1007,11 @@ struct Fwd {
   }
 
   int run() {
-    static const bool prof = getenv("DSTAGNN_HOST_PROFILE") != nullptr;
-    static const bool conc = !getenv("DSTAGNN_FWD_CONCURRENT") || atoi(getenv("DSTAGNN_FWD_CONCURRENT")) != 0;
+    static const bool prof = env_str("DSTAGNN_HOST_PROFILE") != nullptr;
     HostTimer ht(prof, "fwd");
     SigFlushGuard sig_guard;
     ks.init(st);
-    const bool split = conc && ks.sd != st && !params_forked;
+    const bool split = ks.sd != st;
     DS_TRY(stage_params());
     ht.lap("params");
     ChebIO c = cheb_io();
@@ -1162,17 +1139,13 @@ struct Bwd {
     return op_colsum_multi(ins, outs, n, A, O, I, 1, 0.f, q == st ? w.part : w.part_side, kPart, q);
   }
   int gemm(const Gemm& g) { return run_gemm(g, w.gemm_ws, kGemmWs, st); }
-  // side-stream weight gradients: their own split-K target (DSTAGNN_SIDE_SPLITK; 0 = the global
-  // one) — fewer K slices mean a cheaper fold and fewer CUs taken from the main chain.  192: with
-  // the GTU stage fused the side stream is the step's last to finish, and 192 beat the global
-  // 448 by ~8 us/step (256: ~5) in same-box A/Bs (profiles/r05_knob_sweep.txt)
-  static int side_splitk() {
-    static const int t = getenv("DSTAGNN_SIDE_SPLITK") ? atoi(getenv("DSTAGNN_SIDE_SPLITK")) : 192;
-    return t;
-  }
+  // side-stream weight gradients: their own split-K target — fewer K slices mean a cheaper fold
+  // and fewer CUs taken from the main chain.  192: with the GTU stage fused the side stream is
+  // the step's last to finish, and 192 beat the global 448 by ~8 us/step (256: ~5) in same-box A/Bs (profiles/r05_knob_sweep.txt)
+  static constexpr int kSideSplitK = 192;
   int sgemm(const Gemm& g0) {
     Gemm g = g0;
-    if (sd != st && !g.splitk_target) g.splitk_target = side_splitk();
+    if (sd != st && !g.splitk_target) g.splitk_target = kSideSplitK;
     return run_gemm(g, sd == st ? w.gemm_ws : w.gemm_ws_side, kGemmWs, sq());
   }
 
@@ -1301,7 +1274,7 @@ struct Bwd {
         }
       }
       if (sd != st)
-        for (int q = 0; q < nw; ++q) dws[q].splitk_target = side_splitk();
+        for (int q = 0; q < nw; ++q) dws[q].splitk_target = kSideSplitK;
       if (nw) DS_TRY(run_gemm_group(dws, nw, sd == st ? w.gemm_ws : w.gemm_ws_side, kGemmWs, sq()));
     }
     return 0;
@@ -1543,7 +1516,7 @@ struct Bwd {
   // DSTAGNN_DWP_MAIN=1: the pre_conv weight gradient as the main stream's last product instead of
   // the side stream's (stream balance A/B: the side stream's tail sets the step's end)
   static bool dwp_main() {
-    static const bool on = getenv("DSTAGNN_DWP_MAIN") && atoi(getenv("DSTAGNN_DWP_MAIN")) != 0;
+    static const bool on = env_flag("DSTAGNN_DWP_MAIN", false);
     return on;
   }
 
@@ -1560,7 +1533,7 @@ struct Bwd {
   // backward, dE accumulated into dx (inner block) or written for the EmbedT backward (first)
   int stage_tat_fused() {
     const int64_t N = m.N;
-    const bool side_any = tatln_side() || (gd.tat_fc && fc_side()) || wqkv_side();
+    const bool side_any = tatln_side() || (gd.tat_fc && fc_side());
     if (!m.first) DS_TRY(wait_side(dx_ready));  // dx += the Chebyshev-path gradient (side stream) first
     TatFusedBwdArgs t;
     t.dO = w.dO; t.u = s.u_tat; t.mu = s.mu_tat; t.rs = s.rs_tat; t.g = p.tat_ln_g;
@@ -1594,7 +1567,6 @@ struct Bwd {
       DS_TRY(fork());
       if (tatln_side()) DS_TRY(tat_ln_colsums(false));
       if (gd.tat_fc && fc_side()) DS_TRY(sgemm(fc_grad_gemm()));
-      if (wqkv_side()) DS_TRY(tat_wqkv_grad(true));
     }
     return m.first ? embedT_backward() : 0;
   }
@@ -1651,14 +1623,13 @@ struct Bwd {
     DS_TRY(op_tat_bwd(m.B, m.F, m.T, m.h, m.dk, m.dv, s.qkv, s.att, w.dctx, dre, w.dqkv, dsc, dsum, st));
     // --- side: TAt LN gamma / beta, fc and Q|K|V weight grads (one fork; its flag rides on the
     // dE GEMM, issued first)
-    const bool side_any = tatln_side() || (gd.tat_fc && fc_side()) || wqkv_side();
+    const bool side_any = tatln_side() || (gd.tat_fc && fc_side());
     if (side_any) DS_TRY(fork_k());
     auto side_work = [&]() -> int {
       if (!side_any) return 0;
       DS_TRY(fork_k_done());
       if (tatln_side()) DS_TRY(tat_ln_colsums(false));
       if (gd.tat_fc && fc_side()) DS_TRY(sgemm(fc_grad_gemm()));
-      if (wqkv_side()) DS_TRY(tat_wqkv_grad(true));
       return 0;
     };
     {  // dE = dU + dqkv [Wq; Wk; Wv]
@@ -1699,7 +1670,7 @@ struct Bwd {
   // DSTAGNN_GTU_TCONV=0: the GTU input gradient as the K-concatenated GEMM (run_gemm_kcat)
   // instead of the sliding-window kernel (A/B)
   static bool tconv_on() {
-    static const bool on = !getenv("DSTAGNN_GTU_TCONV") || atoi(getenv("DSTAGNN_GTU_TCONV")) != 0;
+    static const bool on = env_flag("DSTAGNN_GTU_TCONV", true);
     return on;
   }
 
@@ -1708,32 +1679,26 @@ struct Bwd {
   // (same box, 2 x 100 steps each) — the strided epilogue of that GEMM on the critical path
   // costs more than the transpose launch it saves.
   static bool dE_omap() {
-    static const bool on = getenv("DSTAGNN_DE_OMAP") && atoi(getenv("DSTAGNN_DE_OMAP")) != 0;
+    static const bool on = env_flag("DSTAGNN_DE_OMAP", false);
     return on;
   }
 
   // [dWq; dWk; dWv] = dqkv^T E — the last product of the backward, issued on the main
   // stream after dx: the side stream is still busy with the earlier parameter gradients
   // (pre_conv, SAt), while the main chain has nothing left (measured: the side stream's tail
-  // was the step's critical path)
-  // DSTAGNN_WQKV_SIDE=1: issue it on the side stream right after the TAt backward instead (beside
-  // the main chain's dE GEMM and transpose, once the side stream's earlier work has drained)
-  static bool wqkv_side() {
-    static const bool on = getenv("DSTAGNN_WQKV_SIDE") && atoi(getenv("DSTAGNN_WQKV_SIDE")) != 0;
-    return on;
-  }
+  // was the step's critical path); see tat_wqkv_grad
   // the TAt fc weight gradient on the side stream (DSTAGNN_FC_SIDE=1) or, by default, on the
   // main stream with the Q|K|V weight gradient as one grouped launch at the step's end: with the
   // main chain's fork flags kernel-written the side stream's tail set the step (two-stream
   // timeline: main ended ~48 us before the side)
   static bool fc_side() {
-    static const bool on = getenv("DSTAGNN_FC_SIDE") && atoi(getenv("DSTAGNN_FC_SIDE")) != 0;
+    static const bool on = env_flag("DSTAGNN_FC_SIDE", false);
     return on;
   }
   // the TAt LayerNorm gamma / beta column sums: likewise on the main stream at the end by default
   // (then the TAt stage forks nothing: no side-stream wait at the step's end); DSTAGNN_TATLN_SIDE=1
   static bool tatln_side() {
-    static const bool on = getenv("DSTAGNN_TATLN_SIDE") && atoi(getenv("DSTAGNN_TATLN_SIDE")) != 0;
+    static const bool on = env_flag("DSTAGNN_TATLN_SIDE", false);
     return on;
   }
   // fused TAt backward: the beta slab's first row (gamma: level-1 rows, then the ticket tree's level-2 rows)
@@ -1755,10 +1720,9 @@ struct Bwd {
     g.C = gd.tat_fc; g.cm = idx1(m.HV); g.cn = idx1(1);
     return g;
   }
-  int tat_wqkv_grad(bool side) {
-    const bool fc_here = !side && !fc_side() && gd.tat_fc;
+  int tat_wqkv_grad() {
+    const bool fc_here = !fc_side() && gd.tat_fc;
     if (!(gd.tat_wq || gd.tat_wk || gd.tat_wv)) return fc_here ? gemm(fc_grad_gemm()) : 0;
-    hipStream_t q = side ? sd : st;
     const int64_t N = m.N;
     Gemm g;
     g.M = (int)m.QW; g.N = m.N; g.K = (int)m.BFT;
@@ -1774,20 +1738,20 @@ struct Bwd {
       const Gemm gs[2] = {g, fc_grad_gemm()};
       DS_TRY(run_gemm_group(gs, 2, w.gemm_ws, kGemmWs, st));
     } else {
-      DS_TRY(side ? sgemm(g) : gemm(g));
+      DS_TRY(gemm(g));
     }
     if (!adjacent) {
       PackRows pk;
       pk.n = 3; pk.cols = m.N; pk.unpack = 1;
       pk.src[0] = w.dWqkv; pk.rows[0] = (int)m.HQ; pk.rows[1] = (int)m.HQ; pk.rows[2] = (int)m.HV;
       pk.dst[0] = gd.tat_wq; pk.dst[1] = gd.tat_wk; pk.dst[2] = gd.tat_wv;
-      DS_TRY(op_pack_rows(pk, q));
+      DS_TRY(op_pack_rows(pk, st));
     }
     return 0;
   }
 
   int run() {
-    static const bool prof = getenv("DSTAGNN_HOST_PROFILE") != nullptr;
+    static const bool prof = env_str("DSTAGNN_HOST_PROFILE") != nullptr;
     HostTimer ht(prof, "bwd");
     SigFlushGuard sig_guard;
     ks.init(st);
@@ -1809,8 +1773,7 @@ struct Bwd {
     DS_TRY(stage_tat());
     DS_TRY(order_err);
     ht.lap("tat");
-    if (!wqkv_side()) DS_TRY(tat_wqkv_grad(false));  // (+ the fc weight gradient)
-    else if (!fc_side() && gd.tat_fc) DS_TRY(gemm(fc_grad_gemm()));
+    DS_TRY(tat_wqkv_grad());  // (+ the fc weight gradient)
     if (gd.pre_conv_w && dwp_main()) DS_TRY(gemm(dwp_gemm()));
 #ifdef DSTAGNN_RACEBUG_NOFORK
     // deliberately racy build (make racebug -> abtest/racebug; tests/test_gpu_knobs.py::

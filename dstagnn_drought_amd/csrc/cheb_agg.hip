@@ -860,7 +860,7 @@ struct SddmmL {
         done = true;
       }
     }
-    static const bool nopf = getenv("DSTAGNN_SDDMM_NOPF") && atoi(getenv("DSTAGNN_SDDMM_NOPF")) != 0;
+    static const bool nopf = env_flag("DSTAGNN_SDDMM_NOPF", false);
     if constexpr (NQ <= 6 && KM <= 3) {
       if (nopf) {
         if (l.lds > (64u << 10)) {
@@ -933,7 +933,7 @@ int op_cheb_agg_fwd(const ChebAg& a0, hipStream_t st) {
   DS_TRY(check(a0));
   const ChebAg a = with_order(a0);
   // T <= 16: sample pairs per wave (cheb_agg_fwd2_kernel; DSTAGNN_AGG_PAIR=0: one sample)
-  static const bool pair_env = !getenv("DSTAGNN_AGG_PAIR") || atoi(getenv("DSTAGNN_AGG_PAIR")) != 0;
+  static const bool pair_env = env_flag("DSTAGNN_AGG_PAIR", true);
   if (pair_env && a.T <= 16 && a.F * a.T <= 512)
     dispatch<Fwd2L>(nq_of(a.F * a.T), km_of(a.K), Launch{a, dim3(grid_rows((int64_t)((a.B + 1) / 2) * a.N)), 0, st});
   else
@@ -952,8 +952,8 @@ int op_cheb_agg_sddmm(const ChebAg& a0, hipStream_t st) {
   const int FT = a.F * a.T;
   // T <= 16: sample pairs per wave (cheb_agg_sddmm2_kernel; DSTAGNN_SDDMM_PAIR=0: one sample)
   // (DSTAGNN_SDDMM_NOPF=1 names a variant of the one-sample kernel: it implies PAIR=0)
-  static const bool pair_env = (!getenv("DSTAGNN_SDDMM_PAIR") || atoi(getenv("DSTAGNN_SDDMM_PAIR")) != 0) &&
-                               !(getenv("DSTAGNN_SDDMM_NOPF") && atoi(getenv("DSTAGNN_SDDMM_NOPF")) != 0);
+  static const bool pair_env = env_flag("DSTAGNN_SDDMM_PAIR", true) &&
+                               !env_flag("DSTAGNN_SDDMM_NOPF", false);
   const bool pair = pair_env && a.T <= 16 && FT <= 512 && 2 * sddmm_lds_bytes(a.K, a.F, a.T) <= (160u << 10);
   if (pair) {
     dispatch<Sddmm2L>(nq_of(FT), km_of(a.K),
@@ -970,7 +970,7 @@ int op_cheb_agg_sddmm(const ChebAg& a0, hipStream_t st) {
 int op_cheb_agg_spmm_t(const ChebAg& a0, hipStream_t st) {
   DS_TRY(check(a0));
   const ChebAg a = with_order(a0);
-  static const bool pair_env = !getenv("DSTAGNN_AGG_PAIR") || atoi(getenv("DSTAGNN_AGG_PAIR")) != 0;
+  static const bool pair_env = env_flag("DSTAGNN_AGG_PAIR", true);
   if (pair_env && a.T <= 16 && a.T * a.C <= 512) {  // sample pairs per wave (cheb_agg_spmm_t2_kernel)
     dispatch<SpmmT2L>(nq_of(a.T * a.C), km_of(a.K), Launch{a, dim3(grid_rows((int64_t)((a.B + 1) / 2) * a.N)), 0, st});
     DS_CHECK_LAUNCH();

@@ -338,65 +338,6 @@ __global__ __launch_bounds__(256) void flash_dk_kernel(ChebFl a) {
   }
 }
 
-// backward: dM_k[i,j] = A_pa[i,j] sum_b dz_b[i,j] on the A_pa support.  One wave per (k, j),
-// lanes over the batch (B <= 128); P recomputed by a 32-long dot product per (b, i, j).
-__global__ __launch_bounds__(256) void flash_mask_grad_kernel(ChebFl a) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (wid >= (int64_t)a.K * a.N) return;
-  const int j = (int)(wid % a.N), k = (int)(wid / a.N);
-  const float* Mk = a.mask[k];
-  float* dM = a.dmask[k];
-  if (!dM) return;
-  // per lane: K'_j, lse_j and c_j of its batch elements b = lane + 64 bb (loaded once per column)
-  constexpr int kMaxBB = 2;
-  const int nb = min(kMaxBB, (a.B + 63) / 64);
-  float kv[kMaxBB][32], lse[kMaxBB], cj[kMaxBB];
-#pragma unroll
-  for (int bb = 0; bb < kMaxBB; ++bb) {
-    const int b = min(lane + 64 * bb, a.B - 1);
-    const int bk = b * a.K + k;
-    const float* kr = a.qk + (int64_t)b * a.N * a.ld + k * 32 + a.kd + (int64_t)j * a.ld;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const float4 v = *reinterpret_cast<const float4*>(kr + 4 * u);
-      kv[bb][4 * u] = v.x; kv[bb][4 * u + 1] = v.y; kv[bb][4 * u + 2] = v.z; kv[bb][4 * u + 3] = v.w;
-    }
-    lse[bb] = a.lse[(int64_t)bk * a.N + j];
-    cj[bb] = a.cc[(int64_t)bk * a.N + j];
-  }
-  for (int q = a.apa_ptr[j]; q < a.apa_ptr[j + 1]; ++q) {
-    const int i = a.apa_row[q];
-    const int64_t o = (int64_t)i * a.N + j;
-    const float w = a.apa[o];
-    int pt = -1;  // the T-support entry (i, j), if any
-    for (int p = a.csc_ptr[j]; p < a.csc_ptr[j + 1]; ++p)
-      if (a.csc_row[p] == i) pt = p;
-    float s = 0.f;
-    for (int bb = 0; bb < nb; ++bb) {
-      const int b = lane + 64 * bb;
-      if (b >= a.B) break;
-      const int bk = b * a.K + k;
-      const float* Q = a.qk + (int64_t)b * a.N * a.ld + k * 32;
-      const float z = dot32(Q + (int64_t)i * a.ld, kv[bb]) * a.scale + w * Mk[o];
-      const float P = __expf(z - lse[bb]);
-      const float dzs = pt >= 0 ? a.dzs[(int64_t)bk * a.nnz + pt] : 0.f;
-      s += dzs - P * cj[bb];
-    }
-    s = wave_sum(s);
-    if (lane == 0) dM[o] = w * s;
-  }
-}
-
-// dM_k = 0 off the A_pa support: every (N,N) mask gradient in one launch (hipMemsetAsync ran at
-// ~0.2 TB/s here, 0.4 ms per 67 MB mask at N = 4096)
-__global__ __launch_bounds__(256) void flash_zero_kernel(ChebFl a) {
-  float* d = a.dmask[blockIdx.y];
-  if (!d) return;
-  const int64_t NN = (int64_t)a.N * a.N;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < NN; e += (int64_t)gridDim.x * 256) d[e] = 0.f;
-}
-
 unsigned grid_waves(int64_t waves) { return (unsigned)cdiv64(waves, 4); }
 
 // ---------------------------------------------------------------------------------------
@@ -540,8 +481,8 @@ __device__ __forceinline__ void lds16(const float* X, int row, int c0, float (&v
 // strip's support (CSC for dK', CSR with the CSR-ordered dzs_r for dQ').
 //   dK'_j = s (sum_{i in supp(j)} dzs_ij Q'_i - c_j sum_i P_ij Q'_i)
 //   dQ'_i = s (sum_{j in supp_row(i)} dzs_ij K'_j - sum_j P_ij c_j K'_j)
-// WPE: the register budget as waves per SIMD (4: no spill; 5: 5 workgroups per CU — the PEMS08
-// grid of 1 152 workgroups in one round — at ~22 spilled dwords per lane; DSTAGNN_FLASH_DQK_WPE);
+// WPE: the register budget as waves per SIMD (4: no spill; 5 — the PEMS08 grid of 1 152
+// workgroups in one round, at ~22 spilled dwords per lane — measured equal and dropped);
 // 1 (no constraint) for 3 / 4 tiles per wave
 template <int kSmallTiles, int WPE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void flash_small_dqk_kernel(ChebFl a) {
@@ -1055,7 +996,7 @@ int op_flash_dqk(const ChebFl& a0, hipStream_t st) {
   a.sig_v = sg.v;
   const int nt = (a.N + 31) >> 5;
   // N <= 192: two strips per workgroup (flash_small_dqk2_kernel; DSTAGNN_FLASH_DQK2=0: one)
-  static const bool dqk2 = !getenv("DSTAGNN_FLASH_DQK2") || atoi(getenv("DSTAGNN_FLASH_DQK2")) != 0;
+  static const bool dqk2 = env_flag("DSTAGNN_FLASH_DQK2", true);
   if (a.am && dqk2 && nt <= 6) {
     const int ns = (nt + 1) / 2;
     const size_t lds = (std::max<size_t>((size_t)nt * 32 * 32, kRedF) + 2 * (size_t)nt * 32 + 2 * (size_t)kStripE2 + 65) *
@@ -1075,17 +1016,12 @@ int op_flash_dqk(const ChebFl& a0, hipStream_t st) {
     const size_t lds = (std::max<size_t>((size_t)nt * 32 * 32, kRedF) + 2 * (size_t)nt * 32 + 2 * (size_t)kStripE) *
                        sizeof(float);
     const dim3 grid((unsigned)(2 * (int64_t)a.B * a.K * nt));
-    static const bool wpe5 = getenv("DSTAGNN_FLASH_DQK_WPE") && atoi(getenv("DSTAGNN_FLASH_DQK_WPE")) == 5;
     switch ((nt + 3) / 4) {  // tiles per wave
-#define DS_DQK(T) case T: \
-      if (wpe5) { DS_TRY(allow_lds(flash_small_dqk_kernel<T, 5>, lds)); \
-                  hipLaunchKernelGGL((flash_small_dqk_kernel<T, 5>), grid, dim3(256), lds, st, a); } \
-      else { DS_TRY(allow_lds(flash_small_dqk_kernel<T, 4>, lds)); \
-             hipLaunchKernelGGL((flash_small_dqk_kernel<T, 4>), grid, dim3(256), lds, st, a); } \
-      break;
-      DS_DQK(1) DS_DQK(2)
-#undef DS_DQK
-      // 3 / 4 tiles per wave (N > 256): the register budget of 4 or 5 waves would spill
+      case 1: DS_TRY(allow_lds(flash_small_dqk_kernel<1, 4>, lds));
+        hipLaunchKernelGGL((flash_small_dqk_kernel<1, 4>), grid, dim3(256), lds, st, a); break;
+      case 2: DS_TRY(allow_lds(flash_small_dqk_kernel<2, 4>, lds));
+        hipLaunchKernelGGL((flash_small_dqk_kernel<2, 4>), grid, dim3(256), lds, st, a); break;
+      // 3 / 4 tiles per wave (N > 256): the register budget of 4 waves would spill
       case 3: DS_TRY(allow_lds(flash_small_dqk_kernel<3, 1>, lds));
         hipLaunchKernelGGL((flash_small_dqk_kernel<3, 1>), grid, dim3(256), lds, st, a); break;
       case 4: DS_TRY(allow_lds(flash_small_dqk_kernel<4, 1>, lds));
@@ -1105,12 +1041,9 @@ int op_flash_dqk(const ChebFl& a0, hipStream_t st) {
 }
 
 int op_flash_mask_grad(const ChebFl& a, hipStream_t st) {
-  // row-wise: every row of dM_k written by one wave (zeros off the A_pa support included);
-  // DSTAGNN_FLASH_MASK_COLS=1 keeps the column-wise kernel + zeroing pass (A/B)
-  static const bool cols = getenv("DSTAGNN_FLASH_MASK_COLS") && atoi(getenv("DSTAGNN_FLASH_MASK_COLS")) != 0;
-  if (a.papa && a.apa_idx && !cols) {  // small graphs: one thread per element, P from the forward
+  if (a.papa && a.apa_idx) {  // small graphs: one thread per element, P from the forward
     // the batch sum over the wave's lanes (B <= 128; DSTAGNN_FLASH_MASK2=0: one thread per sum)
-    static const bool m2 = !getenv("DSTAGNN_FLASH_MASK2") || atoi(getenv("DSTAGNN_FLASH_MASK2")) != 0;
+    static const bool m2 = env_flag("DSTAGNN_FLASH_MASK2", true);
     if (m2 && a.B <= 128)
       hipLaunchKernelGGL(flash_small_mask2_kernel, dim3((unsigned)cdiv64((int64_t)a.K * a.N * a.N, 256)), dim3(256), 0,
                          st, a);
@@ -1120,16 +1053,8 @@ int op_flash_mask_grad(const ChebFl& a, hipStream_t st) {
     DS_CHECK_LAUNCH();
     return 0;
   }
-  if (!cols) {
-    hipLaunchKernelGGL(flash_mask_grad_rows_kernel, dim3(grid_waves((int64_t)a.K * a.N)), dim3(256), 0, st, a);
-    DS_CHECK_LAUNCH();
-    return 0;
-  }
-  const int64_t NN = (int64_t)a.N * a.N;
-  hipLaunchKernelGGL(flash_zero_kernel, dim3((unsigned)std::min<int64_t>(cdiv64(NN, 256), 4096), (unsigned)a.K),
-                     dim3(256), 0, st, a);
-  DS_CHECK_LAUNCH();
-  hipLaunchKernelGGL(flash_mask_grad_kernel, dim3(grid_waves((int64_t)a.K * a.N)), dim3(256), 0, st, a);
+  // row-wise: every row of dM_k written by one wave (zeros off the A_pa support included)
+  hipLaunchKernelGGL(flash_mask_grad_rows_kernel, dim3(grid_waves((int64_t)a.K * a.N)), dim3(256), 0, st, a);
   DS_CHECK_LAUNCH();
   return 0;
 }

@@ -13,6 +13,24 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------
+// The one way the library reads a DSTAGNN_* environment variable (the only getenv in csrc/;
+// tests/test_knob_inventory_cpu.py scans for these calls).  Every call site keeps the result
+// in a `static const`, so a variable is read once per process.
+//   env_str:  the raw value, nullptr when unset (presence switches, the CU mask)
+//   env_flag: unset -> dflt, else "non-zero integer"
+//   env_int:  unset -> dflt, else the integer
+// ---------------------------------------------------------------------------------
+inline const char* env_str(const char* name) { return getenv(name); }
+inline bool env_flag(const char* name, bool dflt) {
+  const char* v = env_str(name);
+  return v ? atoi(v) != 0 : dflt;
+}
+inline int env_int(const char* name, int dflt) {
+  const char* v = env_str(name);
+  return v ? atoi(v) : dflt;
+}
+
+// ---------------------------------------------------------------------------------
 // Unsigned fast division by a runtime constant (round-up magic, valid for n < 2^31).
 // q = (umulhi(n, m) + n) >> s   with s = ceil(log2 d), m = 2^32 (2^s - d) / d + 1.
 // ---------------------------------------------------------------------------------

@@ -316,7 +316,6 @@ __global__ __launch_bounds__(1024) void skinny_dw_kernel(SkinnyK s) {
 
 // A's k map sends every aligned k quad to 4 contiguous, 16-B aligned floats (skinny_dw_kernel A4)
 bool skinny_a4(const SkinnyK& s) {
-  static const bool on = !getenv("DSTAGNN_SKINNY_A4") || atoi(getenv("DSTAGNN_SKINNY_A4")) != 0;
   const GemmK& g = s.g;
   const bool quads = g.ak.s0 == 1 && (g.ak.d == 0x80000000u || g.ak.d % 4 == 0) && g.ak.s1 % 4 == 0;
   bool rows = reinterpret_cast<uintptr_t>(g.A) % 16 == 0 && g.abias % 4 == 0 && g.K % 4 == 0 && s.kpw % 4 == 0;
@@ -324,7 +323,7 @@ bool skinny_a4(const SkinnyK& s) {
     const uint32_t q = g.am.d == 0x80000000u ? 0u : (uint32_t)m / g.am.d, r = (uint32_t)m - q * g.am.d;
     rows = ((int64_t)r * g.am.s0 + (int64_t)q * g.am.s1) % 4 == 0;
   }
-  return on && quads && rows;
+  return quads && rows;
 }
 
 void launch_skinny(const SkinnyK& s, hipStream_t st) {
@@ -388,8 +387,8 @@ Prof g_prof;
 // range to about this many (448: best of the round-3-end same-box sweep over 256 / 320 / 448,
 // tools/knob_sweep.sh; 1 = never split: every tiled reduction in one fixed order, so
 // a per-sample result is bit-identical at any batch size — the skinny weight-gradient kernel
-// splits regardless, see plan_skinny); DSTAGNN_SPLITK_TARGET overrides
-int g_splitk_target = getenv("DSTAGNN_SPLITK_TARGET") ? atoi(getenv("DSTAGNN_SPLITK_TARGET")) : 448;
+// splits regardless, see plan_skinny); dstagnn_set_splitk_target overrides
+int g_splitk_target = 448;
 // operand precision of every GEMM: 0 = fp32 (v_mfma_f32_32x32x2_f32, the reference's
 // arithmetic), 1 = bf16 operands rounded to nearest even with fp32 accumulation
 // (v_mfma_f32_32x32x16_bf16) — an opt-in variant, see gemm_set_bf16
@@ -491,25 +490,9 @@ int gemm_prof_records(dstagnn_prof_record* out, int cap) {
 
 namespace {
 
-// persistent tile loop knobs: DSTAGNN_GEMM_PERSIST=1 turns it on; _MIN = fewest tiles that take
-// it; _WPC = workgroups per CU of its grid
-bool gemm_persist_on() {
-  static const bool on = getenv("DSTAGNN_GEMM_PERSIST") && atoi(getenv("DSTAGNN_GEMM_PERSIST")) != 0;
-  return on;
-}
-int64_t gemm_persist_min_tiles() {
-  static const int64_t v = getenv("DSTAGNN_GEMM_PERSIST_MIN") ? atoll(getenv("DSTAGNN_GEMM_PERSIST_MIN")) : 384;
-  return v;
-}
-int gemm_persist_wpc() {
-  static const int v = getenv("DSTAGNN_GEMM_PERSIST_WPC") ? std::max(1, atoi(getenv("DSTAGNN_GEMM_PERSIST_WPC"))) : 1;
-  return v;
-}
-constexpr int kCUs = 256;  // MI355X compute units
-
 // one problem's launch plan: its kernel descriptor and the kernel configuration it needs
 bool gemm_log_on() {
-  static const bool on = getenv("DSTAGNN_GEMM_LOG") != nullptr;
+  static const bool on = env_str("DSTAGNN_GEMM_LOG") != nullptr;
   return on;
 }
 
@@ -519,15 +502,11 @@ struct Plan {
   int best, va, vb, ns;
   bool akc, bnc, ktwo, hot, acc2;
   bool skinny;  // runs as skinny_dw_kernel (sk), never grouped
-  bool persist; // runs as gemm_f32_persist_kernel: k.count tiles over `wgs` workgroups
-  uint32_t wgs;
   SkinnyK sk;
   bool same_kernel(const Plan& o) const {
     return !skinny && !o.skinny && best == o.best && va == o.va && vb == o.vb && ns == o.ns && akc == o.akc &&
-           bnc == o.bnc && ktwo == o.ktwo && hot == o.hot && acc2 == o.acc2 && persist == o.persist;
+           bnc == o.bnc && ktwo == o.ktwo && hot == o.hot && acc2 == o.acc2;
   }
-  // workgroups of this problem's grid slice (before the padding to a multiple of 8)
-  uint32_t slice() const { return persist ? wgs : k.count; }
   // split-K slab floats this plan takes from the workspace
   size_t ws_floats() const {
     if (skinny) return (size_t)(sk.nwg + sk.ngrp) * sk.P4;
@@ -537,13 +516,13 @@ struct Plan {
 
 // the skinny kernel's plan (plan_gemm has filled pl.k); false: keep the tiled kernel
 bool plan_skinny(Plan& pl, float* ws, size_t ws_floats, hipStream_t st) {
-  static const bool on = !getenv("DSTAGNN_GEMM_SKINNY") || atoi(getenv("DSTAGNN_GEMM_SKINNY")) != 0;
+  static const bool on = env_flag("DSTAGNN_GEMM_SKINNY", true);
   const GemmK& k = pl.k;
   if (!on || g_bf16 || !ws || k.batch != 1 || k.M > kSkMaxM || k.N > 32 || k.K < kSkinnyMinK) return false;
   SkinnyK& s = pl.sk;
   s = SkinnyK{};
   // <= kSkMaxWg workgroups of kSkWaves waves, a multiple of 4 k per wave
-  static const int env_kpw = getenv("DSTAGNN_SKINNY_KPW") ? atoi(getenv("DSTAGNN_SKINNY_KPW")) : 0;
+  static const int env_kpw = env_int("DSTAGNN_SKINNY_KPW", 0);
   s.kpw = (int)std::max<int64_t>(4, cdiv64(cdiv64(k.K, (int64_t)kSkMaxWg * kSkWaves), 4) * 4);
   if (env_kpw > 0) s.kpw = (int)std::max<int64_t>(s.kpw, cdiv64(env_kpw, 4) * 4);
   s.nwg = (int)cdiv64(k.K, (int64_t)kSkWaves * s.kpw);
@@ -551,12 +530,13 @@ bool plan_skinny(Plan& pl, float* ws, size_t ws_floats, hipStream_t st) {
   s.P4 = (s.P + 3) / 4 * 4;
   // one fold level while the last workgroup reads <= DSTAGNN_SKINNY_FOLD1_KB of partials (one
   // CU pulls ~150 GB/s: 512 KB ~ 3.5 us), else groups of kSkGroup first
-  static const int fold1_kb = getenv("DSTAGNN_SKINNY_FOLD1_KB") ? atoi(getenv("DSTAGNN_SKINNY_FOLD1_KB")) : 512;
+  static const int fold1_kb = env_int("DSTAGNN_SKINNY_FOLD1_KB", 512);
   s.ngrp = (int64_t)s.nwg * s.P4 * 4 > (int64_t)fold1_kb * 1024 ? (int)cdiv64(s.nwg, kSkGroup) : 0;
   if ((size_t)(s.nwg + s.ngrp) * s.P4 > ws_floats || (reinterpret_cast<uintptr_t>(ws) & 15) != 0) return false;
   s.cnt = stream_counters(st, 1 + s.ngrp);
   if (!s.cnt) return false;
-  s.stop = getenv("DSTAGNN_SKINNY_STOP") ? atoi(getenv("DSTAGNN_SKINNY_STOP")) : 0;
+  static const int stop = env_int("DSTAGNN_SKINNY_STOP", 0);
+  s.stop = stop;
   pl.k.splitk = 1;
   pl.k.kchunk = k.K;
   s.g = pl.k;
@@ -570,11 +550,8 @@ bool plan_skinny(Plan& pl, float* ws, size_t ws_floats, hipStream_t st) {
 }
 
 // a split-K workgroup reducing more than this many k in one fp32 chain takes the two-level
-// accumulation (gemm_kern.hpp ACC2); DSTAGNN_GEMM_ACC2_MINK overrides
-int acc2_min_k() {
-  static const int v = getenv("DSTAGNN_GEMM_ACC2_MINK") ? atoi(getenv("DSTAGNN_GEMM_ACC2_MINK")) : 1024;
-  return v;
-}
+// accumulation (gemm_kern.hpp ACC2)
+constexpr int kAcc2MinK = 1024;
 
 // Plan one problem (tile shape, split-K, DMA widths, stages); ws: its split-K slab space.
 int plan_gemm(const Gemm& g, float* ws, size_t ws_floats, Plan* out) {
@@ -587,8 +564,6 @@ int plan_gemm(const Gemm& g, float* ws, size_t ws_floats, Plan* out) {
   GemmK& k = pl.k;
   k = GemmK{};
   pl.skinny = false;
-  pl.persist = false;
-  pl.wgs = 0;
   const int Nk = g.N + (g.ones_out ? 1 : 0);  // kernel columns (the column-sum column last)
   k.M = g.M; k.N = Nk; k.K = g.K; k.batch = g.batch;
   k.nload = g.N; k.ones_out = g.ones_out; k.ones_stride = (int32_t)g.ones_stride;
@@ -634,8 +609,8 @@ int plan_gemm(const Gemm& g, float* ws, size_t ws_floats, Plan* out) {
   k.ws = ws;
 
   // optional overrides for tuning sweeps (tools/gemm_sweep.py)
-  static const int env_cfg = getenv("DSTAGNN_GEMM_CFG") ? atoi(getenv("DSTAGNN_GEMM_CFG")) : -1;
-  static const int env_split = getenv("DSTAGNN_GEMM_SPLITK") ? atoi(getenv("DSTAGNN_GEMM_SPLITK")) : 0;
+  static const int env_cfg = env_int("DSTAGNN_GEMM_CFG", -1);
+  static const int env_split = env_int("DSTAGNN_GEMM_SPLITK", 0);
   // Tile choice, from the measured sweep (tools/gemm_sweep.py, profiles/): at these
   // sizes a block's latency (setup, first-tile load, epilogue) dominates, so the small
   // 64x64 tile (most blocks, 4 resident per CU) wins unless N is skinny (<= 32: 128x32)
@@ -654,8 +629,7 @@ int plan_gemm(const Gemm& g, float* ws, size_t ws_floats, Plan* out) {
 
   // split-K when the grid leaves CUs idle and the reduction is long
   int splitk = 1;
-  static const int min_grid = getenv("DSTAGNN_SPLITK_MINGRID") ? atoi(getenv("DSTAGNN_SPLITK_MINGRID")) : 128;
-  static const int min_k = getenv("DSTAGNN_SPLITK_MINK") ? atoi(getenv("DSTAGNN_SPLITK_MINK")) : 512;
+  constexpr int min_grid = 128, min_k = 512;
   if (g.K > 0 && blocks < min_grid && g.K >= min_k && ws) {
     // (a per-call target yields to the global "split-K off" = 1 of the deterministic tests)
     const int target = (g.splitk_target > 0 && g_splitk_target != 1) ? g.splitk_target : g_splitk_target;
@@ -683,28 +657,21 @@ int plan_gemm(const Gemm& g, float* ws, size_t ws_floats, Plan* out) {
   // split-K launches only: their K slices are the long chains (weight gradients), and a GEMM
   // that does not split keeps one summation order under every tile configuration (a B=1 and a
   // B=32 call may pick different tiles: per-sample results stay bit-identical, test_batch_consistency)
-  pl.acc2 = !g_bf16 && (best == 0 || best == 2) && splitk > 1 && kchunk > acc2_min_k();
-  // persistent tile loop (gemm_persist_body): no split-K, no column-sum column, fp32, the 64x64 /
-  // 128x32 tiles, enough tiles that a workgroup walks several; the workgroup count is set per
-  // launch (persist_slices)
-  pl.persist = gemm_persist_on() && splitk == 1 && !g.ones_out && !g.omap && !g_bf16 && (best == 0 || best == 2) && g.K > 0 &&
-               (int64_t)blocks >= gemm_persist_min_tiles();
+  pl.acc2 = !g_bf16 && (best == 0 || best == 2) && splitk > 1 && kchunk > kAcc2MinK;
   pl.akc = !g.ak.two && g.ak.s0 == 1;
   pl.bnc = !g.bn.two && g.bn.s0 == 1;
   pl.ktwo = g.ak.two || g.bk.two;
   pl.hot = g.hot != 0;
-  // DSTAGNN_GEMM_DMA16: bit 0 allows the 16-B DMA for A, bit 1 for B (default both)
-  static const int env_v = getenv("DSTAGNN_GEMM_DMA16") ? atoi(getenv("DSTAGNN_GEMM_DMA16")) : 3;
-  pl.va = (env_v & 1) ? dma_width(g.A + g.a_off, g.am, g.M, g.ak, g.az, pl.akc) : 1;
-  pl.vb = (env_v & 2) ? dma_width(g.B + g.b_off, g.bn, g.N, g.bk, g.bz, !pl.bnc) : 1;
+  pl.va = dma_width(g.A + g.a_off, g.am, g.M, g.ak, g.az, pl.akc);
+  pl.vb = dma_width(g.B + g.b_off, g.bn, g.N, g.bk, g.bz, !pl.bnc);
   // LDS pipeline depth: two stages, compile-time (gemm_glds_body)
   pl.ns = 2;
   k.nstage = pl.ns;
   if (gemm_log_on()) {
     // one "[gemm]" line per kernel launch (run_gemm_group joins a group's problems with " | ")
-    snprintf(pl.log, sizeof(pl.log), "M=%d N=%d K=%d batch=%d cfg=%d splitk=%d akc=%d bnc=%d ktwo=%d blocks=%lld ns=%d va=%d vb=%d bf=%d ones=%d acc2=%d persist=%d",
+    snprintf(pl.log, sizeof(pl.log), "M=%d N=%d K=%d batch=%d cfg=%d splitk=%d akc=%d bnc=%d ktwo=%d blocks=%lld ns=%d va=%d vb=%d bf=%d ones=%d acc2=%d",
              g.M, Nk, g.K, g.batch, best, splitk, (int)pl.akc, (int)pl.bnc, (int)pl.ktwo, (long long)blocks * splitk,
-             pl.ns, pl.va, pl.vb, g_bf16, g.ones_out ? 1 : 0, (int)pl.acc2, (int)pl.persist);
+             pl.ns, pl.va, pl.vb, g_bf16, g.ones_out ? 1 : 0, (int)pl.acc2);
   }
   return 0;
 }
@@ -722,31 +689,10 @@ uint32_t make_group(const GemmK* const* ks, const uint32_t* counts, int n, GemmG
   return at;
 }
 
-// the workgroups of each persistent problem of one launch: about kCUs * wpc in all, shared in
-// proportion to the problems' k-tile work, each a multiple of 8 (every XCD walks its eighth of
-// the tile order) and at most the problem's tile count rounded up to 8
-void persist_slices(Plan* const* ps, int n, int ktiles_per_tile0 = -1) {
-  double work[kGroupMax], tot = 0;
-  for (int p = 0; p < n; ++p) {
-    const GemmK& k = ps[p]->k;
-    const int kt = ktiles_per_tile0 > 0 ? ktiles_per_tile0 : (k.K + BKMAX - 1) / BKMAX;
-    work[p] = (double)k.count * std::max(1, kt);
-    tot += work[p];
-  }
-  const double slots = (double)kCUs * gemm_persist_wpc();
-  for (int p = 0; p < n; ++p) {
-    const GemmK& k = ps[p]->k;
-    uint32_t w = (uint32_t)std::max(8.0, slots * work[p] / std::max(tot, 1.0));
-    w = std::min<uint32_t>((w + 7u) & ~7u, (k.count + 7u) & ~7u);
-    ps[p]->wgs = std::max<uint32_t>(8u, w & ~7u);
-  }
-}
-
 int launch_plans(Plan* const* ps, int n, hipStream_t st) {
   const GemmK* ks[kGroupMax];
   uint32_t counts[kGroupMax];
-  if (ps[0]->persist) persist_slices(ps, n);
-  for (int p = 0; p < n; ++p) { ks[p] = &ps[p]->k; counts[p] = ps[p]->slice(); }
+  for (int p = 0; p < n; ++p) { ks[p] = &ps[p]->k; counts[p] = ps[p]->k.count; }
   GemmG gg;
   const uint32_t grid = make_group(ks, counts, n, &gg);
   const StreamSig sg = peek_stream_sig(st);
@@ -758,13 +704,8 @@ int launch_plans(Plan* const* ps, int n, hipStream_t st) {
       {{gemm_c0_k0_bf, gemm_c0_k1_bf}, {gemm_c1_k0_bf, gemm_c1_k1_bf}, {gemm_c2_k0_bf, gemm_c2_k1_bf}},
       {{gemm_c0_k0_a2, gemm_c0_k1_a2}, {nullptr, nullptr}, {gemm_c2_k0_a2, gemm_c2_k1_a2}}};
   const Plan& pl = *ps[0];
-  if (pl.persist) {
-    static const Unit punits[3][2] = {{gemm_p0_k0, gemm_p0_k1}, {nullptr, nullptr}, {gemm_p2_k0, gemm_p2_k1}};
-    punits[pl.best][pl.ktwo ? 1 : 0](gg, dim3(grid), pl.akc, pl.bnc, pl.va, pl.vb, false, st);
-  } else {
-    const int var = pl.acc2 ? 2 : (g_bf16 ? 1 : 0);
-    units[var][pl.best][pl.ktwo ? 1 : 0](gg, dim3(grid), pl.akc, pl.bnc, pl.va, pl.vb, pl.hot, st);
-  }
+  const int var = pl.acc2 ? 2 : (g_bf16 ? 1 : 0);
+  units[var][pl.best][pl.ktwo ? 1 : 0](gg, dim3(grid), pl.akc, pl.bnc, pl.va, pl.vb, pl.hot, st);
   DS_CHECK_LAUNCH();
   if (sg.p) DS_TRY(stream_sig_sent(st, sg));
   return 0;
@@ -893,11 +834,7 @@ int run_gemm_kcat(const Gemm* gs, int n, hipStream_t st) {
     }
   }
   GemmG gg{};
-  Plan* p0 = &plans[0];
-  int kts = 0;
-  for (int p = 0; p < n; ++p) kts += (gs[p].K + BKMAX - 1) / BKMAX;
-  if (p0->persist) persist_slices(&p0, 1, kts);
-  const uint32_t grid = (p0->slice() + 7u) & ~7u;
+  const uint32_t grid = (plans[0].k.count + 7u) & ~7u;
   gg.start[0] = (uint32_t)n;  // K-concatenated
   for (int p = 1; p < 4; ++p) gg.start[p] = grid;
   for (int p = 0; p < n; ++p) gg.k[p] = plans[p].k;
@@ -909,10 +846,7 @@ int run_gemm_kcat(const Gemm* gs, int n, hipStream_t st) {
       {{gemm_c0_k0, gemm_c0_k1}, {gemm_c1_k0, gemm_c1_k1}, {gemm_c2_k0, gemm_c2_k1}},
       {{gemm_c0_k0_bf, gemm_c0_k1_bf}, {gemm_c1_k0_bf, gemm_c1_k1_bf}, {gemm_c2_k0_bf, gemm_c2_k1_bf}}};
   const Plan& pl = plans[0];
-  if (pl.persist)
-    gemm_p2_k0(gg, dim3(grid), pl.akc, pl.bnc, pl.va, pl.vb, false, st);
-  else
-    units[g_bf16 ? 1 : 0][pl.best][pl.ktwo ? 1 : 0](gg, dim3(grid), pl.akc, pl.bnc, pl.va, pl.vb, false, st);
+  units[g_bf16 ? 1 : 0][pl.best][pl.ktwo ? 1 : 0](gg, dim3(grid), pl.akc, pl.bnc, pl.va, pl.vb, false, st);
   DS_CHECK_LAUNCH();
   if (sg.p) DS_TRY(stream_sig_sent(st, sg));
   if (gemm_log_on()) {

@@ -814,7 +814,7 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_bwd_fused_kernel(GtuFusedBwdA
 }  // namespace
 
 bool gtu_fused_fwd_ok(int C, int T) {
-  static const bool on = !getenv("DSTAGNN_GTU_FUSED") || atoi(getenv("DSTAGNN_GTU_FUSED")) != 0;  // default on
+  static const bool on = env_flag("DSTAGNN_GTU_FUSED", true);  // default on
   return on && C == kGC && T == kGT;
 }
 
@@ -854,7 +854,7 @@ int op_gtu_fused_fwd(const GtuFusedArgs& a, hipStream_t st) {
 }
 
 bool gtu_fused_bwd_ok(int C, int T) {
-  static const bool on = !getenv("DSTAGNN_GTU_FUSED_BWD") || atoi(getenv("DSTAGNN_GTU_FUSED_BWD")) != 0;  // default on
+  static const bool on = env_flag("DSTAGNN_GTU_FUSED_BWD", true);  // default on
   return on && C == kGC && T == kGT;
 }
 int64_t gtu_fused_bwd_part_floats(int64_t BN) {

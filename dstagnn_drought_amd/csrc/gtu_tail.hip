@@ -124,7 +124,7 @@ __device__ __forceinline__ float fast_tanh(float x) {
 constexpr int kNT = 64;
 constexpr int kU = 8;
 
-// KC / KT: compile-time C and T (0 = runtime) so the index divisions fold.  WL: the fcmy
+// WL: the fcmy
 // weight (T x 3T-12) staged in LDS; false for long series (GAMBIA T=144: 242 KB), where
 // it is read through L1/L2 instead.
 //
@@ -167,10 +167,10 @@ __device__ __forceinline__ void col_sums_over_c(const float* v, int C, int T, in
 
 // PH: 0 = fused, 2 = split path: from the GEMM's tc (in tco) to the output (the gates run
 // in gtu_gates_kernel)
-template <int KC, int KT, bool WL, int PH = 0, int NT = kNT>
+template <bool WL, int PH = 0, int NT = kNT>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 8))) void gtu_tail_fwd_kernel(GtuTailArgs a) {
   extern __shared__ float lds[];
-  const int C = KC ? KC : a.C, T = KT ? KT : a.T, S = 3 * T - 12, CT = C * T, C2 = 2 * C, CS = C * S;
+  const int C = a.C, T = a.T, S = 3 * T - 12, CT = C * T, C2 = 2 * C, CS = C * S;
   const TailFwdLds L(C, T, WL, PH != 2, NT);
   const int SP = L.SP, CP = L.CP;
   float* Gs = lds + L.gs;    // [c][SP]
@@ -407,10 +407,10 @@ struct TailBwdLds {
 
 // PH: 0 = fused, 1 = split path: LN / residual backward to dtc only (dG by a GEMM, the
 // gates backward in gtu_gates_bwd_kernel)
-template <int KC, int KT, bool WL, int PH = 0, int NT = kNT>
+template <bool WL, int PH = 0, int NT = kNT>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 8))) void gtu_tail_bwd_kernel(GtuTailArgs a) {
   extern __shared__ float lds[];
-  const int C = KC ? KC : a.C, T = KT ? KT : a.T, S = 3 * T - 12, CT = C * T, C2 = 2 * C;
+  const int C = a.C, T = a.T, S = 3 * T - 12, CT = C * T, C2 = 2 * C;
   const TailBwdLds L(C, T, WL, PH == 0, NT);
   const int SP = L.SP, CP = L.CP;
   float* dxh = lds + L.dxh;   // CT  (LN dxhat, then dtc)
@@ -603,7 +603,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 8))) void
 
 // ---------------------------------------------------------------------------------------
 // Compile-time C / T fused tail (the C = 32, T = 12 blocks of PEMS04/07/08): the arithmetic of
-// gtu_tail_{fwd,bwd}_kernel<C, T, true, 0, NT> element for element (bit-identical outputs),
+// gtu_tail_{fwd,bwd}_kernel<true> element for element (bit-identical outputs),
 // restructured for latency.  The per-node kernels above walk a node in phases that each
 // start with their own global loads (fwd: conv rows, then X, then x; bwd: dout / r / mu / rs,
 // dout again for the LN partials, tco, then the conv rows of each GTU), and a node's lifetime
@@ -616,8 +616,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 8))) void
 // FIRST (compile-time a.first): no uniform branch among the node's loads — a branch there made
 // the compiler wait for every load issued before it (vmcnt(0) at the join), splitting the one
 // round into three dependent ones
-template <int C, int T, int NT, int W, bool FIRST>  // W: occupancy floor for the register allocator (waves / SIMD)
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(W, 8))) void gtu_tail_fwd_ct_kernel(GtuTailArgs a) {
+template <int C, int T, int NT, bool FIRST>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 8))) void gtu_tail_fwd_ct_kernel(GtuTailArgs a) {
   constexpr int S = 3 * T - 12, CT = C * T, C2 = 2 * C, CS = C * S, SP = S + 1, CP = C + 1;
   constexpr int P = T < NT ? NT / T : 1, NRED = P * T > NT ? P * T : NT;
   constexpr int NG = (CS + NT - 1) / NT, NE = (CT + NT - 1) / NT;
@@ -778,8 +778,8 @@ __device__ __forceinline__ void tail_gate_bwd(float* dconv, int ks, int off, int
   }
 }
 
-template <int C, int T, int NT, int W, bool FIRST>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(W, 8))) void gtu_tail_bwd_ct_kernel(GtuTailArgs a) {
+template <int C, int T, int NT, bool FIRST>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 8))) void gtu_tail_bwd_ct_kernel(GtuTailArgs a) {
   constexpr int S = 3 * T - 12, CT = C * T, SP = S + 1, CP = C + 1;
   constexpr int P = T < NT ? NT / T : 1, NRED2 = 2 * (P * T > NT ? P * T : NT);
   constexpr int SH0 = C * SP > T * CP ? C * SP : T * CP, SH = SH0 > NRED2 ? SH0 : NRED2;
@@ -988,48 +988,30 @@ int rows_gemm(const float* A, int lda, const float* B, Idx2 bk, Idx2 bn, float* 
 }  // namespace
 
 // split (gates | GEMM | tail) when the weight does not fit LDS, or from T >= 20 on
-// (measured: SYN T=24 step 60.9 -> 57.7 ms split; PEMS08 T=12 0.91 fused vs 0.99 split);
-// DSTAGNN_TAIL_SPLIT_T overrides the threshold (0 = always split, used by the parity runs)
+// (measured: SYN T=24 step 60.9 -> 57.7 ms split; PEMS08 T=12 0.91 fused vs 0.99 split)
 constexpr int kTailSplitT = 20;
 // The compile-time tail kernels also at C = 32, T = 24 (the synthetic N = 4096 config) instead
 // of the split path: SYN B=32 40.2 -> 37.4-37.7 ms/step same box (2 x 2 runs,
 // tools/gpu_check.sh cfgab); DSTAGNN_TAIL_CT24=0 keeps the split path (A/B)
 static bool tail_ct24(const GtuTailArgs& a) {
-  static const bool on = !getenv("DSTAGNN_TAIL_CT24") || atoi(getenv("DSTAGNN_TAIL_CT24")) != 0;
+  static const bool on = env_flag("DSTAGNN_TAIL_CT24", true);
   return on && a.C == 32 && a.T == 24;
 }
+// the one-round-of-loads compile-time kernels: C = 32 at T = 12 (and T = 24, tail_ct24)
+static bool tail_ct(const GtuTailArgs& a) { return tail_ct24(a) || (a.C == 32 && a.T == 12); }
 bool tail_split_fwd(const GtuTailArgs& a) {
-  static const int split_t = getenv("DSTAGNN_TAIL_SPLIT_T") ? atoi(getenv("DSTAGNN_TAIL_SPLIT_T")) : kTailSplitT;
-  if (tail_ct24(a) && split_t > 0) return false;
-  return fwd_lds(a, true) > 32 * 1024 || a.T >= split_t;
+  if (tail_ct24(a)) return false;
+  return fwd_lds(a, true) > 32 * 1024 || a.T >= kTailSplitT;
 }
 bool tail_split_bwd(const GtuTailArgs& a) {
-  static const int split_t = getenv("DSTAGNN_TAIL_SPLIT_T") ? atoi(getenv("DSTAGNN_TAIL_SPLIT_T")) : kTailSplitT;
-  if (tail_ct24(a) && split_t > 0) return false;
-  return bwd_lds(a, true) > 32 * 1024 || a.T >= split_t;
+  if (tail_ct24(a)) return false;
+  return bwd_lds(a, true) > 32 * 1024 || a.T >= kTailSplitT;
 }
 
 // threads per node in the split path's residual / LayerNorm kernels: a long series' node
 // tile (C*T = 4608 at GAMBIA) holds ~74 KB of LDS, so only two workgroups fit a CU; 256
-// threads each keep 8 waves per CU in flight instead of 2 (DSTAGNN_TAIL_NT=64 for A/B)
-int split_nt() {
-  static const int nt = getenv("DSTAGNN_TAIL_NT") ? atoi(getenv("DSTAGNN_TAIL_NT")) : 256;
-  return nt == 64 ? 64 : 256;
-}
-
-// threads per node of the fused C=32/T=12 kernels (DSTAGNN_TAIL_FUSED_NT = 64 | 128 | 256):
-// 256 measured 0.868 vs 0.873 ms/step for 64 (PEMS08 block, 2 x 200 steps each)
-int fused_nt() {
-  static const int nt = getenv("DSTAGNN_TAIL_FUSED_NT") ? atoi(getenv("DSTAGNN_TAIL_FUSED_NT")) : 256;
-  return nt;
-}
-
-// the one-round-of-loads C = 32 / T = 12 kernels (DSTAGNN_TAIL_CT=0: the phase-by-phase ones;
-// 2: register cap for 5 waves / SIMD)
-int tail_ct() {
-  static const int v = getenv("DSTAGNN_TAIL_CT") ? atoi(getenv("DSTAGNN_TAIL_CT")) : 1;
-  return v;
-}
+// threads each keep 8 waves per CU in flight instead of 2
+constexpr int kSplitNT = 256;
 
 bool gtu_tail_bwd_split(int C, int T) {
   GtuTailArgs a;
@@ -1050,77 +1032,51 @@ int op_gtu_tail_fwd(const GtuTailArgs& a, hipStream_t st) {
       DS_CHECK_LAUNCH();
     }
     DS_TRY(rows_gemm(a.G, S, a.fcmy_w, idx1(1), idx1(S), a.tco, a.T, a.BN * a.C, a.T, S, a.fcmy_b, st));
-    if (split_nt() == 64)
-      return launch_node_kernel(gtu_tail_fwd_kernel<0, 0, false, 2, 64>, fwd_lds(a, false, false, 64), a, st, 64);
-    return launch_node_kernel(gtu_tail_fwd_kernel<0, 0, false, 2, 256>, fwd_lds(a, false, false, 256), a, st, 256);
+    return launch_node_kernel(gtu_tail_fwd_kernel<false, 2, kSplitNT>, fwd_lds(a, false, false, kSplitNT), a, st, kSplitNT);
   }
-  const size_t lds = fwd_lds(a, true);
-  if (tail_ct24(a)) {
+  if (tail_ct(a)) {
     const dim3 g(node_grid(a.BN));
-    if (a.first) hipLaunchKernelGGL((gtu_tail_fwd_ct_kernel<32, 24, 256, 1, true>), g, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((gtu_tail_fwd_ct_kernel<32, 24, 256, 1, false>), g, dim3(256), 0, st, a);
-    DS_CHECK_LAUNCH();
-    return 0;
-  }
-  if (a.C == 32 && a.T == 12 && tail_ct()) {
-    const dim3 g(node_grid(a.BN));
-    if (tail_ct() == 2) {
-      if (a.first) hipLaunchKernelGGL((gtu_tail_fwd_ct_kernel<32, 12, 256, 5, true>), g, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((gtu_tail_fwd_ct_kernel<32, 12, 256, 5, false>), g, dim3(256), 0, st, a);
+    if (a.T == 24) {
+      if (a.first) hipLaunchKernelGGL((gtu_tail_fwd_ct_kernel<32, 24, 256, true>), g, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((gtu_tail_fwd_ct_kernel<32, 24, 256, false>), g, dim3(256), 0, st, a);
     } else {
-      if (a.first) hipLaunchKernelGGL((gtu_tail_fwd_ct_kernel<32, 12, 256, 1, true>), g, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((gtu_tail_fwd_ct_kernel<32, 12, 256, 1, false>), g, dim3(256), 0, st, a);
+      if (a.first) hipLaunchKernelGGL((gtu_tail_fwd_ct_kernel<32, 12, 256, true>), g, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((gtu_tail_fwd_ct_kernel<32, 12, 256, false>), g, dim3(256), 0, st, a);
     }
     DS_CHECK_LAUNCH();
     return 0;
   }
-  if (a.C == 32 && a.T == 12) {
-    switch (fused_nt()) {
-      case 128: return launch_node_kernel(gtu_tail_fwd_kernel<32, 12, true, 0, 128>, fwd_lds(a, true, true, 128), a, st, 128);
-      case 256: return launch_node_kernel(gtu_tail_fwd_kernel<32, 12, true, 0, 256>, fwd_lds(a, true, true, 256), a, st, 256);
-      default: return launch_node_kernel(gtu_tail_fwd_kernel<32, 12, true>, lds, a, st);
-    }
-  }
-  return launch_node_kernel(gtu_tail_fwd_kernel<0, 0, true>, lds, a, st);
+  return launch_node_kernel(gtu_tail_fwd_kernel<true>, fwd_lds(a, true), a, st);
 }
 
-static int64_t fold_wgs() {
-  static const int v = getenv("DSTAGNN_TAIL_FOLD_WGS") ? atoi(getenv("DSTAGNN_TAIL_FOLD_WGS")) : 2048;
-  return v > 0 ? v : 2048;
-}
-static bool tail_generic() {
-  static const bool generic = getenv("DSTAGNN_TAIL_GENERIC") && atoi(getenv("DSTAGNN_TAIL_GENERIC")) != 0;
-  return generic;
-}
+// workgroups of the folding backward's grid-stride grid
+constexpr int64_t kTailFoldWgs = 2048;
 // the compile-time C / T backward with one node per workgroup, which folds its partial sums
-// in-kernel (DSTAGNN_TAIL_FOLD=0: colsum2d launches instead)
+// in-kernel (DSTAGNN_TAIL_FOLD=1; default: colsum2d launches instead)
 bool gtu_tail_bwd_folds(const GtuTailArgs& a) {
-  static const bool on = getenv("DSTAGNN_TAIL_FOLD") && atoi(getenv("DSTAGNN_TAIL_FOLD")) != 0;
-  if (!on || tail_split_bwd(a) || tail_generic() || !a.gpart) return false;
-  return tail_ct24(a) || (a.C == 32 && a.T == 12 && tail_ct());
+  static const bool on = env_flag("DSTAGNN_TAIL_FOLD", false);
+  if (!on || tail_split_bwd(a) || !a.gpart) return false;
+  return tail_ct(a);
 }
 
 int op_gtu_tail_bwd(const GtuTailArgs& a0, hipStream_t st) {
-  const bool generic = tail_generic();
   GtuTailArgs a = a0;
   a.fold = a0.fold && gtu_tail_bwd_folds(a0) && a0.fold_ws;
   if (a.fold) {
-    a.fold_cnt = stream_counters(st, (int)cdiv64(std::min<int64_t>(a.BN, fold_wgs()), 64) + 1);
+    a.fold_cnt = stream_counters(st, (int)cdiv64(std::min<int64_t>(a.BN, kTailFoldWgs), 64) + 1);
     if (!a.fold_cnt) a.fold = 0;
   }
   if (tail_split_bwd(a)) {  // long series: LN / residual | dG GEMM | gates
     if (!a.dG) { set_last_error("gtu_tail: split backward needs the dG scratch"); return DSTAGNN_E_ARG; }
     const int S = 3 * a.T - 12;
     if (bwd_lds(a, false, false) > kLdsMax) { set_last_error("gtu_tail: C*T too large for LDS"); return DSTAGNN_E_SHAPE; }
-    if (split_nt() == 64)
-      DS_TRY(launch_node_kernel(gtu_tail_bwd_kernel<0, 0, false, 1, 64>, bwd_lds(a, false, false, 64), a, st, 64));
-    else
-      DS_TRY(launch_node_kernel(gtu_tail_bwd_kernel<0, 0, false, 1, 256>, bwd_lds(a, false, false, 256), a, st, 256));
+    DS_TRY(launch_node_kernel(gtu_tail_bwd_kernel<false, 1, kSplitNT>, bwd_lds(a, false, false, kSplitNT), a, st, kSplitNT));
     DS_TRY(rows_gemm(a.dtc, a.T, a.fcmy_w, idx1(S), idx1(1), a.dG, S, a.BN * a.C, S, a.T, nullptr, st));
     const int nchunk = (a.T + 6 + kGsW - 1) / kGsW;  // rows of the longest padded output (ks = 7)
     const int64_t nwg = a.BN * 3 * nchunk;
     if (nwg >= (1ll << 31)) { set_last_error("gtu_gates_bwd: grid too large"); return DSTAGNN_E_SHAPE; }
-    bool vec = a.C % 4 == 0 && !(getenv("DSTAGNN_GATES_BWD_SCALAR") && atoi(getenv("DSTAGNN_GATES_BWD_SCALAR")));
+    static const bool scalar = env_flag("DSTAGNN_GATES_BWD_SCALAR", false);
+    bool vec = a.C % 4 == 0 && !scalar;
     for (int q = 0; q < 3; ++q)
       vec = vec && (reinterpret_cast<uintptr_t>(a.conv[q]) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.dconv_pad[q]) & 15) == 0;
     hipLaunchKernelGGL(gtu_gates_bwd_kernel, dim3((unsigned)nwg), dim3(256), sizeof(float) * kGsW * (a.C + 1), st, a,
@@ -1128,35 +1084,19 @@ int op_gtu_tail_bwd(const GtuTailArgs& a0, hipStream_t st) {
     DS_CHECK_LAUNCH();
     return 0;
   }
-  const size_t lds = bwd_lds(a, true);
-  // folding: fewer workgroups, each walking several nodes, so the per-workgroup hand-off (store
-  // drain, barrier, ticket) is paid once per ~3 nodes (one node per workgroup: 36 -> 72 us)
-  const unsigned fold_grid = (unsigned)std::min<int64_t>(a.BN, fold_wgs());
-  if (tail_ct24(a) && !generic) {
-    const dim3 g(a.fold ? fold_grid : node_grid(a.BN));
-    if (a.first) hipLaunchKernelGGL((gtu_tail_bwd_ct_kernel<32, 24, 256, 1, true>), g, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((gtu_tail_bwd_ct_kernel<32, 24, 256, 1, false>), g, dim3(256), 0, st, a);
-    DS_CHECK_LAUNCH();
-    return 0;
-  }
-  if (a.C == 32 && a.T == 12 && !generic && tail_ct()) {
-    const dim3 g(a.fold ? fold_grid : node_grid(a.BN));
-    if (tail_ct() == 2) {
-      if (a.first) hipLaunchKernelGGL((gtu_tail_bwd_ct_kernel<32, 12, 256, 5, true>), g, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((gtu_tail_bwd_ct_kernel<32, 12, 256, 5, false>), g, dim3(256), 0, st, a);
+  if (tail_ct(a)) {
+    // folding: fewer workgroups, each walking several nodes, so the per-workgroup hand-off (store
+    // drain, barrier, ticket) is paid once per ~3 nodes (one node per workgroup: 36 -> 72 us)
+    const dim3 g(a.fold ? (unsigned)std::min<int64_t>(a.BN, kTailFoldWgs) : node_grid(a.BN));
+    if (a.T == 24) {
+      if (a.first) hipLaunchKernelGGL((gtu_tail_bwd_ct_kernel<32, 24, 256, true>), g, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((gtu_tail_bwd_ct_kernel<32, 24, 256, false>), g, dim3(256), 0, st, a);
     } else {
-      if (a.first) hipLaunchKernelGGL((gtu_tail_bwd_ct_kernel<32, 12, 256, 1, true>), g, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((gtu_tail_bwd_ct_kernel<32, 12, 256, 1, false>), g, dim3(256), 0, st, a);
+      if (a.first) hipLaunchKernelGGL((gtu_tail_bwd_ct_kernel<32, 12, 256, true>), g, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((gtu_tail_bwd_ct_kernel<32, 12, 256, false>), g, dim3(256), 0, st, a);
     }
     DS_CHECK_LAUNCH();
     return 0;
   }
-  if (a.C == 32 && a.T == 12 && !generic) {
-    switch (fused_nt()) {
-      case 128: return launch_node_kernel(gtu_tail_bwd_kernel<32, 12, true, 0, 128>, bwd_lds(a, true, true, 128), a, st, 128);
-      case 256: return launch_node_kernel(gtu_tail_bwd_kernel<32, 12, true, 0, 256>, bwd_lds(a, true, true, 256), a, st, 256);
-      default: return launch_node_kernel(gtu_tail_bwd_kernel<32, 12, true>, lds, a, st);
-    }
-  }
-  return launch_node_kernel(gtu_tail_bwd_kernel<0, 0, true>, lds, a, st);
+  return launch_node_kernel(gtu_tail_bwd_kernel<true>, bwd_lds(a, true), a, st);
 }

@@ -776,7 +776,7 @@ __global__ __launch_bounds__(256) void ln_bwd_v4_kernel(LnBwd a) {
 static bool al16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static bool map4(const Idx2& m) { return m.s0 % 4 == 0 && m.s1 % 4 == 0; }
 static bool ln_v4_env() {
-  static const bool on = !getenv("DSTAGNN_LN_V4") || atoi(getenv("DSTAGNN_LN_V4")) != 0;  // default on
+  static const bool on = env_flag("DSTAGNN_LN_V4", true);  // default on
   return on;
 }
 static bool ln_fwd_v4_ok(const LnFwd& a) {
@@ -1855,7 +1855,7 @@ static int allow_lds(const void* kernel, size_t bytes) {
 // the matrix-core TAt kernels: T in {4, 8, 12, 16}, d_k = d_v = 32, 16-B aligned operands
 // (float4 rows); DSTAGNN_TAT_MFMA=0 keeps the VALU wave kernels (A/B switch)
 static bool tat_mfma_ok(int T, int dk, int dv, std::initializer_list<const float*> ptrs) {
-  static const bool off = getenv("DSTAGNN_TAT_MFMA") && atoi(getenv("DSTAGNN_TAT_MFMA")) == 0;
+  static const bool off = !env_flag("DSTAGNN_TAT_MFMA", true);
   if (off || dk != kTmD || dv != kTmD || T % 4 != 0 || T < 4 || T > 16) return false;
   for (const float* p : ptrs)
     if (reinterpret_cast<uintptr_t>(p) % 16 != 0) return false;
@@ -1988,12 +1988,6 @@ static void launch_ln_fwd(const LnFwd& a, dim3 grid, hipStream_t st) {
   else hipLaunchKernelGGL((ln_fwd_kernel<VPT, 3>), grid, dim3(256), 0, st, a);
 }
 
-// DSTAGNN_LN_WG=0: long rows keep the wave-per-row kernels (A/B)
-static bool ln_wg_rows() {
-  static const bool on = !getenv("DSTAGNN_LN_WG") || atoi(getenv("DSTAGNN_LN_WG")) != 0;
-  return on;
-}
-
 int op_ln_fwd(const LnFwd& a, hipStream_t st) {
   if (a.nsrc < 1 || a.nsrc > 3 || a.L < 1) { set_last_error("ln_fwd: 1..3 sources, L >= 1"); return DSTAGNN_E_ARG; }
   dim3 grid((unsigned)cdiv64(a.R, 4));
@@ -2013,7 +2007,7 @@ int op_ln_fwd(const LnFwd& a, hipStream_t st) {
   else if (vpt <= 4) launch_ln_fwd<4>(a, grid, st);
   else if (vpt <= 8) launch_ln_fwd<8>(a, grid, st);
   else if (vpt <= 16) launch_ln_fwd<16>(a, grid, st);
-  else if (ln_wg_rows() && a.L <= 4096) {  // a workgroup per row (ln_fwd_wg_kernel)
+  else if (a.L <= 4096) {  // a workgroup per row (ln_fwd_wg_kernel)
     const dim3 g((unsigned)a.R);
     const int v = (int)cdiv64(a.L, 256);
 #define DS_LNW(V) \
@@ -2023,7 +2017,6 @@ int op_ln_fwd(const LnFwd& a, hipStream_t st) {
     if (v <= 8) { DS_LNW(8) } else { DS_LNW(16) }
 #undef DS_LNW
   }
-  else if (vpt <= 64) launch_ln_fwd<64>(a, grid, st);
   else { set_last_error("ln_fwd: row too long"); return DSTAGNN_E_SHAPE; }
   DS_CHECK_LAUNCH();
   return 0;
@@ -2055,11 +2048,10 @@ int op_ln_bwd(const LnBwd& a, hipStream_t st) {
   else if (vpt <= 4) hipLaunchKernelGGL((ln_bwd_kernel<4, false>), grid, dim3(256), 0, st, a);
   else if (vpt <= 8) hipLaunchKernelGGL((ln_bwd_kernel<8, false>), grid, dim3(256), 0, st, a);
   else if (vpt <= 16) hipLaunchKernelGGL((ln_bwd_kernel<16, false>), grid, dim3(256), 0, st, a);
-  else if (ln_wg_rows() && a.L <= 4096) {
+  else if (a.L <= 4096) {
     if (a.L <= 2048) hipLaunchKernelGGL((ln_bwd_wg_kernel<8>), dim3((unsigned)a.R), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((ln_bwd_wg_kernel<16>), dim3((unsigned)a.R), dim3(256), 0, st, a);
   }
-  else if (vpt <= 64) hipLaunchKernelGGL((ln_bwd_kernel<64, false>), grid, dim3(256), 0, st, a);
   else { set_last_error("ln_bwd: row too long"); return DSTAGNN_E_SHAPE; }
   DS_CHECK_LAUNCH();
   return 0;
@@ -2072,9 +2064,8 @@ int op_colsum_multi(const float* const* ins, float* const* outs, int nsrc, int64
   if (nsrc < 1 || nsrc > 4) { set_last_error("colsum: 1..4 sources"); return DSTAGNN_E_ARG; }
   if (E > 16384) { set_last_error("colsum: O*I > 16384"); return DSTAGNN_E_SHAPE; }
   if (A <= 0 || O <= 0) return 0;
-  static const int kCsBlocks = getenv("DSTAGNN_COLSUM_BLOCKS") ? atoi(getenv("DSTAGNN_COLSUM_BLOCKS")) : 256;
-  static const bool two_stage = getenv("DSTAGNN_COLSUM_2STAGE") && atoi(getenv("DSTAGNN_COLSUM_2STAGE")) != 0;
-  if (I <= kCsW && !two_stage) {
+  constexpr int kCsBlocks = 256;
+  if (I <= kCsW) {
     Colsum2dArgs c;
     for (int q = 0; q < nsrc; ++q) { c.in[q] = ins[q]; c.out[q] = outs[q]; }
     c.nsrc = nsrc; c.A = A; c.O = O; c.I = I; c.E = E;

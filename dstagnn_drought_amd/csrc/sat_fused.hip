@@ -212,7 +212,7 @@ bool sb_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
 }  // namespace
 
 bool sat_ln_bwd_fused_ok(int64_t D, int64_t K2) {
-  static const bool on = getenv("DSTAGNN_SATLN_FUSED") && atoi(getenv("DSTAGNN_SATLN_FUSED")) != 0;
+  static const bool on = env_flag("DSTAGNN_SATLN_FUSED", false);
   return on && D == kSbD && K2 == kSbK;
 }
 int64_t sat_ln_bwd_fused_wgs(int64_t R) { return cdiv64(R, kSbRows); }

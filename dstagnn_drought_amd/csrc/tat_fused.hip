@@ -132,13 +132,10 @@ __device__ __forceinline__ void tf_mma(floatx4 (&acc)[3][NJ], const float4 (&av)
 // a full L2 round trip (the products ran at ~1/3 of the CU's MFMA rate, -DDSTAGNN_TF_TIMING).  A
 // ring of DB chunks keeps DB - 1 chunks of B loads in flight; A (LDS) is double-buffered.  Chunk
 // indices past NC are clamped (the redundant loads hit L2) and their products skipped.
-#ifndef DSTAGNN_TF_DB
-#define DSTAGNN_TF_DB 4  // (-DDSTAGNN_TF_DB=2: one chunk of look-ahead, the round-5 pipeline; A/B builds)
-#endif
-template <int NJ, int DB = DSTAGNN_TF_DB>
+template <int NJ>
 __device__ __forceinline__ void tf_gemm_rows48(floatx4 (&acc)[3][NJ], const float* A, int LA, int NC, int i, int q,
                                                const float* const (&wp)[NJ]) {
-  static_assert(DB % 2 == 0 && DB >= 2, "even ring: the A ping-pong slot is d % 2");
+  constexpr int DB = 4;  // (even: the A ping-pong slot is d % 2)
   float4 b[DB][NJ], av[2][3];
 #pragma unroll
   for (int d = 0; d < DB - 1; ++d) tf_ld_b(b[d], wp, 16 * min(d, NC - 1));
@@ -619,11 +616,7 @@ __global__ __launch_bounds__(64 * W, 1) void tat_fused_bwd_kernel(TatFusedBwdArg
   // the u / dO tiles: a raw barrier behind the LDS stores only — __syncthreads() would also
   // drain vmcnt, i.e. wait here for the 55 KB of Q|K|V rows (and the softmax / d re_At
   // operands) that are first used after the LayerNorm phase; they stay in flight through it
-#ifdef DSTAGNN_TF_SYNC_A0
-  __syncthreads();  // (A/B builds: the round-5 barrier)
-#else
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
   TF_MARK(1);
   TF_MARK(2);
   // ---- A1. LayerNorm(N) backward of the wave's RPW rows at once (ln_bwd_kernel's arithmetic) --
@@ -1029,8 +1022,8 @@ size_t tat_fused_bwd_lds(int NP, int W) {
 
 bool tat_fused_fwd_ok(int N, int T, int h, int dk, int dv) {
   // DSTAGNN_TAT_FUSED=0 (or DSTAGNN_TAT_MFMA=0, the VALU attention A/B): the unfused launches
-  static const bool env = (!getenv("DSTAGNN_TAT_FUSED") || atoi(getenv("DSTAGNN_TAT_FUSED")) != 0) &&
-                          (!getenv("DSTAGNN_TAT_MFMA") || atoi(getenv("DSTAGNN_TAT_MFMA")) != 0);
+  static const bool env = env_flag("DSTAGNN_TAT_FUSED", true) &&
+                          env_flag("DSTAGNN_TAT_MFMA", true);
   // (T >= 7 for any block — check_dims — so of the 48-row tilings only T = 8, 12, 16 occur)
   return env && h == kTfH && dk == kTfD && dv == kTfD && N >= 1 && N <= kTfNmax && (T == 8 || T == 12 || T == 16);
 }
@@ -1064,7 +1057,7 @@ int op_tat_fused_fwd(const TatFusedArgs& a0, hipStream_t st) {
   using Kern = void (*)(TatFusedArgs);
   Kern k = nullptr;
   // DSTAGNN_TF_WAVES=4|8: the forward's workgroup size (A/B)
-  static const int waves = getenv("DSTAGNN_TF_WAVES") && atoi(getenv("DSTAGNN_TF_WAVES")) == 4 ? 4 : 8;
+  static const int waves = env_int("DSTAGNN_TF_WAVES", 8) == 4 ? 4 : 8;
 #define TF_NTW(TT, WW)                                        \
   switch (ntw) {                                              \
     case 1: k = tat_fused_fwd_kernel<TT, 1, WW>; break;       \
@@ -1102,7 +1095,7 @@ int op_tat_fused_fwd(const TatFusedArgs& a0, hipStream_t st) {
 }
 
 bool tat_fused_bwd_ok(int N, int T, int h, int dk, int dv, int F, int res_mode) {
-  static const bool env = !getenv("DSTAGNN_TAT_FUSED_BWD") || atoi(getenv("DSTAGNN_TAT_FUSED_BWD")) != 0;
+  static const bool env = env_flag("DSTAGNN_TAT_FUSED_BWD", true);
   if (!env || !tat_fused_fwd_ok(N, T, h, dk, dv)) return false;
   // the in-kernel res_att fold needs whole workgroups per sample
   return res_mode != DSTAGNN_RES_BCAST || ((int64_t)F * T) % kTfRows == 0;
@@ -1135,7 +1128,7 @@ int op_tat_fused_bwd(const TatFusedBwdArgs& a0, hipStream_t st) {
   a.sig_v = sg.v;
   const int64_t grid = cdiv64(a.BFT, kTfRows);
   // DSTAGNN_TF_BWD_WAVES=4|8: the backward's workgroup size (A/B)
-  static const int waves = getenv("DSTAGNN_TF_BWD_WAVES") && atoi(getenv("DSTAGNN_TF_BWD_WAVES")) == 4 ? 4 : 8;
+  static const int waves = env_int("DSTAGNN_TF_BWD_WAVES", 8) == 4 ? 4 : 8;
   // (NP > 256 stays on four waves: eight would spill — 256 VGPRs each at two waves per SIMD)
   const int wv = waves == 8 && (a.NP / 16 + 3) / 4 < 5 ? 8 : 4;
   const size_t lds = tat_fused_bwd_lds(a.NP, wv);

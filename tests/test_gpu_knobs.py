@@ -40,6 +40,12 @@ a subprocess (the library reads its switches once per process):
   DSTAGNN_LN_V4=0      the LayerNorm rows of 256 / 512 / 1024 floats by the scalar wave-per-row kernels
                        instead of the float4 ones
   DSTAGNN_DWP_MAIN=1   the pre_conv weight gradient on the main stream instead of the side stream
+  DSTAGNN_SIDE_STREAM=0  everything on the caller's stream, no fork / join (the serialised path of
+                       the profiling tools)
+  DSTAGNN_TAT_FUSED_BWD=0  the fused temporal-attention forward with the unfused backward launches
+                       (LayerNorm backward, GEMMs, attention backward, dE transpose)
+  DSTAGNN_CHEB_AGG=0   the Theta-first sparse Chebyshev (x Theta GEMM, then SpMM) at a geometry that
+                       takes the aggregate-first kernels by default
   DSTAGNN_DEBUG_STREAMS=1  the fork invariant asserted (block.hip Bwd::sq): no side-stream work
                        issued while a fork's signal is still pending
   DSTAGNN_DEBUG_MAIN_DELAY_US / DSTAGNN_DEBUG_SIDE_DELAY_US   race probes: a 1.5 ms busy-wait
@@ -92,7 +98,10 @@ print("KNOB_OK")
                                        ("DSTAGNN_GTU_FUSED=0", "pems08", 4), ("DSTAGNN_GTU_FUSED_BWD=0", "pems08", 4),
                                        ("DSTAGNN_SATLN_FUSED=1", "pems08", 4), ("DSTAGNN_LN_V4=0", "pems08", 4),
                                        ("DSTAGNN_DWP_MAIN=1", "pems08", 4),
-                                       ("DSTAGNN_DEBUG_STREAMS=1", "pems07+flash", 2)])
+                                       ("DSTAGNN_DEBUG_STREAMS=1", "pems07+flash", 2),
+                                       ("DSTAGNN_SIDE_STREAM=0", "pems08", 4),
+                                       ("DSTAGNN_TAT_FUSED_BWD=0", "pems08", 4),
+                                       ("DSTAGNN_CHEB_AGG=0", "pems08", 4)])
 def test_knob_path_vs_oracle(env, cfg, B):
     import torch
     if not torch.cuda.is_available():

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Tuning sweep for the strided f32-MFMA GEMM (dstagnn_gemm_f32) on the DSTAGNN block's
-GEMM shapes (PEMS08, B=32).  Each (tile config, implementation) runs in its own subprocess
-because the overrides (DSTAGNN_GEMM_CFG / DSTAGNN_GEMM_NS) are read once per process;
+GEMM shapes (PEMS08, B=32).  Each tile config runs in its own subprocess because the override
+(DSTAGNN_GEMM_CFG) is read once per process;
 every run is checked against torch.bmm.
 
     python tools/gemm_sweep.py            # full sweep, prints a table
@@ -97,8 +97,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--iters", type=int, default=20)
-    # spec = <tile config | auto>:<LDS pipeline stages: 2, 3, or auto>
-    ap.add_argument("--configs", default="auto:auto,0:2,1:2,2:2")
+    # spec = <tile config | auto>
+    ap.add_argument("--configs", default="auto,0,1,2")
     ap.add_argument("--only", default=None)
     ap.add_argument("--big", action="store_true", help="add large square steady-state probes")
     ap.add_argument("--large", action="store_true", help="add the GAMBIA / SYN large-M shapes")
@@ -115,10 +115,8 @@ def main():
         return
     table = {}
     for spec in args.configs.split(","):
-        cfg, ns = spec.split(":")
+        cfg = spec
         env = dict(os.environ)
-        if ns != "auto":
-            env["DSTAGNN_GEMM_NS"] = ns
         if cfg != "auto":
             env["DSTAGNN_GEMM_CFG"] = cfg
         env["DSTAGNN_GEMM_CHECK"] = "" if os.environ.get("DSTAGNN_NOCHECK") else "1"

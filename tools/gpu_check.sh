@@ -55,7 +55,7 @@ for s in "${S[@]}"; do
                  run serial_$c 300 rocprofv3 --kernel-trace -d gpurun_out/serial_$c -o run --output-format csv -- \
                  python3 tools/bench_configs.py $c ;;
     sweep)  run gemm_sweep 600 python tools/gemm_sweep.py ;;
-    sweep1) run gemm_sweep1 300 python tools/gemm_sweep.py --configs auto:auto --iters 50 ;;
+    sweep1) run gemm_sweep1 300 python tools/gemm_sweep.py --configs auto --iters 50 ;;
     gemmref) run gemm_ref 300 python tools/torch_gemm_ref.py ;;
     knobs)  echo "== knobs ($(date +%T))"
             # KNOB_LIST: ';'-separated env sets ("" = default), e.g. ';DSTAGNN_TAT_MFMA=0'

@@ -2,7 +2,7 @@
 # Build a variant of libdstagnn.so with extra compile definitions into scratch/<name>/ for a
 # same-box A/B (bench / traces with LD_LIBRARY_PATH=scratch/<name>; _C.so finds libdstagnn.so
 # by RUNPATH, so the variant directory on LD_LIBRARY_PATH wins).
-#   bash tools/variant_build.sh <name> -DDSTAGNN_GEMM_NS=3 ...
+#   bash tools/variant_build.sh <name> -DDSTAGNN_TF_TIMING ...
 set -eu
 cd "$(dirname "$0")/.."
 NAME=${1:?name}; shift
