@@ -22,6 +22,7 @@
 #include <map>
 #include <utility>
 #include "ops.hpp"
+#include "streams.hpp"
 
 static thread_local std::string g_last_error;
 void set_last_error(const std::string& s) { g_last_error = s; }
@@ -463,261 +464,6 @@ struct HostTimer {
 };
 
 // ------------------------------------------------------------------------------
-// side stream
-// ------------------------------------------------------------------------------
-// The backward has two dependency chains: the data gradients (dx -> ... -> d_x, each step
-// needing the previous) and the parameter gradients (weight GEMMs, bias / gamma / beta
-// column sums, split-K folds), which only read values the data chain has produced. The
-// second chain runs on a side stream (lowest priority) forked from the caller's stream
-// by events, so its kernels fill the CUs the small data-chain kernels leave idle; it has
-// its own GEMM / reduction workspaces and its inputs are never overwritten by the main
-// chain afterwards (buffers that would be are given their own allocation). One join at
-// the end. DSTAGNN_SIDE_STREAM=0 runs everything on the caller's stream.
-struct SideStream {
-  hipStream_t side = nullptr;
-  hipEvent_t ev[64] = {};
-  // ring positions and sequence numbers are claimed atomically: the SideStream is shared by
-  // every caller on the device (e.g. the autograd device thread and a forward on another
-  // thread), and two callers must never get the same slot or sequence number
-  std::atomic<uint32_t> next{0};
-  // flag words for stream-ordered write / wait-value synchronisation (see Streams)
-  static constexpr int kSlots = 4096;  // divides 2^32: the claimed counters wrap consistently
-  uint32_t* flags = nullptr;
-  std::atomic<uint32_t> gseq{0};
-  std::atomic<uint32_t> fnext{0};
-  bool ksig = true;         // fork flags written by the next main-stream kernel (DSTAGNN_KSIG=0: off)
-  bool ok = false;
-};
-
-}  // namespace
-
-// the pending kernel-written signal of this host thread (common.hpp); one at a time: a fork
-// flushes the previous one first
-namespace {
-struct PendingSig {
-  hipStream_t st = nullptr;    // the writer's (main) stream
-  hipStream_t side = nullptr;  // the waiting stream
-  uint32_t* p = nullptr;
-  uint32_t v = 0;
-};
-thread_local PendingSig t_sig;
-}  // namespace
-
-StreamSig peek_stream_sig(hipStream_t st) {
-  StreamSig s;
-  if (t_sig.p && t_sig.st == st) { s.p = t_sig.p; s.v = t_sig.v; }
-  return s;
-}
-static int sig_wait(const PendingSig& s) {
-  const hipError_t r = hipStreamWaitValue32(s.side, s.p, s.v, hipStreamWaitValueGte, 0xffffffffu);
-  if (r != hipSuccess) {
-    set_last_error(std::string("side stream: ") + hipGetErrorString(r));
-    return (int)r;
-  }
-  return 0;
-}
-int stream_sig_sent(hipStream_t st, const StreamSig& s) {
-  if (!(t_sig.p && t_sig.st == st && t_sig.p == s.p && t_sig.v == s.v)) return 0;
-  const PendingSig q = t_sig;
-  t_sig = PendingSig{};
-  return sig_wait(q);  // the writer is queued: now the side's wait
-}
-static void set_stream_sig(hipStream_t st, hipStream_t side, uint32_t* p, uint32_t v) {
-  t_sig.st = st;
-  t_sig.side = side;
-  t_sig.p = p;
-  t_sig.v = v;
-}
-int flush_stream_sig() {
-  if (!t_sig.p) return 0;
-  const PendingSig s = t_sig;
-  t_sig = PendingSig{};
-  const hipError_t r = hipStreamWriteValue32(s.st, s.p, s.v, 0);
-  if (r != hipSuccess) {
-    set_last_error(std::string("side stream: ") + hipGetErrorString(r));
-    return (int)r;
-  }
-  return sig_wait(s);
-}
-
-// DSTAGNN_DEBUG_STREAMS=1: the fork invariant check (Bwd::sq)
-static bool stream_debug() {
-  static const bool on = env_flag("DSTAGNN_DEBUG_STREAMS", false);
-  return on;
-}
-// a fork signal for `side` is pending: its writer (and so the side's wait) is not queued yet
-static bool side_sig_pending(hipStream_t side) { return t_sig.p && t_sig.side == side; }
-
-namespace {
-// Race probes (tests/test_gpu_knobs.py): DSTAGNN_DEBUG_MAIN_DELAY_US / DSTAGNN_DEBUG_SIDE_DELAY_US
-// put a bounded busy-wait kernel (<= 20 ms, one wave) on the main stream before every stage /
-// on the side stream after every fork, so a cross-stream read issued without its dependency
-// reads stale data instead of winning the race by timing (a missing fork once went unnoticed
-// because the side stream happened to reach the read late).
-__global__ void debug_delay_kernel(uint64_t ticks) {
-  const uint64_t t0 = wall_clock64();
-  while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
-}
-int debug_delay(hipStream_t q, bool on_main) {
-  static const int us_main = env_int("DSTAGNN_DEBUG_MAIN_DELAY_US", 0);
-  static const int us_side = env_int("DSTAGNN_DEBUG_SIDE_DELAY_US", 0);
-  const int us = std::min(on_main ? us_main : us_side, 20000);
-  if (us <= 0) return 0;
-  static const int rate_khz = [] {
-    int dev = 0, r = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&r, hipDeviceAttributeWallClockRate, dev) != hipSuccess)
-      r = 0;
-    return r > 0 ? r : 100000;
-  }();
-  hipLaunchKernelGGL(debug_delay_kernel, dim3(1), dim3(64), 0, q, (uint64_t)us * (uint64_t)rate_khz / 1000u);
-  DS_CHECK_LAUNCH();
-  return 0;
-}
-
-// every exit of a block op (errors included) releases a side-stream wait still queued
-struct SigFlushGuard {
-  ~SigFlushGuard() { (void)flush_stream_sig(); }
-};
-
-SideStream* side_stream_for_device() {
-  static std::mutex mu;
-  static SideStream cache[64];
-  static const bool enabled = env_flag("DSTAGNN_SIDE_STREAM", true);
-  if (!enabled) return nullptr;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-  std::lock_guard<std::mutex> lock(mu);
-  SideStream& s = cache[dev];
-  if (!s.ok) {
-    int lo = 0, hi = 0;
-    if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) lo = 0;
-    // DSTAGNN_SIDE_CUMASK=0x<32-bit pattern>: the side stream confined to the CUs the pattern
-    // selects (replicated over every 32-CU word; A/B knob: the side stream's weight-gradient
-    // GEMMs otherwise take CUs from the latency-bound main chain); no priority with a mask
-    // (hipExtStreamCreateWithCUMask takes no flags: that stream is BLOCKING, so with a caller on
-    // the legacy null stream it also serialises with it — measurements under this knob include
-    // that serialisation)
-    static const char* const cm = env_str("DSTAGNN_SIDE_CUMASK");
-    if (cm && *cm) {
-      const uint32_t pat = (uint32_t)strtoul(cm, nullptr, 0);
-      int ncu = 0;
-      if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-      std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, pat);  // one 32-bit word per 32 CUs
-      if (ncu % 32) mask.back() &= (1u << (ncu % 32)) - 1u;
-      if (hipExtStreamCreateWithCUMask(&s.side, (uint32_t)mask.size(), mask.data()) != hipSuccess) return nullptr;
-    } else if (hipStreamCreateWithPriority(&s.side, hipStreamNonBlocking, lo) != hipSuccess) {
-      return nullptr;
-    }
-    for (auto& e : s.ev)
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr;
-    s.ksig = env_flag("DSTAGNN_KSIG", true);
-    if (hipMalloc(&s.flags, sizeof(uint32_t) * SideStream::kSlots) != hipSuccess ||
-        hipMemset(s.flags, 0, sizeof(uint32_t) * SideStream::kSlots) != hipSuccess ||
-        hipDeviceSynchronize() != hipSuccess)
-      return nullptr;
-    s.ok = true;
-  }
-  return &s;
-}
-
-// One cross-stream dependency: the consumer stream's later work waits for everything the
-// producer stream had issued when the token was made.
-struct SyncTok {
-  hipEvent_t ev = nullptr;
-  int slot = -1;
-  uint32_t seq = 0;
-};
-
-// fork / join between the caller's stream and the side stream (no-ops when disabled).
-// Prices on gfx950 / ROCm 7.2 (tools/fork_probe.hip, tools/flag_sync_probe.hip, step timelines):
-// an hipEventRecord between two kernels idles the RECORDING stream ~5.6 us, while waiting for an
-// event that has already completed costs the waiting stream nothing; a stream-ordered flag write
-// (hipStreamWriteValue32 of a fresh sequence number into a device-memory flag word, after all
-// prior work of the producer stream) and a flag wait (hipStreamWaitValue32, >= that number) run
-// as small ROCclr kernels of ~4 us each on their streams.  (Flags in hipMallocSignalMemory do
-// NOT order the data: stale reads in flag_sync_probe; device memory: 0 stale reads in 600
-// rounds both ways.)  So the main chain never records an event: a dependency made BY the main
-// stream (fork) is a flag write on main + a flag wait on the side; one made by the side stream
-// (join, dx_ready) is an event recorded on the side, usually complete by the time the main
-// stream waits for it.  Flag words rotate over kSlots; numbers only grow, so a wait can only
-// be released by its own write or a later one issued behind it.
-// Kernel-written fork flags (fork_k; default, DSTAGNN_KSIG=0 for the hipStreamWriteValue32
-// above): the flag is stored by workgroup 0 of the next kernel the main stream launches that
-// carries the signal (common.hpp) — every earlier kernel of the stream has completed when it
-// starts — and the side's wait is queued right after that launch, before the side's work: the
-// writer always precedes the wait in host order (a first version queued the wait at the fork
-// and hung with a CU-masked side stream).  tools/flag_sync_probe.hip modes 4 / 5: 0 stale
-// reads in 300 rounds each way.
-// This relies on the HIP runtime setting the AQL barrier bit on every same-stream dispatch (a
-// kernel's workgroup 0 starts only once every earlier kernel of the stream has completed; true
-// for ROCm 7.2's in-order streams).  Nothing checks it at run time: after a runtime upgrade run
-// the race probes (tests/test_gpu_knobs.py, DSTAGNN_DEBUG_*_DELAY_US with the default
-// DSTAGNN_KSIG=1; tools/gpu_check.sh knobs) before trusting the flags; DSTAGNN_KSIG=0 falls
-// back to hipStreamWriteValue32.
-// Invariant (asserted under DSTAGNN_DEBUG_STREAMS=1, stream_check_side): no side-stream work is
-// issued while a fork's signal is still pending, i.e. every side wait is queued after its writer
-// and before the side work that depends on it.
-struct Streams {
-  hipStream_t st = nullptr, sd = nullptr;
-  SideStream* ss = nullptr;
-  void init(hipStream_t main) {
-    st = main;
-    ss = gemm_prof_on() ? nullptr : side_stream_for_device();
-    sd = ss ? ss->side : st;
-  }
-  static int fail(hipError_t r) {
-    set_last_error(std::string("side stream: ") + hipGetErrorString(r));
-    return (int)r;
-  }
-  int signal(hipStream_t from, SyncTok* t) {
-    *t = SyncTok{};
-    if (!ss) return 0;
-    if (from != ss->side) {  // made by the main stream: a flag write
-      t->slot = (int)(ss->fnext.fetch_add(1, std::memory_order_relaxed) % SideStream::kSlots);
-      t->seq = ss->gseq.fetch_add(1, std::memory_order_relaxed) + 1;
-      const hipError_t r = hipStreamWriteValue32(from, ss->flags + t->slot, t->seq, 0);
-      return r == hipSuccess ? 0 : fail(r);
-    }
-    t->ev = ss->ev[ss->next.fetch_add(1, std::memory_order_relaxed) % 64];  // by the side stream: an event
-    const hipError_t r = hipEventRecord(t->ev, from);
-    return r == hipSuccess ? 0 : fail(r);
-  }
-  int wait(hipStream_t to, const SyncTok& t) {
-    // the main stream about to wait for the side: a signal the side may be waiting for goes
-    // out first (else both would wait for each other)
-    if (to == st) DS_TRY(flush_stream_sig());
-    hipError_t r = hipSuccess;
-    if (t.slot >= 0)
-      r = hipStreamWaitValue32(to, ss->flags + t.slot, t.seq, hipStreamWaitValueGte, 0xffffffffu);
-    else if (t.ev)
-      r = hipStreamWaitEvent(to, t.ev, 0);
-    return r == hipSuccess ? 0 : fail(r);
-  }
-  int event_pair(hipStream_t from, hipStream_t to) {
-    if (from == to) return 0;
-    SyncTok t;
-    DS_TRY(signal(from, &t));
-    return wait(to, t);
-  }
-  int fork() {  // side sees everything the main chain issued so far
-    DS_TRY(event_pair(st, sd));
-    return sd != st ? debug_delay(sd, false) : 0;
-  }
-  // the same dependency, its flag carried by the NEXT kernel launched on the main stream (if it
-  // can carry one; else flushed).  The caller issues that main-stream launch BEFORE any side
-  // work that depends on the fork: the side's wait is queued when the signal goes out.
-  int fork_k() {
-    if (!(ss && ss->ksig && st != sd)) return fork();
-    DS_TRY(flush_stream_sig());
-    const int slot = (int)(ss->fnext.fetch_add(1, std::memory_order_relaxed) % SideStream::kSlots);
-    const uint32_t seq = ss->gseq.fetch_add(1, std::memory_order_relaxed) + 1;
-    set_stream_sig(st, sd, ss->flags + slot, seq);
-    return 0;
-  }
-  int join() { return event_pair(sd, st); }  // main waits for everything issued on the side
-};
-
-// ------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------
 struct Fwd {
@@ -736,26 +482,24 @@ struct Fwd {
   bool e_side = false;           // E = x transposed is issued on the side stream (token e_ready)
   SyncTok e_ready;
   ChebFl fl;
-  // the forward's side work (E, x Theta), forked by fork_k in run() and issued right after the
-  // Q|K|V GEMM, which carries the fork's flag
-  bool side_pending = false, side_xth_pending = false;
-  ChebIO side_io{};
-  int issue_fwd_side() {
-    if (!side_pending) return 0;
-    side_pending = false;
-    DS_TRY(flush_stream_sig());  // (no-op when the GEMM carried the flag)
-    DS_TRY(debug_delay(ks.sd, false));
+  // the TAt stage's first product (launch), and beside it the forward's side work: E (e_side)
+  // and x Theta (xth non-null) need only x and the re-laid parameters, so the fork's flag rides
+  // on that product
+  template <class Launch>
+  int fork_side(const ChebIO* xth, Launch&& launch) {
+    if (!e_side && !xth) return launch(nullptr);
+    DS_TRY(ks.fork_on(launch));
     if (e_side) {  // E = x transposed (read by the TAt LayerNorm and saved for the backward)
-      DS_TRY(op_transpose(x, s.E, m.N, (int)m.FT, m.B, (int64_t)m.N * m.FT, m.FT * m.N, 0.f, ks.sd));
+      DS_TRY(op_transpose(x, s.E, m.N, (int)m.FT, m.B, (int64_t)m.N * m.FT, m.FT * m.N, 0.f, ks.side()));
       DS_TRY(ks.signal(ks.sd, &e_ready));
     }
-    if (side_xth_pending) DS_TRY(cheb_xtheta(side_io, w.gemm_ws_side, ks.sd));
+    if (xth) DS_TRY(cheb_xtheta(*xth, w.gemm_ws_side, ks.side()));
     return 0;
   }
 
   // the whole stage as one kernel (tat_fused.hip): E read in place from x (inner block) or from
   // the EmbedT LayerNorm's output (first block); no E transpose, no intermediate round trips
-  int stage_tat_fused() {
+  int stage_tat_fused(const ChebIO* xth_side) {
     const int64_t N = m.N;
     TatFusedArgs t;
     if (m.first) {
@@ -771,11 +515,10 @@ struct Fwd {
     t.FT = m.FT; t.BFT = m.BFT; t.BN = m.BN;
     t.F = m.F; t.T = m.T; t.N = m.N; t.NP = m.NP; t.h = m.h;
     t.scale = 1.f / sqrtf((float)m.dk);
-    DS_TRY(op_tat_fused_fwd(t, st));
-    return issue_fwd_side();  // (the fork's flag, if any, rode on the fused kernel)
+    return fork_side(xth_side, [&](ForkSig* sig) { return op_tat_fused_fwd(t, st, sig); });
   }
 
-  int stage_tat() {
+  int stage_tat(const ChebIO* xth_side) {
     const int64_t N = m.N;
     // E: TAt input (B,F,T,N)
     if (m.first) {
@@ -792,7 +535,7 @@ struct Fwd {
       DS_TRY(op_transpose(x, s.E, m.N, (int)m.FT, m.B, N * m.FT, m.FT * N, 0.f, st));
     }
     // Q | K | V projections (MultiHeadAttention :92-94) as ONE GEMM over the stacked weights
-    if (m.tfused) return stage_tat_fused();
+    if (m.tfused) return stage_tat_fused(xth_side);
     {
       Gemm g;
       g.M = (int)m.BFT; g.N = (int)m.QW; g.K = m.N;
@@ -803,9 +546,8 @@ struct Fwd {
       }
       g.B = s.Wqkv; g.bk = idx1(1); g.bn = idx1(N);
       g.C = s.qkv; g.cm = idx1(m.QW); g.cn = idx1(1);
-      DS_TRY(run_gemm(g, w.gemm_ws, kGemmWs, st));
+      DS_TRY(fork_side(xth_side, [&](ForkSig* sig) { return run_gemm(g, w.gemm_ws, kGemmWs, st, sig); }));
     }
-    DS_TRY(issue_fwd_side());
     DS_TRY(op_tat_fwd(m.B, m.F, m.T, m.h, m.dk, m.dv, s.qkv, res, d.res_mode, re_at, s.att, s.ctx, st));
     // fc (:99)
     {
@@ -972,7 +714,7 @@ struct Fwd {
     return on;
   }
 
-  int stage_tail(bool /*split*/) {
+  int stage_tail() {
     if (m.gfused) {  // convolutions + gates + fcmy + residual + LN in one kernel (gtu_fused.hip)
       GtuFusedArgs g;
       g.BN = m.BN; g.C = m.C; g.T = m.T; g.first = m.first;
@@ -1009,25 +751,18 @@ struct Fwd {
   int run() {
     static const bool prof = env_str("DSTAGNN_HOST_PROFILE") != nullptr;
     HostTimer ht(prof, "fwd");
-    SigFlushGuard sig_guard;
     ks.init(st);
-    const bool split = ks.sd != st;
+    const bool split = ks.split();
     DS_TRY(stage_params());
     ht.lap("params");
     ChebIO c = cheb_io();
     // aggregate-first Chebyshev (m.agg) has no x Theta GEMM: the side stream then carries only
     // E = x transposed, which the main chain awaits by its own token (e_ready)
-    const bool side_xth = split && !m.agg;
-    const bool e_need = !m.first && !m.tfused;  // the fused TAt kernel reads x in place
-    if (split && (side_xth || e_need)) {  // x Theta needs only x and Theta: it runs beside the whole attention chain
-      DS_TRY(ks.fork_k());  // issued after the Q|K|V GEMM / fused TAt (issue_fwd_side), which carries the flag
-      side_pending = true;
-      side_xth_pending = side_xth;
-      side_io = c;
-      e_side = e_need;
-    }
+    const bool side_xth = split && !m.agg;  // x Theta needs only x and Theta: it runs beside the whole attention chain
+    e_side = split && !m.first && !m.tfused;  // (the fused TAt kernel reads x in place)
     DS_TRY(debug_delay(st, true));
-    DS_TRY(stage_tat());
+    DS_TRY(stage_tat(side_xth ? &c : nullptr));
+    DS_TRY(ks.order_err);
     ht.lap("tat");
     DS_TRY(debug_delay(st, true));
     DS_TRY(stage_preconv());
@@ -1045,7 +780,7 @@ struct Fwd {
     }
     ht.lap("cheb");
     DS_TRY(debug_delay(st, true));
-    DS_TRY(stage_tail(split));
+    DS_TRY(stage_tail());
     ht.lap("tail");
     return 0;
   }
@@ -1069,9 +804,7 @@ struct Bwd {
   Scratch& w;
   hipStream_t st;
   Streams ks;
-  hipStream_t sd = nullptr;  // side stream (== st when disabled)
   ChebFl fl;
-  bool defer_mask = false;  // stage_cheb forked the mask gradient; stage_sat issues it
   ChebFl flash_args() {
     ChebFl f = make_fl(m, p, gr, s);
     f.dzs = w.dzs; f.dzs_r = w.dzs_r; f.cc = w.cc; f.dqk = w.dqk;
@@ -1079,33 +812,16 @@ struct Bwd {
     return f;
   }
   int fork() { return ks.fork(); }
-  int fork_k() { return ks.fork_k(); }
-  // a fork_k's signal went out (or was flushed): side work may be issued
-  int fork_k_done() {
-    DS_TRY(flush_stream_sig());
-    return sd != st ? debug_delay(sd, false) : 0;
-  }
   int join() { return ks.join(); }
-  // the side stream for a launch; DSTAGNN_DEBUG_STREAMS=1 checks the fork invariant (Streams):
-  // side work issued while a fork's signal is still pending would not be ordered after the fork
-  // (its wait is not queued yet) — recorded here, returned as an error at the next stage boundary
-  int order_err = 0;
-  hipStream_t sq() {
-    if (stream_debug() && sd != st && side_sig_pending(sd) && !order_err) {
-      set_last_error("stream invariant: side-stream work issued before its fork's signal went out");
-      order_err = DSTAGNN_E_ARG;
-    }
-    return sd;
-  }
   // a point on the side stream that the main stream can wait for later (wait_side)
   SyncTok dx_ready;
   int mark_side(SyncTok* t) {
     *t = SyncTok{};
-    if (sd == st) return 0;
-    return ks.signal(sd, t);
+    if (!ks.split()) return 0;
+    return ks.signal(ks.sd, t);
   }
   int wait_side(const SyncTok& t) {
-    if (sd == st) return 0;
+    if (!ks.split()) return 0;
     return ks.wait(st, t);
   }
 
@@ -1129,7 +845,7 @@ struct Bwd {
   // outputs skipped
   int colsums(std::initializer_list<std::pair<const float*, float*>> io, int64_t A, int O, int I,
               bool on_main = false) {
-    const hipStream_t q = on_main ? st : sq();
+    const hipStream_t q = on_main ? st : ks.side();
     const float* ins[4];
     float* outs[4];
     int n = 0;
@@ -1138,15 +854,15 @@ struct Bwd {
     if (!n) return 0;
     return op_colsum_multi(ins, outs, n, A, O, I, 1, 0.f, q == st ? w.part : w.part_side, kPart, q);
   }
-  int gemm(const Gemm& g) { return run_gemm(g, w.gemm_ws, kGemmWs, st); }
+  int gemm(const Gemm& g, ForkSig* sig = nullptr) { return run_gemm(g, w.gemm_ws, kGemmWs, st, sig); }
   // side-stream weight gradients: their own split-K target — fewer K slices mean a cheaper fold
   // and fewer CUs taken from the main chain.  192: with the GTU stage fused the side stream is
   // the step's last to finish, and 192 beat the global 448 by ~8 us/step (256: ~5) in same-box A/Bs (profiles/r05_knob_sweep.txt)
   static constexpr int kSideSplitK = 192;
   int sgemm(const Gemm& g0) {
     Gemm g = g0;
-    if (sd != st && !g.splitk_target) g.splitk_target = kSideSplitK;
-    return run_gemm(g, sd == st ? w.gemm_ws : w.gemm_ws_side, kGemmWs, sq());
+    if (ks.split() && !g.splitk_target) g.splitk_target = kSideSplitK;
+    return run_gemm(g, ks.split() ? w.gemm_ws_side : w.gemm_ws, kGemmWs, ks.side());
   }
 
   // the GTU stage backward as one kernel (gtu_fused.hip): LN / residual / dropout backward, dG,
@@ -1196,8 +912,9 @@ struct Bwd {
       t.fold_ws = w.gcon_t + 2 * m.BN * m.C;
     }
     DS_TRY(op_gtu_tail_bwd(t, st));
-    DS_TRY(fork_k());
-    {
+    // --- side: LN / residual / fcmy / GTU parameter gradients (one fork; its flag rides on
+    // the GTU input-gradient launch)
+    DS_TRY(ks.fork_on([&](ForkSig* sig) -> int {
       // gpre = (X > 0) * (dX + sum_q sum_{(j',o)} dconv_pad_q[bn,t+j',o] W_q[o,c,ks-1-j']): the three
       // transposed convolutions as ONE K-concatenated product (K = 2C (3 + 5 + 7)), with the
       // tail's dX as the beta input and the ReLU backward of the Chebyshev output in the epilogue
@@ -1221,14 +938,10 @@ struct Bwd {
         TconvArgs tc;
         for (int q = 0; q < 3; ++q) { tc.dconv[q] = w.dconv[q]; tc.wflip[q] = s.Wgb[q]; tc.ks[q] = m.ks[q]; }
         tc.dX = w.dX; tc.X = s.X; tc.gpre = w.gpre; tc.M = m.BN * m.T;
-        DS_TRY(op_gtu_tconv(tc, st));
-      } else {
-        DS_TRY(run_gemm_kcat(segs, 3, st));
+        return op_gtu_tconv(tc, st, sig);
       }
-    }
-    // --- side: LN / residual / fcmy / GTU parameter gradients (one fork; its flag rides on
-    // the GTU input-gradient launch, issued first)
-    DS_TRY(fork_k_done());
+      return run_gemm_kcat(segs, 3, st, sig);
+    }));
     if (!tail_fold)
       DS_TRY(colsums({{w.gcon_t, gd.ln_g}, {w.gcon_t + m.BN * m.C, gd.ln_b}, {w.bcon_t, m.first ? gd.res_w : nullptr},
                       {w.bcon_t + m.BN * m.C, m.first ? gd.res_b : nullptr}}, m.BN, m.C, 1));
@@ -1251,31 +964,31 @@ struct Bwd {
       g.ones_out = gd.fcmy_b;
       DS_TRY(sgemm(g));
     } else {
-      DS_TRY(colsum_on(sd, w.dtc, m.BN * m.C, m.T, 1, gd.fcmy_b));
+      DS_TRY(colsum_on(ks.side(), w.dtc, m.BN * m.C, m.T, 1, gd.fcmy_b));
     }
     {
       Gemm dws[3];
       int nw = 0;
       for (int q = 0; q < 3; ++q) {
-        const int ks = m.ks[q], Tg = m.Tg[q];
+        const int kw = m.ks[q], Tg = m.Tg[q];
         const int64_t C2 = 2 * (int64_t)m.C;
         const int64_t cs = C2 * m.T;  // per-(b,n) stride of the padded dconv rows (t', o)
         if (gd.gtu_w[q]) {
           Gemm& g = dws[nw++];  // dW[o,c,j] = sum_{(bn,t')} dconv[bn,t',o] X[bn,t'+j,c]; db[o] = sum dconv[.,o]
-          g.M = (int)C2; g.N = m.C * ks; g.K = (int)(m.BN * Tg);
+          g.M = (int)C2; g.N = m.C * kw; g.K = (int)(m.BN * Tg);
           g.A = w.dconv[q]; g.am = idx1(1);
           if (compact) g.ak = idx1(C2);
-          else { g.a_off = (ks - 1) * C2; g.ak = idx2(Tg, C2, cs); }
+          else { g.a_off = (kw - 1) * C2; g.ak = idx2(Tg, C2, cs); }
           g.B = s.X; g.bk = idx2(Tg, m.C, m.CT); g.bn = idx1(1);
-          g.C = gd.gtu_w[q]; g.cm = idx1((int64_t)m.C * ks); g.cn = idx2(m.C, ks, 1);
+          g.C = gd.gtu_w[q]; g.cm = idx1((int64_t)m.C * kw); g.cn = idx2(m.C, kw, 1);
           g.ones_out = gd.gtu_b[q];
         } else {
-          DS_TRY(colsum_on(sd, w.dconv[q], compact ? m.BN * Tg : m.BN * m.T + ks - 1, (int)C2, 1, gd.gtu_b[q]));
+          DS_TRY(colsum_on(ks.side(), w.dconv[q], compact ? m.BN * Tg : m.BN * m.T + kw - 1, (int)C2, 1, gd.gtu_b[q]));
         }
       }
-      if (sd != st)
+      if (ks.split())
         for (int q = 0; q < nw; ++q) dws[q].splitk_target = kSideSplitK;
-      if (nw) DS_TRY(run_gemm_group(dws, nw, sd == st ? w.gemm_ws : w.gemm_ws_side, kGemmWs, sq()));
+      if (nw) DS_TRY(run_gemm_group(dws, nw, ks.split() ? w.gemm_ws_side : w.gemm_ws, kGemmWs, ks.side()));
     }
     return 0;
   }
@@ -1296,10 +1009,8 @@ struct Bwd {
         a.nnz = (int)m.nnz; a.wsupp = s.wsupp; a.psupp = s.psupp; a.tsupp = gr.tsupp; a.dzs = w.dzs; a.cc = w.cc;
         if (m.fsmall) { a.csc2csr = gr.csc2csr; a.dzs_r = w.dzs_r; }
       }
-      DS_TRY(fork_k());  // its flag rides on the SDDMM, issued before the side's work
-      DS_TRY(op_cheb_agg_sddmm(a, st));
-      DS_TRY(fork_k_done());
-      DS_TRY(op_cheb_agg_spmm_t(a, sq()));
+      DS_TRY(ks.fork_on([&](ForkSig* sig) { return op_cheb_agg_sddmm(a, st, sig); }));
+      DS_TRY(op_cheb_agg_spmm_t(a, ks.side()));
       DS_TRY(mark_side(&dx_ready));
       {
         Gemm g;  // dTheta[(k,f), c] = sum_{b,j,t} agg[b,j,k,f,t] g[b,j,t,c]
@@ -1314,7 +1025,7 @@ struct Bwd {
           g.C = w.dthcat; g.cm = idx2(F, KC, C); g.cn = idx1(1);
         }
         DS_TRY(sgemm(g));
-        if (!adjacent) DS_TRY(unpack_theta(w.dthcat, K, F, C, gd.theta, sq()));
+        if (!adjacent) DS_TRY(unpack_theta(w.dthcat, K, F, C, gd.theta, ks.side()));
       }
     } else if (m.sparse) {
       // dW is written on the support only; the softmax backward reads it only where
@@ -1329,7 +1040,7 @@ struct Bwd {
       // dxth = W^T g on the side stream (only the Theta / x gradients, also on the side,
       // read it), dW = (x Theta) g^T on the support on the main chain: independent products
       DS_TRY(fork());
-      DS_TRY(op_cheb_spmm_t_bwd(sp, sq()));
+      DS_TRY(op_cheb_spmm_t_bwd(sp, ks.side()));
       DS_TRY(op_cheb_sddmm_bwd(sp, st));
     } else {
       {
@@ -1362,14 +1073,10 @@ struct Bwd {
       DS_TRY(op_cheb_softmax_bwd(sm, st));
     }
     // --- side: mask and Theta gradients
-    if (m.flash && m.agg) {  // the flag rides on the flash dQ'/dK' launch (stage_sat), issued first
-      DS_TRY(fork_k());
-      defer_mask = true;
-      return 0;
-    }
+    if (m.flash && m.agg) return 0;  // (the mask gradient is forked on stage_sat's dQ'/dK' launch)
     DS_TRY(fork());
-    if (m.flash) DS_TRY(op_flash_mask_grad(fl, sq()));
-    else DS_TRY(op_cheb_mask_grad(sm, sq()));
+    if (m.flash) DS_TRY(op_flash_mask_grad(fl, ks.side()));
+    else DS_TRY(op_cheb_mask_grad(sm, ks.side()));
     if (m.agg) return 0;  // Theta and x gradients came with the aggregate-first kernels above
     {
       Gemm g;  // dTheta_cat[f,(k,c)] = sum_{b,i,t} x[b,i,f,t] dxth[b,i,t,k,c]
@@ -1386,7 +1093,7 @@ struct Bwd {
         g.C = w.dthcat; g.cm = idx1(KC); g.cn = idx1(1);
       }
       DS_TRY(sgemm(g));
-      if (!adjacent) DS_TRY(unpack_theta(w.dthcat, K, F, C, gd.theta, sq()));
+      if (!adjacent) DS_TRY(unpack_theta(w.dthcat, K, F, C, gd.theta, ks.side()));
     }
     {
       Gemm g;  // dx[b,i,f,t] += sum_{k,c} Theta_k[f,c] dxth[b,i,t,k,c]
@@ -1406,11 +1113,12 @@ struct Bwd {
   int stage_sat() {
     const float sc = 1.f / sqrtf((float)m.dk);
     const int64_t ld = 2 * m.KD;
-    if (m.flash) DS_TRY(op_flash_dqk(fl, st));  // dQ' | dK' with P tiles recomputed, no dense dz
-    if (defer_mask) {  // side: the mask gradient (stage_cheb's fork_k)
-      defer_mask = false;
-      DS_TRY(fork_k_done());
-      DS_TRY(op_flash_mask_grad(fl, sq()));
+    // dQ' | dK' with P tiles recomputed, no dense dz
+    if (m.flash && m.agg) {  // side: the mask gradient; the fork's flag rides on the dQ'/dK' launch
+      DS_TRY(ks.fork_on([&](ForkSig* sig) { return op_flash_dqk(fl, st, sig); }));
+      DS_TRY(op_flash_mask_grad(fl, ks.side()));
+    } else if (m.flash) {
+      DS_TRY(op_flash_dqk(fl, st));
     }
     if (!m.flash) {  // dQ'[b,i,k,:] = sum_j dz[b,k,i,j] K'[b,j,k,:] / sqrt(dk)
       Gemm g;
@@ -1469,11 +1177,11 @@ struct Bwd {
     }
     }
     // --- side: SAt projection, EmbedS gamma / beta / pos-embedding, pre_conv bias and weight
-    // grads; the fork's flag rides on the pre_conv data-gradient GEMM, issued first
-    DS_TRY(fork_k());
-    DS_TRY(debug_delay(st, true));
-    DS_TRY(stage_preconv());
-    DS_TRY(fork_k_done());
+    // grads; the fork's flag rides on the pre_conv data-gradient GEMM
+    DS_TRY(ks.fork_on([&](ForkSig* sig) -> int {
+      DS_TRY(debug_delay(st, true));
+      return stage_preconv(sig);
+    }));
     if (gd.sat_wq || gd.sat_wk) {  // side: [dW_Q'; dW_K'] = dqk^T Zd, then split
       Gemm g;
       g.M = (int)ld; g.N = m.D; g.K = (int)m.BN;
@@ -1488,7 +1196,7 @@ struct Bwd {
         pk.n = 2; pk.cols = m.D; pk.unpack = 1;
         pk.src[0] = w.dWqk; pk.rows[0] = (int)m.KD; pk.rows[1] = (int)m.KD;
         pk.dst[0] = gd.sat_wq; pk.dst[1] = gd.sat_wk;
-        DS_TRY(op_pack_rows(pk, sq()));
+        DS_TRY(op_pack_rows(pk, ks.side()));
       }
     }
     // gamma / beta: column sums of the LN backward's partial slabs (or contribution tensors)
@@ -1498,8 +1206,8 @@ struct Bwd {
     float* xpart = preconv_bias_part();
     DS_TRY(colsums({{w.gcon_s, gd.embS_g}, {w.bcon_s, gd.embS_b}, {xpart, xpart ? gd.pre_conv_b : nullptr}},
                    ln_rows, m.D, 1));
-    if (!xpart) DS_TRY(colsum_on(sd, w.dY, m.BN, m.D, 1, gd.pre_conv_b));
-    if (gd.embS_pos) DS_TRY(op_sum_middle(w.dY, 1, m.B, (int64_t)m.N * m.D, gd.embS_pos, 0.f, sq()));
+    if (!xpart) DS_TRY(colsum_on(ks.side(), w.dY, m.BN, m.D, 1, gd.pre_conv_b));
+    if (gd.embS_pos) DS_TRY(op_sum_middle(w.dY, 1, m.B, (int64_t)m.N * m.D, gd.embS_pos, 0.f, ks.side()));
     if (gd.pre_conv_w && !dwp_main()) DS_TRY(sgemm(dwp_gemm()));
     return 0;
   }
@@ -1520,13 +1228,13 @@ struct Bwd {
     return on;
   }
 
-  int stage_preconv() {
+  int stage_preconv(ForkSig* sig) {
     Gemm g;  // dO[b,(f,t),n] = sum_d Wp[d,(f,t)] dY[(b,n),d]
     g.M = (int)m.FT; g.N = (int)m.BN; g.K = m.D;
     g.A = s.Wp; g.am = idx1(1); g.ak = idx1(m.FT);
     g.B = w.dY; g.bk = idx1(1); g.bn = idx1(m.D);
     g.C = w.dO; g.cm = idx1(m.BN); g.cn = idx1(1);  // dO in O's [(f,t)][(b,n)] order
-    return gemm(g);
+    return gemm(g, sig);
   }
 
   // the whole TAt backward as one kernel (tat_fused.hip): LN_N backward, dctx, attention
@@ -1587,7 +1295,7 @@ struct Bwd {
     DS_TRY(fork());
     if (part) DS_TRY(colsums({{w.gcon_e, gd.embT_g}, {w.gcon_e + pb * N, gd.embT_b}}, pb, m.N, 1));
     else DS_TRY(colsums({{w.gcon_e, gd.embT_g}, {w.dE, gd.embT_b}}, (int64_t)m.B * m.T, m.N, 1));
-    if (gd.embT_pos) DS_TRY(op_sum_middle(w.du_et, 1, m.B, (int64_t)m.T * m.N, gd.embT_pos, 0.f, sq()));
+    if (gd.embT_pos) DS_TRY(op_sum_middle(w.du_et, 1, m.B, (int64_t)m.T * m.N, gd.embT_pos, 0.f, ks.side()));
     DS_TRY(wait_side(dx_ready));  // dx += the Chebyshev-path gradient (side stream) first
     return op_transpose(w.du_et, dx, m.T, m.N, m.B, (int64_t)m.T * m.N, (int64_t)m.N * m.T, 1.f, st);
   }
@@ -1621,13 +1329,10 @@ struct Bwd {
     float* dsc = (d.res_mode == DSTAGNN_RES_FULL && dres) ? dres : w.dscore;
     float* dsum = (d.res_mode == DSTAGNN_RES_BCAST && dres) ? dres : nullptr;
     DS_TRY(op_tat_bwd(m.B, m.F, m.T, m.h, m.dk, m.dv, s.qkv, s.att, w.dctx, dre, w.dqkv, dsc, dsum, st));
-    // --- side: TAt LN gamma / beta, fc and Q|K|V weight grads (one fork; its flag rides on the
-    // dE GEMM, issued first)
+    // --- side (A/B knobs only): TAt LN gamma / beta and fc weight grads, one fork before the
+    // dE GEMM
     const bool side_any = tatln_side() || (gd.tat_fc && fc_side());
-    if (side_any) DS_TRY(fork_k());
     auto side_work = [&]() -> int {
-      if (!side_any) return 0;
-      DS_TRY(fork_k_done());
       if (tatln_side()) DS_TRY(tat_ln_colsums(false));
       if (gd.tat_fc && fc_side()) DS_TRY(sgemm(fc_grad_gemm()));
       return 0;
@@ -1645,8 +1350,10 @@ struct Bwd {
       } else if (dE_omap() && m.FT % 32 == 0) {
         // inner block: E is x transposed, so dE accumulates straight into dx (B,N,F,T) through
         // the output map (row (b, ft), column n -> b N FT + n FT + ft) once the side stream's
-        // Chebyshev-path gradient is in dx
-        DS_TRY(wait_side(dx_ready));  // (flushes the fork_k's signal first)
+        // Chebyshev-path gradient is in dx.  The main stream waits for the side before the
+        // GEMM, which no fork_on scope may do: a plain fork, its flag written ahead of the wait
+        if (side_any) DS_TRY(fork());
+        DS_TRY(wait_side(dx_ready));
         g.Cout = dx; g.omap = true; g.obeta = 1.f;
         g.om = idx2(m.FT, 1, N * m.FT); g.on = idx1(m.FT);
         DS_TRY(gemm(g));
@@ -1654,7 +1361,8 @@ struct Bwd {
       } else {
         g.Cout = w.dE;
       }
-      DS_TRY(gemm(g));
+      if (side_any) DS_TRY(ks.fork_on([&](ForkSig* sig) { return gemm(g, sig); }));  // the flag rides on the GEMM
+      else DS_TRY(gemm(g));
     }
     DS_TRY(side_work());
     // dE -> dx
@@ -1753,25 +1461,23 @@ struct Bwd {
   int run() {
     static const bool prof = env_str("DSTAGNN_HOST_PROFILE") != nullptr;
     HostTimer ht(prof, "bwd");
-    SigFlushGuard sig_guard;
     ks.init(st);
-    sd = ks.sd;
     ht.lap("init");
     DS_TRY(debug_delay(st, true));
     DS_TRY(stage_tail());
-    DS_TRY(order_err);
+    DS_TRY(ks.order_err);
     ht.lap("tail");
     DS_TRY(debug_delay(st, true));
     DS_TRY(stage_cheb());
-    DS_TRY(order_err);
+    DS_TRY(ks.order_err);
     ht.lap("cheb");
     DS_TRY(debug_delay(st, true));
     DS_TRY(stage_sat());  // + stage_preconv
-    DS_TRY(order_err);
+    DS_TRY(ks.order_err);
     ht.lap("sat");
     DS_TRY(debug_delay(st, true));
     DS_TRY(stage_tat());
-    DS_TRY(order_err);
+    DS_TRY(ks.order_err);
     ht.lap("tat");
     DS_TRY(tat_wqkv_grad());  // (+ the fc weight gradient)
     if (gd.pre_conv_w && dwp_main()) DS_TRY(gemm(dwp_gemm()));
@@ -1783,7 +1489,7 @@ struct Bwd {
 #else
     if (!tatln_side() && !m.tfused_bwd) DS_TRY(tat_ln_colsums(true));  // (fused: summed in-kernel)
 #endif
-    DS_TRY(order_err);
+    DS_TRY(ks.order_err);
     DS_TRY(join());
     ht.lap("join");
     return 0;

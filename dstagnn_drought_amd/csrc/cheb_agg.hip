@@ -943,12 +943,10 @@ int op_cheb_agg_fwd(const ChebAg& a0, hipStream_t st) {
   return 0;
 }
 
-int op_cheb_agg_sddmm(const ChebAg& a0, hipStream_t st) {
+int op_cheb_agg_sddmm(const ChebAg& a0, hipStream_t st, ForkSig* sig) {
   DS_TRY(check(a0));
   ChebAg a = with_order(a0);
-  const StreamSig sg = peek_stream_sig(st);  // carries a pending stream signal (common.hpp)
-  a.sig = sg.p;
-  a.sig_v = sg.v;
+  if (sig) { a.sig = sig->p; a.sig_v = sig->v; }  // carries the caller's fork signal (common.hpp)
   const int FT = a.F * a.T;
   // T <= 16: sample pairs per wave (cheb_agg_sddmm2_kernel; DSTAGNN_SDDMM_PAIR=0: one sample)
   // (DSTAGNN_SDDMM_NOPF=1 names a variant of the one-sample kernel: it implies PAIR=0)
@@ -963,7 +961,7 @@ int op_cheb_agg_sddmm(const ChebAg& a0, hipStream_t st) {
     dispatch<SddmmL>(nq_of(std::min(FT, 1024)), km_of(a.K), Launch{a, dim3(grid_rows((int64_t)a.B * a.N)), lds, st});
   }
   DS_CHECK_LAUNCH();
-  if (sg.p) DS_TRY(stream_sig_sent(st, sg));
+  if (sig) sig->carried = true;
   return 0;
 }
 

@@ -989,11 +989,9 @@ int op_flash_colc(const ChebFl& a, hipStream_t st) {
   return 0;
 }
 
-int op_flash_dqk(const ChebFl& a0, hipStream_t st) {
-  ChebFl a = a0;  // the first launch carries a pending stream signal (common.hpp)
-  const StreamSig sg = peek_stream_sig(st);
-  a.sig = sg.p;
-  a.sig_v = sg.v;
+int op_flash_dqk(const ChebFl& a0, hipStream_t st, ForkSig* sig) {
+  ChebFl a = a0;  // the first launch carries the caller's fork signal (common.hpp)
+  if (sig) { a.sig = sig->p; a.sig_v = sig->v; }
   const int nt = (a.N + 31) >> 5;
   // N <= 192: two strips per workgroup (flash_small_dqk2_kernel; DSTAGNN_FLASH_DQK2=0: one)
   static const bool dqk2 = env_flag("DSTAGNN_FLASH_DQK2", true);
@@ -1009,7 +1007,7 @@ int op_flash_dqk(const ChebFl& a0, hipStream_t st) {
 #undef DS_DQK2
     }
     DS_CHECK_LAUNCH();
-    if (sg.p) DS_TRY(stream_sig_sent(st, sg));
+    if (sig) sig->carried = true;
     return 0;
   }
   if (a.am) {  // small graphs (flash_small): dK' and dQ' strips in one launch
@@ -1029,12 +1027,12 @@ int op_flash_dqk(const ChebFl& a0, hipStream_t st) {
       default: set_last_error("flash: graph too large for the small-graph kernels"); return DSTAGNN_E_SHAPE;
     }
     DS_CHECK_LAUNCH();
-    if (sg.p) DS_TRY(stream_sig_sent(st, sg));
+    if (sig) sig->carried = true;
     return 0;
   }
   hipLaunchKernelGGL(flash_dq_kernel, dim3(grid_waves((int64_t)a.B * a.K * nt)), dim3(256), 0, st, a);
   DS_CHECK_LAUNCH();
-  if (sg.p) DS_TRY(stream_sig_sent(st, sg));
+  if (sig) sig->carried = true;
   hipLaunchKernelGGL(flash_dk_kernel, dim3(grid_waves((int64_t)a.B * a.K * nt)), dim3(256), 0, st, a0);
   DS_CHECK_LAUNCH();
   return 0;

@@ -276,27 +276,20 @@ void set_last_error(const std::string& s);
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ---------------------------------------------------------------------------------
-// kernel-written stream signals (block.hip Streams::fork_k): a fork from the block's main
-// stream to its side stream leaves the flag write PENDING for the next kernel launched on the
-// main stream that can carry it (the GEMMs, the GTU input-gradient kernel, the aggregate-first
-// SDDMM, the flash dQ / dK kernels): that kernel's workgroup 0 stores the flag as it starts —
-// every earlier kernel of the stream has completed by then — instead of a
-// hipStreamWriteValue32 (a ~4.5 us ROCclr kernel plus its dispatch gap on the critical path).
-// A launcher reads the pending signal (peek_stream_sig), passes it to its kernel and, once the
-// launch succeeded, calls stream_sig_sent, which queues the side stream's wait for the flag —
-// so the writer is always queued BEFORE the wait (no dependence on how streams map to hardware
-// queues, nor on whether a wait can block the host).  A signal nobody consumed is written by
-// flush_stream_sig() (write on main, then the side's wait), which runs before the main stream
-// waits for the side stream and when the block's op returns (also on its error paths).  The
-// block issues no side-stream work between a fork_k and the launch that carries its signal.
+// kernel-written fork signals (streams.hpp Streams::fork_on): the flag of a main -> side
+// dependency, stored by workgroup 0 of a main-stream kernel as it starts (stream_sig_store) —
+// every earlier kernel of the stream has completed by then — instead of a hipStreamWriteValue32
+// (a ~4.5 us ROCclr kernel plus its dispatch gap on the critical path).  The caller of fork_on
+// names the launch and hands it the ForkSig.  Carriers: the GEMMs (run_gemm*: the call's first
+// non-skinny launch), op_gtu_tconv, op_cheb_agg_sddmm, op_flash_dqk, op_tat_fused_fwd.  A
+// carrier copies p / v into its kernel arguments and sets `carried` only after that launch
+// succeeded; fork_on writes a signal nobody carried itself, then queues the side stream's wait.
 // ---------------------------------------------------------------------------------
-struct StreamSig {
+struct ForkSig {
   uint32_t* p = nullptr;
   uint32_t v = 0;
+  bool carried = false;
 };
-StreamSig peek_stream_sig(hipStream_t st);  // the pending signal for st, or {}
-int stream_sig_sent(hipStream_t st, const StreamSig& s);  // a launch on st carried s: queue the wait
-int flush_stream_sig();  // a pending signal nobody consumed: hipStreamWriteValue32, then the wait
 
 // workgroup 0, thread 0: a vector store (system scope, release) of the signal, if any
 __device__ __forceinline__ void stream_sig_store(uint32_t* p, uint32_t v) {
@@ -330,14 +323,14 @@ struct Gemm {
   int splitk_target = 0;  // split-K workgroup target for this call (0: the global target)
   Gemm() { am = ak = az = bk = bn = bz = cm = cn = cz = om = on = oz = idx1(0); }
 };
-// ws: split-K partial slab scratch (may be null -> no split)
-int run_gemm(const Gemm& g, float* ws, size_t ws_floats, hipStream_t st);
+// ws: split-K partial slab scratch (may be null -> no split); sig: a fork signal to carry
+int run_gemm(const Gemm& g, float* ws, size_t ws_floats, hipStream_t st, ForkSig* sig = nullptr);
 // 1..3 independent problems (disjoint outputs) as one grouped launch where their kernel
 // configurations agree; each takes its own slice of the split-K slab space ws
-int run_gemm_group(const Gemm* gs, int n, float* ws, size_t ws_floats, hipStream_t st);
+int run_gemm_group(const Gemm* gs, int n, float* ws, size_t ws_floats, hipStream_t st, ForkSig* sig = nullptr);
 // 1..3 products summed over their concatenated K ranges into problem 0's output and
 // epilogue (same M, N, batch): C = epilogue_0(sum_p A_p B_p), one launch, no split-K
-int run_gemm_kcat(const Gemm* gs, int n, hipStream_t st);
+int run_gemm_kcat(const Gemm* gs, int n, hipStream_t st, ForkSig* sig = nullptr);
 // GEMM-family profiling (gemm.hip): while on, the block runs on ONE stream (no side-stream
 // overlap) so every recorded GEMM duration is its own
 bool gemm_prof_on();

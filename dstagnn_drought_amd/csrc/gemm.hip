@@ -689,15 +689,15 @@ uint32_t make_group(const GemmK* const* ks, const uint32_t* counts, int n, GemmG
   return at;
 }
 
-int launch_plans(Plan* const* ps, int n, hipStream_t st) {
+// sig: a fork signal not carried yet rides on this launch (common.hpp)
+int launch_plans(Plan* const* ps, int n, hipStream_t st, ForkSig* sig) {
   const GemmK* ks[kGroupMax];
   uint32_t counts[kGroupMax];
   for (int p = 0; p < n; ++p) { ks[p] = &ps[p]->k; counts[p] = ps[p]->k.count; }
   GemmG gg;
   const uint32_t grid = make_group(ks, counts, n, &gg);
-  const StreamSig sg = peek_stream_sig(st);
-  gg.sig = sg.p;
-  gg.sig_v = sg.v;
+  if (sig && sig->carried) sig = nullptr;
+  if (sig) { gg.sig = sig->p; gg.sig_v = sig->v; }
   using Unit = void (*)(const GemmG&, dim3, bool, bool, int, int, bool, hipStream_t);
   static const Unit units[3][3][2] = {
       {{gemm_c0_k0, gemm_c0_k1}, {gemm_c1_k0, gemm_c1_k1}, {gemm_c2_k0, gemm_c2_k1}},
@@ -707,7 +707,7 @@ int launch_plans(Plan* const* ps, int n, hipStream_t st) {
   const int var = pl.acc2 ? 2 : (g_bf16 ? 1 : 0);
   units[var][pl.best][pl.ktwo ? 1 : 0](gg, dim3(grid), pl.akc, pl.bnc, pl.va, pl.vb, pl.hot, st);
   DS_CHECK_LAUNCH();
-  if (sg.p) DS_TRY(stream_sig_sent(st, sg));
+  if (sig) sig->carried = true;
   return 0;
 }
 
@@ -717,7 +717,7 @@ int launch_plans(Plan* const* ps, int n, hipStream_t st) {
 // split-K slab space), launched as ONE grouped kernel when their kernel configurations agree
 // (else one launch per run of equal configurations), their split-K folds as one grouped
 // reduce.  The problems must not write overlapping outputs.
-int run_gemm_group(const Gemm* gs, int n, float* ws, size_t ws_floats, hipStream_t st) {
+int run_gemm_group(const Gemm* gs, int n, float* ws, size_t ws_floats, hipStream_t st, ForkSig* sig) {
   if (n < 1 || n > 3) { set_last_error("gemm: 1..3 problems per group"); return DSTAGNN_E_ARG; }
   ProfRec* prec = nullptr;
   Plan plans[3];
@@ -751,7 +751,7 @@ int run_gemm_group(const Gemm* gs, int n, float* ws, size_t ws_floats, hipStream
     int j = i + 1;
     while (j < nl && j - i < kGroupMax && live[j]->same_kernel(*live[i])) ++j;
     if (live[i]->skinny) launch_skinny(live[i]->sk, st);
-    else DS_TRY(launch_plans(live + i, j - i, st));
+    else DS_TRY(launch_plans(live + i, j - i, st, sig));
     DS_CHECK_LAUNCH();
     if (gemm_log_on()) {
       fprintf(stderr, "[gemm] %s", live[i]->log);
@@ -786,7 +786,7 @@ int run_gemm_group(const Gemm* gs, int n, float* ws, size_t ws_floats, hipStream
 // (same M, N, batch and kernel configuration; each A_p / B_p with its own pointer and maps;
 // the epilogue, C and its maps are problem 0's).  One launch, no split-K, no intermediate C
 // round trips: the GTU transposed convolutions of widths 3, 5, 7 accumulating into one dX.
-int run_gemm_kcat(const Gemm* gs, int n, hipStream_t st) {
+int run_gemm_kcat(const Gemm* gs, int n, hipStream_t st, ForkSig* sig) {
   if (n < 1 || n > 3) { set_last_error("gemm: 1..3 K segments"); return DSTAGNN_E_ARG; }
   const Gemm& g0 = gs[0];
   if (g0.M <= 0 || g0.N <= 0 || g0.batch <= 0) return 0;
@@ -806,14 +806,14 @@ int run_gemm_kcat(const Gemm* gs, int n, hipStream_t st) {
       // different kernels (DMA widths / map kinds): fall back to a chain of launches
       Gemm first = g0, next;
       first.Cout = nullptr; first.emask = nullptr;
-      DS_TRY(run_gemm(first, nullptr, 0, st));
+      DS_TRY(run_gemm(first, nullptr, 0, st, sig));
       for (int q = 1; q < n; ++q) {
         next = gs[q];
         next.C = g0.C; next.cm = g0.cm; next.cn = g0.cn; next.cz = g0.cz; next.c_off = g0.c_off;
         next.beta = 1.f; next.bias = nullptr; next.relu = 0;
         next.Cout = q == n - 1 ? g0.Cout : nullptr;
         next.emask = q == n - 1 ? g0.emask : nullptr;
-        DS_TRY(run_gemm(next, nullptr, 0, st));
+        DS_TRY(run_gemm(next, nullptr, 0, st, sig));
       }
       return 0;
     }
@@ -838,9 +838,7 @@ int run_gemm_kcat(const Gemm* gs, int n, hipStream_t st) {
   gg.start[0] = (uint32_t)n;  // K-concatenated
   for (int p = 1; p < 4; ++p) gg.start[p] = grid;
   for (int p = 0; p < n; ++p) gg.k[p] = plans[p].k;
-  const StreamSig sg = peek_stream_sig(st);
-  gg.sig = sg.p;
-  gg.sig_v = sg.v;
+  if (sig) { gg.sig = sig->p; gg.sig_v = sig->v; }
   using Unit = void (*)(const GemmG&, dim3, bool, bool, int, int, bool, hipStream_t);
   static const Unit units[2][3][2] = {
       {{gemm_c0_k0, gemm_c0_k1}, {gemm_c1_k0, gemm_c1_k1}, {gemm_c2_k0, gemm_c2_k1}},
@@ -848,7 +846,7 @@ int run_gemm_kcat(const Gemm* gs, int n, hipStream_t st) {
   const Plan& pl = plans[0];
   units[g_bf16 ? 1 : 0][pl.best][pl.ktwo ? 1 : 0](gg, dim3(grid), pl.akc, pl.bnc, pl.va, pl.vb, false, st);
   DS_CHECK_LAUNCH();
-  if (sg.p) DS_TRY(stream_sig_sent(st, sg));
+  if (sig) sig->carried = true;
   if (gemm_log_on()) {
     fprintf(stderr, "[gemm] kcat %s", plans[0].log);
     for (int q = 1; q < n; ++q) fprintf(stderr, " + %s", plans[q].log);
@@ -858,5 +856,7 @@ int run_gemm_kcat(const Gemm* gs, int n, hipStream_t st) {
   return 0;
 }
 
-int run_gemm(const Gemm& g, float* ws, size_t ws_floats, hipStream_t st) { return run_gemm_group(&g, 1, ws, ws_floats, st); }
+int run_gemm(const Gemm& g, float* ws, size_t ws_floats, hipStream_t st, ForkSig* sig) {
+  return run_gemm_group(&g, 1, ws, ws_floats, st, sig);
+}
 

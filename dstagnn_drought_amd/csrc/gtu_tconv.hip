@@ -260,7 +260,7 @@ bool gtu_tconv_ok(int C, const int* ks, int n) {
   return true;
 }
 
-int op_gtu_tconv(const TconvArgs& a, hipStream_t st) {
+int op_gtu_tconv(const TconvArgs& a, hipStream_t st, ForkSig* sig) {
   if (a.M <= 0) return 0;
   if (!gtu_tconv_ok(kTcC, a.ks, 3)) {
     set_last_error("gtu_tconv: C = 32 and GTU widths 1..7 only");
@@ -277,14 +277,12 @@ int op_gtu_tconv(const TconvArgs& a, hipStream_t st) {
     flops += 2.0 * a.M * kTcC * (double)(kTcCin * a.ks[q]);
     bytes += 4.0 * ((double)(a.M + a.ks[q] - 1) * kTcCin + (double)kTcCin * a.ks[q] * kTcC);
   }
-  TconvArgs b = a;  // carries a pending stream signal (common.hpp)
-  const StreamSig sg = peek_stream_sig(st);
-  b.sig = sg.p;
-  b.sig_v = sg.v;
+  TconvArgs b = a;  // carries the caller's fork signal (common.hpp)
+  if (sig) { b.sig = sig->p; b.sig_v = sig->v; }
   void* rec = gemm_prof_begin(flops, bytes, st, DSTAGNN_PROF_GTU_TCONV);
   hipLaunchKernelGGL(gtu_tconv_kernel, dim3((unsigned)cdiv64(a.M, kTcBM)), dim3(256), 0, st, b);
   DS_CHECK_LAUNCH();
-  if (sg.p) DS_TRY(stream_sig_sent(st, sg));
+  if (sig) sig->carried = true;
   gemm_prof_end(rec, st);
   return 0;
 }

@@ -200,7 +200,7 @@ struct ChebAg {
 };
 bool cheb_agg_ok(int F, int C, int K, int T);
 int op_cheb_agg_fwd(const ChebAg& a, hipStream_t st);
-int op_cheb_agg_sddmm(const ChebAg& a, hipStream_t st);
+int op_cheb_agg_sddmm(const ChebAg& a, hipStream_t st, ForkSig* sig = nullptr);
 int op_cheb_agg_spmm_t(const ChebAg& a, hipStream_t st);
 
 // fused (flash-style) Chebyshev attention (cheb_flash.hip); dk == 32
@@ -232,7 +232,7 @@ struct ChebFl {
 bool flash_small(int N);  // the LDS-staged small-graph kernels (N <= 512)
 int op_flash_forward(const ChebFl& a, hipStream_t st);   // lse, psupp, wsupp
 int op_flash_colc(const ChebFl& a, hipStream_t st);      // cc, dzs
-int op_flash_dqk(const ChebFl& a, hipStream_t st);       // dqk
+int op_flash_dqk(const ChebFl& a, hipStream_t st, ForkSig* sig = nullptr);       // dqk
 int op_flash_mask_grad(const ChebFl& a, hipStream_t st); // dmask
 int op_cheb_spmm_fwd(const ChebSp& a, hipStream_t st);
 int op_cheb_sddmm_bwd(const ChebSp& a, hipStream_t st);
@@ -267,7 +267,7 @@ struct GconvArgs {
 };
 bool gtu_conv_fwd_ok(int C, int T, const int* ks, int n);
 int op_gtu_conv_fwd(GconvArgs a, hipStream_t st);
-int op_gtu_tconv(const TconvArgs& a, hipStream_t st);
+int op_gtu_tconv(const TconvArgs& a, hipStream_t st, ForkSig* sig = nullptr);
 // the temporal-attention stage as one kernel (tat_fused.hip): Q|K|V projection, attention, fc,
 // residual and the LayerNorm over N; E(R, n) = src[(R % FT) s0 + (R / FT) s1 + n sN]
 struct TatFusedArgs {
@@ -287,7 +287,7 @@ bool tat_fused_fwd_ok(int N, int T, int h, int dk, int dv);
 int tat_fused_np(int N);  // the padded node count of the re-laid Q|K|V weights
 int64_t tat_fused_bwd_wgs(int64_t BFT);        // the fused backward's workgroups (partial rows)
 int64_t tat_fused_bwd_part_rows(int64_t BFT);  // ... + its level-2 ticket-tree rows: one slab's rows
-int op_tat_fused_fwd(const TatFusedArgs& a, hipStream_t st);
+int op_tat_fused_fwd(const TatFusedArgs& a, hipStream_t st, ForkSig* sig = nullptr);
 struct TatFusedBwdArgs {
   const float* dO = nullptr;  // O's [(f,t)][(b,n)] order
   const float *u = nullptr, *mu = nullptr, *rs = nullptr, *g = nullptr;

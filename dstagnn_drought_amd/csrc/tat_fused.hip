@@ -1038,15 +1038,13 @@ int64_t tat_fused_bwd_part_rows(int64_t BFT) {
   return nwg + cdiv64(nwg, kTfG1);
 }
 
-int op_tat_fused_fwd(const TatFusedArgs& a0, hipStream_t st) {
+int op_tat_fused_fwd(const TatFusedArgs& a0, hipStream_t st, ForkSig* sig) {
   if (!tat_fused_fwd_ok(a0.N, a0.T, a0.h, kTfD, kTfD) || a0.NP != tat_fused_np(a0.N) || a0.BFT % a0.T != 0) {
     set_last_error("tat_fused_fwd: unsupported shape");
     return DSTAGNN_E_SHAPE;
   }
-  TatFusedArgs a = a0;
-  const StreamSig sg = peek_stream_sig(st);
-  a.sig = sg.p;
-  a.sig_v = sg.v;
+  TatFusedArgs a = a0;  // carries the caller's fork signal (common.hpp)
+  if (sig) { a.sig = sig->p; a.sig_v = sig->v; }
   const int64_t grid = cdiv64(a.BFT, kTfRows);
   const size_t lds = tat_fused_lds(a.NP);
   const int ntw = (a.NP / 16 + 3) / 4;  // fc column tiles per wave
@@ -1089,7 +1087,7 @@ int op_tat_fused_fwd(const TatFusedArgs& a0, hipStream_t st) {
   void* rec = gemm_prof_begin(flops, bytes, st, DSTAGNN_PROF_TAT_FUSED_FWD);
   hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(64 * waves), lds, st, a);
   DS_CHECK_LAUNCH();
-  if (sg.p) DS_TRY(stream_sig_sent(st, sg));
+  if (sig) sig->carried = true;
   gemm_prof_end(rec, st);
   return 0;
 }
@@ -1123,9 +1121,6 @@ int op_tat_fused_bwd(const TatFusedBwdArgs& a0, hipStream_t st) {
       return DSTAGNN_E_ARG;
     }
   }
-  const StreamSig sg = peek_stream_sig(st);
-  a.sig = sg.p;
-  a.sig_v = sg.v;
   const int64_t grid = cdiv64(a.BFT, kTfRows);
   // DSTAGNN_TF_BWD_WAVES=4|8: the backward's workgroup size (A/B)
   static const int waves = env_int("DSTAGNN_TF_BWD_WAVES", 8) == 4 ? 4 : 8;
@@ -1169,7 +1164,6 @@ int op_tat_fused_bwd(const TatFusedBwdArgs& a0, hipStream_t st) {
   void* rec = gemm_prof_begin(flops, bytes, st, DSTAGNN_PROF_TAT_FUSED_BWD);
   hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(64 * wv), lds, st, a);
   DS_CHECK_LAUNCH();
-  if (sg.p) DS_TRY(stream_sig_sent(st, sg));
   gemm_prof_end(rec, st);
   return 0;
 }

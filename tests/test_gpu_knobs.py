@@ -21,8 +21,8 @@ a subprocess (the library reads its switches once per process):
   DSTAGNN_GTU_GCONV=1  the GTU forward convolutions by the sliding-window kernel (gtu_tconv.hip)
   DSTAGNN_TAIL_CT24=0  the split GTU tail path at T = 24 instead of the compile-time kernels
   DSTAGNN_KSIG=0       main -> side stream forks signalled by hipStreamWriteValue32 instead of
-                       by the next main-stream kernel's prologue store (block.hip Streams::fork;
-                       the default path is held by every other GPU test)
+                       by the prologue store of the main-stream kernel the call site names
+                       (streams.hpp Streams::fork_on; the default path is held by every other GPU test)
   DSTAGNN_FC_SIDE=1    the TAt fc weight gradient on the side stream instead of grouped with the
                        Q|K|V weight gradient on the main stream
   DSTAGNN_TATLN_SIDE=1 the TAt LayerNorm gamma / beta column sums on the side stream
@@ -46,14 +46,15 @@ a subprocess (the library reads its switches once per process):
                        (LayerNorm backward, GEMMs, attention backward, dE transpose)
   DSTAGNN_CHEB_AGG=0   the Theta-first sparse Chebyshev (x Theta GEMM, then SpMM) at a geometry that
                        takes the aggregate-first kernels by default
-  DSTAGNN_DEBUG_STREAMS=1  the fork invariant asserted (block.hip Bwd::sq): no side-stream work
-                       issued while a fork's signal is still pending
+  DSTAGNN_DEBUG_STREAMS=1  the fork invariant asserted (streams.hip Streams::side): no side-stream
+                       work issued while a fork's signal is still pending
   DSTAGNN_DEBUG_MAIN_DELAY_US / DSTAGNN_DEBUG_SIDE_DELAY_US   race probes: a 1.5 ms busy-wait
                        kernel on the main stream before every stage / on the side stream after
                        every fork, so a cross-stream read without its dependency reads stale
-                       data (block.hip debug_delay); results must not change
+                       data (streams.hip debug_delay); results must not change
 
-PEMS08 geometry (the bench's default path otherwise; t24 for the T = 24 switches), inner block
+PEMS08 geometry (the bench's default path otherwise; t24 for the T = 24 switches and, with h = 2,
+for the unfused TAt backward's fork with side work and its DE_OMAP branch), inner block
 with a broadcast res_att in eval and train mode plus the first block, same bounds as
 tests/test_gpu_parity.py::test_block_vs_oracle_configs."""
 import os
@@ -101,7 +102,11 @@ print("KNOB_OK")
                                        ("DSTAGNN_DEBUG_STREAMS=1", "pems07+flash", 2),
                                        ("DSTAGNN_SIDE_STREAM=0", "pems08", 4),
                                        ("DSTAGNN_TAT_FUSED_BWD=0", "pems08", 4),
-                                       ("DSTAGNN_CHEB_AGG=0", "pems08", 4)])
+                                       ("DSTAGNN_CHEB_AGG=0", "pems08", 4),
+                                       ("DSTAGNN_FC_SIDE=1", "t24", 2), ("DSTAGNN_TATLN_SIDE=1", "t24", 2),
+                                       ("DSTAGNN_DE_OMAP=1", "t24", 2), ("DSTAGNN_DEBUG_STREAMS=1", "t24", 2),
+                                       ("DSTAGNN_DEBUG_MAIN_DELAY_US=1500", "t24", 2),
+                                       ("DSTAGNN_DEBUG_SIDE_DELAY_US=1500", "t24", 2)])
 def test_knob_path_vs_oracle(env, cfg, B):
     import torch
     if not torch.cuda.is_available():

@@ -7,7 +7,7 @@
 // argv[1] = s: the flag words in hipMallocSignalMemory (else hipMalloc).
 // Modes 4 / 5: the flag is written by the NEXT kernel on the producer stream (workgroup 0,
 // thread 0, at its start: a system-scope release store) instead of a hipStreamWriteValue32 —
-// the block's kernel-prologue signal (block.hip Streams::fork) — the producer's data being
+// the block's kernel-prologue signal (streams.hpp Streams::fork_on) — the producer's data being
 // complete once any later kernel of its stream runs.
 //   hipcc -O3 --offload-arch=gfx950 tools/flag_sync_probe.hip -o tools/flag_sync_probe
 #include <hip/hip_runtime.h>
