@@ -544,7 +544,9 @@ bool plan_skinny(Plan& pl, float* ws, size_t ws_floats, hipStream_t st) {
   pl.skinny = true;
   if (gemm_log_on()) {
     const size_t n = strlen(pl.log);
-    snprintf(pl.log + n, sizeof(pl.log) - n, " skinny kpw=%d nwg=%d ngrp=%d", s.kpw, s.nwg, s.ngrp);
+    // (mt / nt / a4 as launch_skinny derives them: the template the launch takes)
+    snprintf(pl.log + n, sizeof(pl.log) - n, " skinny kpw=%d nwg=%d ngrp=%d mt=%d nt=%d a4=%d", s.kpw, s.nwg, s.ngrp,
+             k.M > 64 ? 6 : (k.M + 15) / 16, k.N > 16 ? 2 : 1, (int)skinny_a4(s));
   }
   return true;
 }
