@@ -20,6 +20,7 @@ LIB_PATH = os.path.join(_HERE, "libdstagnn.so")
 RES_NONE, RES_BCAST, RES_FULL = 0, 1, 2
 # dstagnn::block flags
 F_TRAIN, F_SPARSE, F_DIRECT, F_POISON, F_FLASH = 1, 2, 4, 8, 16
+F_FULL_FWD = 32  # keep the full (backward-state-writing) forward where no autograd node is recorded
 
 _ops = None
 

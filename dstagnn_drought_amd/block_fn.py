@@ -1,7 +1,9 @@
 """Host side of the HIP DSTAGNN_block: the call into ``torch.ops.dstagnn.block``.
 
 ``dstagnn::block`` (csrc/torch_ops.cpp) is ONE C++ autograd node per block: its forward is
-one ``dstagnn_block_forward`` call and its backward one ``dstagnn_block_backward`` call, so
+one ``dstagnn_block_forward`` call and its backward one ``dstagnn_block_backward`` call (where
+no node would be recorded — ``torch.no_grad()``, ``torch.inference_mode()``, nothing requiring
+grad — the forward is one ``dstagnn_block_forward_only`` call that writes no backward state), so
 every stage of model/DSTAGNN_my.py:225-253 and its gradient runs in our own gfx950 kernels
 on torch's current HIP stream.  PyTorch only provides the device memory (caching
 allocator), the stream and the autograd engine.  This module maps the reference's
@@ -103,24 +105,26 @@ def cfg_of(meta):
 SAMPLE_SHIFT = 32  # flags bits 32..: the call's first global sample index (torch_ops.cpp kSampleShift)
 
 
-def flags_of(train, sparse, direct, flash=False, sample_base=0):
+def flags_of(train, sparse, direct, flash=False, sample_base=0, forward_only=True):
     if sample_base < 0:
         raise ValueError("sample_base must be >= 0")
     return ((_lib.F_TRAIN if train else 0) | (_lib.F_SPARSE if sparse else 0) | (_lib.F_DIRECT if direct else 0)
-            | (_lib.F_POISON if _POISON else 0) | (_lib.F_FLASH if flash else 0) | (int(sample_base) << SAMPLE_SHIFT))
+            | (_lib.F_POISON if _POISON else 0) | (_lib.F_FLASH if flash else 0)
+            | (0 if forward_only else _lib.F_FULL_FWD) | (int(sample_base) << SAMPLE_SHIFT))
 
 
 def block_call(x, res_att, params, slots, graph, meta, train, seed, direct=False, flash=None, plan_cache=None,
-               sample_base=0):
+               sample_base=0, forward_only=True):
     """(out, re_at) = dstagnn::block(...) — autograd-tracked.  In direct-gradient mode with a
     plan_cache dict (the module's), the block's constant arguments go to the library once, as a
     cached BlockPlan (dstagnn::block_planned): same kernels, less host work per call.
-    sample_base: global index of x[0] (a data-parallel shard's offset; keys the dropout masks)."""
+    sample_base: global index of x[0] (a data-parallel shard's offset; keys the dropout masks).
+    forward_only=False: a call that records no autograd node still runs the full forward (A/B tools)."""
     ops = _lib.load()
     x = x.float().contiguous()
     sparse = use_sparse(graph, meta, x.shape[3])
     fl = use_flash(graph, meta, x.shape[3], flash, x.shape[0])
-    flags = flags_of(train, sparse, direct, fl, sample_base)
+    flags = flags_of(train, sparse, direct, fl, sample_base, forward_only)
     if direct and plan_cache is not None:
         key = (id(params), id(graph), sparse, fl)
         ent = plan_cache.get("plan")
@@ -159,6 +163,25 @@ def dropout_masks(meta, x_shape, seed, sample_base=0):
 # dstagnn_block_paths bits (include/dstagnn.h DSTAGNN_PATH_*)
 PATH_BITS = {"sparse": 1, "flash": 2, "flash_small": 4, "cheb_agg": 8, "tat_fused_fwd": 16, "tat_fused_bwd": 32,
              "gtu_fused_fwd": 64, "gtu_fused_bwd": 128, "sat_ln_fused": 256}
+
+
+def _explicit_args(blk, x, res_att, train=False, seed=0, poison=False):
+    """The explicit-op argument list (DSTAGNN_BLK_ARGS) of this block module on this input."""
+    names, ps, slots = blk._param_list()
+    graph = blk._graph()
+    sparse = use_sparse(graph, blk.meta, x.shape[3])
+    fl = use_flash(graph, blk.meta, x.shape[3], blk.flash_cheb, x.shape[0])
+    if fl:
+        graph = blk._flash_graph(graph)
+    flags = flags_of(train, sparse, False, fl) | (_lib.F_POISON if poison else 0)
+    return (x.detach().float().contiguous(), res_arg(res_att, x.shape[2]), list(ps), slots,
+            graph_list(graph, sparse, fl), cfg_of(blk.meta), float(blk.meta.get("drop_p", 0.05)), int(seed), flags)
+
+
+def forward_only_bytes(blk, x, res_att):
+    """Bytes of the ONE workspace the forward-only call of this block module allocates on this
+    input (dstagnn::block_fwd_only_bytes over dstagnn_block_forward_only_size; launches nothing)."""
+    return int(_lib.load().block_fwd_only_bytes(*_explicit_args(blk, x, res_att)))
 
 
 def block_paths(blk, x, res_att, train=False):

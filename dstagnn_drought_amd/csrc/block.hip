@@ -210,6 +210,67 @@ Scratch plan_scratch(const Dims& m, Arena& a) {
   return s;
 }
 
+// The forward-only workspace (dstagnn_block_forward_only): the tensors of plan_save that a LATER
+// FORWARD kernel reads, and the two GEMM workspaces (one per stream) — nothing the backward alone
+// reads.  Every other member stays null: the stage functions pass the nulls on and the launchers
+// pick the kernels' SAVE = false forms, which hold neither the store nor the pointer.
+//   parameters   Wqkv (unfused TAt) | Wqkv_p (fused TAt), Wgt (fused GTU) | Wgf (unfused), Wqk, Wp,
+//                thcat, am (small-graph flash)
+//   region A     E (first block, or unfused TAt), qkv / att / ctx / u_tat (unfused TAt), O, u_s, Zd,
+//                qk, P (no flash), W (dense T_k), lse (streamed flash), wsupp (flash), xth (Theta-first)
+//   after A      X, conv[0..2] (unfused GTU)
+// Region A is dead once X is written.  One reuse: in an inner block with the unfused TAt stage, X
+// takes E's place (both (B N, C T) floats): E's last reader is the TAt LayerNorm on the caller's
+// stream, X's writer the Chebyshev aggregation, later on the same stream.
+// The split GTU tail (long series: gates | fcmy GEMM | tail) has two intermediates of its own: G
+// goes through the main GEMM workspace a chunk of nodes at a time (Fwd::stage_tail; that
+// workspace is idle from the convolutions on), the fcmy output through the out buffer itself.
+struct WorkBufs {
+  SaveBufs s;
+  Scratch w;
+};
+
+WorkBufs plan_work(const Dims& m, Arena& a) {
+  WorkBufs k{};
+  SaveBufs& s = k.s;
+  s.Wqkv = m.tfused ? nullptr : a.take(m.QW * m.N);
+  s.Wqkv_p = m.tfused ? a.take(m.QW * m.NP) : nullptr;
+  for (int g = 0; g < 3; ++g) s.Wgt[g] = m.gfused ? a.take(2 * (int64_t)m.C * m.C * m.ks[g]) : nullptr;
+  s.Wqk = a.take(2 * m.KD * m.D);
+  s.Wp = a.take((int64_t)m.D * m.FT);
+  s.thcat = a.take((int64_t)m.F * m.KC);
+  for (int g = 0; g < 3; ++g) s.Wgf[g] = m.gfused ? nullptr : a.take(2 * (int64_t)m.C * m.C * m.ks[g]);
+  s.am = m.fsmall ? a.take((int64_t)m.K * m.NN) : nullptr;
+  k.w.gemm_ws = a.take(kGemmWs);
+  k.w.gemm_ws_side = a.take(kGemmWs);
+  if (m.first || !m.tfused) s.E = a.take(m.BFT * m.N);
+  if (!m.tfused) {
+    s.qkv = a.take(m.BFT * m.QW);
+    s.att = a.take(m.BFT * m.h * m.T);
+    s.ctx = a.take(m.BFT * m.HV);
+    s.u_tat = a.take(m.BFT * m.N);
+  }
+  s.O = a.take(m.BFT * m.N);
+  s.u_s = a.take(m.BN * m.D);
+  s.Zd = a.take(m.BN * m.D);
+  s.qk = a.take(m.BN * 2 * m.KD);
+  if (!m.flash) s.P = a.take((int64_t)m.B * m.K * m.NN);
+  if (!m.sparse) s.W = a.take((int64_t)m.B * m.K * m.NN);
+  if (m.flash && !m.fsmall) s.lse = a.take((int64_t)m.B * m.K * m.N);
+  if (m.flash) s.wsupp = a.take((int64_t)m.B * m.K * m.nnz);
+  if (!m.agg) s.xth = a.take(m.BN * m.KCT);
+  s.X = (!m.first && !m.tfused) ? s.E : a.take(m.BN * m.CT);
+  if (!m.gfused)
+    for (int g = 0; g < 3; ++g) s.conv[g] = a.take(m.BN * 2 * m.C * std::max(m.Tg[g], 0));
+  return k;
+}
+
+size_t plan_work_size(const Dims& m) {
+  Arena a(nullptr);
+  plan_work(m, a);
+  return a.off + 256;
+}
+
 void plan_sizes(const Dims& m, size_t* save, size_t* scratch) {
   Arena a(nullptr);
   plan_save(m, a);
@@ -482,6 +543,9 @@ struct Fwd {
   bool e_side = false;           // E = x transposed is issued on the side stream (token e_ready)
   SyncTok e_ready;
   ChebFl fl;
+  // forward-only mode (dstagnn_block_forward_only): s and w come from plan_work, so every tensor
+  // only the backward reads is null, and the in-place LayerNorm inputs are not rewritten
+  bool lean = false;
   // the TAt stage's first product (launch), and beside it the forward's side work: E (e_side)
   // and x Theta (xth non-null) need only x and the re-laid parameters, so the fork's flag rides
   // on that product
@@ -570,7 +634,7 @@ struct Fwd {
       // O in [(f,t)][(b,n)] order: the pre_conv products read it with single-level unit-stride
       // maps (16-B DMA; no two-level k map in the weight gradient), row r = (b, ft) of the LN
       a.y = s.O; a.yrow = idx2(m.FT, m.BN, N);
-      a.u = s.u_tat; a.mu = s.mu_tat; a.rs = s.rs_tat;
+      a.u = lean ? nullptr : s.u_tat; a.mu = s.mu_tat; a.rs = s.rs_tat;
       DS_TRY(op_ln_fwd(a, st));
     }
     return 0;
@@ -597,6 +661,7 @@ struct Fwd {
     PrepSeg spare;  // (a segment past the capacity lands here; the call then fails below)
     auto add = [&](int kind, const float* src, float* dst, int64_t n, int p0 = 0, int p1 = 0, int p2 = 0,
                    int64_t off = 0) -> PrepSeg& {
+      if (lean && !dst) return spare;  // forward-only: a re-layout only the backward reads
       full = full || pp.nseg >= kPrepSegsHost;
       PrepSeg& g = full ? spare : pp.seg[pp.nseg++];
       g.kind = kind; g.src = src; g.dst = dst; g.n = n; g.p0 = p0; g.p1 = p1; g.p2 = p2; g.dst_off = off;
@@ -610,7 +675,7 @@ struct Fwd {
       add(8, p.tat_wk, s.Wqkv_p, m.HQ * m.NP, m.N, m.NP, 0, m.HQ * m.NP);
       add(8, p.tat_wv, s.Wqkv_p, m.HV * m.NP, m.N, m.NP, 0, 2 * m.HQ * m.NP);
     }
-    if (m.tfused_bwd) {  // the fused backward's B operands (zero-padded transposes, kind 9)
+    if (m.tfused_bwd && !lean) {  // the fused backward's B operands (zero-padded transposes, kind 9)
       add(9, p.tat_fc, s.WfcT, m.HV * m.NP, m.NP, (int)m.HV, m.NP, 0).p3 = m.N;
       add(9, p.tat_wq, s.WqT, m.NP * m.HQ, (int)m.HQ, m.N, (int)m.QW, 0).p3 = (int)m.HQ;
       add(9, p.tat_wk, s.WqT, m.NP * m.HQ, (int)m.HQ, m.N, (int)m.QW, m.HQ).p3 = (int)m.HQ;
@@ -618,7 +683,7 @@ struct Fwd {
     }
     add(0, p.sat_wq, s.Wqk, m.KD * m.D, 0, 0, 0, 0);
     add(0, p.sat_wk, s.Wqk, m.KD * m.D, 0, 0, 0, m.KD * m.D);
-    if (m.sfused) {  // [W_Q'; W_K']^T (D, 2 KD): WqkT[d][k] = W[k][d]
+    if (m.sfused && !lean) {  // [W_Q'; W_K']^T (D, 2 KD): WqkT[d][k] = W[k][d]
       add(9, p.sat_wq, s.WqkT, m.D * m.KD, (int)m.KD, m.D, (int)(2 * m.KD), 0).p3 = (int)m.KD;
       add(9, p.sat_wk, s.WqkT, m.D * m.KD, (int)m.KD, m.D, (int)(2 * m.KD), m.KD).p3 = (int)m.KD;
     }
@@ -627,13 +692,13 @@ struct Fwd {
     for (int g = 0; g < 3; ++g) {
       const int64_t n = 2 * (int64_t)m.C * m.C * m.ks[g];
       if (m.gfused) add(3, p.gtu_w[g], s.Wgt[g], n, m.C, m.ks[g]);  // (o, j, c): the fused forward
-      if (!m.gfused || m.gbfused) add(7, p.gtu_w[g], s.Wgf[g], n, m.C, m.ks[g]);  // (j, c, o): also the fused bwd
-      if (!m.gbfused) add(4, p.gtu_w[g], s.Wgb[g], n, m.C, m.ks[g]);
+      if (!m.gfused || (m.gbfused && !lean)) add(7, p.gtu_w[g], s.Wgf[g], n, m.C, m.ks[g]);  // (j, c, o): also the fused bwd
+      if (!m.gbfused && !lean) add(4, p.gtu_w[g], s.Wgb[g], n, m.C, m.ks[g]);
     }
     if (m.fsmall)  // the dense A_pa o M_k of the small-graph attention kernels (:122)
       for (int k = 0; k < m.K; ++k) {
         add(5, p.mask[k], s.am + (int64_t)k * m.NN, m.NN).src2 = gr.adj_pa;
-        add(6, p.mask[k], s.amt + (int64_t)k * m.NN, m.NN, m.N).src2 = gr.adj_pa;
+        if (!lean) add(6, p.mask[k], s.amt + (int64_t)k * m.NN, m.NN, m.N).src2 = gr.adj_pa;
       }
     if (full) {
       set_last_error("param_prep: more parameter re-layouts than kPrepSegsHost");
@@ -652,7 +717,7 @@ struct Fwd {
       a.nsrc = 2;
       a.g = p.embS_g; a.b = p.embS_b;
       a.y = s.Zd; a.yrow = idx1(m.D);
-      a.u = s.u_s; a.mu = s.mu_s; a.rs = s.rs_s;
+      a.u = lean ? nullptr : s.u_s; a.mu = s.mu_s; a.rs = s.rs_s;
       if (d.train && d.drop_p > 0.f) {
         a.drop_p = d.drop_p; a.seed = d.seed; a.which = 0; a.drop_off = drop_off(d, 0);
       }
@@ -745,6 +810,28 @@ struct Fwd {
     t.X = s.X; t.x = x; t.res_w = p.res_w; t.res_b = p.res_b; t.ln_g = p.ln_g; t.ln_b = p.ln_b;
     if (d.train && d.drop_p > 0.f) { t.drop_p = d.drop_p; t.seed = d.seed; t.drop_off = drop_off(d, 1); }
     t.G = s.G; t.tco = s.tco; t.r = s.r; t.mu = s.mu_c; t.rs = s.rs_c; t.out = out;
+    if (lean && gtu_tail_fwd_split(m.C, m.T)) {
+      // forward-only, split tail: G in the main GEMM workspace (idle since the convolutions), as
+      // many nodes at a time as fit it; the fcmy GEMM's output passes through the out buffer (a
+      // workgroup of the tail kernel reads its node's values before it stores that node's
+      // output).  A GEMM that does not split K keeps one summation order whatever its row count
+      // (gemm.hip plan_gemm), so the chunks change no bit.
+      const int64_t per = (int64_t)m.C * m.S, nb = (int64_t)kGemmWs / per;
+      if (nb < 1) { set_last_error("gtu_tail: C*(3T-12) exceeds the GEMM workspace"); return DSTAGNN_E_SHAPE; }
+      for (int64_t bn0 = 0; bn0 < m.BN; bn0 += nb) {
+        GtuTailArgs c = t;
+        c.BN = std::min(nb, m.BN - bn0);
+        for (int q = 0; q < 3; ++q) c.conv[q] = t.conv[q] + bn0 * m.Tg[q] * 2 * m.C;
+        c.X = t.X + bn0 * m.CT;
+        c.x = t.x + bn0 * (m.first ? (int64_t)m.T : m.CT);
+        c.drop_off = t.drop_off + (uint64_t)(bn0 * m.CT);
+        c.out = out + bn0 * m.CT;
+        c.tco = c.out;
+        c.G = w.gemm_ws;
+        DS_TRY(op_gtu_tail_fwd(c, st));
+      }
+      return 0;
+    }
     return op_gtu_tail_fwd(t, st);
   }
 
@@ -1585,6 +1672,32 @@ int dstagnn_block_forward(const dstagnn_block_dims* d, const dstagnn_block_param
   SaveBufs s = plan_save(m, a);
   Scratch w = plan_scratch(m, b);
   Fwd f{m, *d, *p, *g, x, d->res_mode ? res_att : nullptr, out, re_at, s, w, (hipStream_t)stream};
+  return f.run();
+}
+
+int dstagnn_block_forward_only_size(const dstagnn_block_dims* d, size_t* work_bytes) {
+  DS_TRY(check_dims(d));
+  if (!work_bytes) return DSTAGNN_E_ARG;
+  *work_bytes = plan_work_size(mkdims(*d));
+  return 0;
+}
+
+int dstagnn_block_forward_only(const dstagnn_block_dims* d, const dstagnn_block_params* p, const dstagnn_graph* g,
+                               const float* x, const float* res_att, float* out, float* re_at, void* work,
+                               size_t work_bytes, dstagnn_stream_t stream) {
+  DS_TRY(check_dims(d));
+  if (!p || !g || !x || !out || !re_at || !work) { set_last_error("null argument"); return DSTAGNN_E_ARG; }
+  if (d->res_mode != DSTAGNN_RES_NONE && !res_att) { set_last_error("res_att missing"); return DSTAGNN_E_ARG; }
+  Dims m = mkdims(*d);
+  if (work_bytes < plan_work_size(m)) {
+    set_last_error("work smaller than dstagnn_block_forward_only_size()");
+    return DSTAGNN_E_SPACE;
+  }
+  DS_TRY(check_graph(m, g));
+  Arena a(align256(work));
+  WorkBufs k = plan_work(m, a);
+  Fwd f{m, *d, *p, *g, x, d->res_mode ? res_att : nullptr, out, re_at, k.s, k.w, (hipStream_t)stream};
+  f.lean = true;
   return f.run();
 }
 

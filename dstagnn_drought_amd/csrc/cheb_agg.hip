@@ -80,6 +80,13 @@ constexpr int gather_wpe() {
   return kNQ >= 12 ? 2 : (agg_prefetch<kNQ>() ? 2 : 1) * kE * kNQ + KM * kNQ + 40 <= 110 ? 4
        : ((agg_prefetch<kNQ>() ? 2 : 1) * kE * kNQ + KM * kNQ + 40 <= 125 ? 3 : 2);
 }
+// the forward-only forms (SAVE = false) of the forward kernels: the variants whose accumulators
+// do not fit 256 VGPRs (they spill at the target above) take one wave per SIMD and the whole
+// register file instead — none of them spills
+template <int kNQ, int KM, bool SAVE>
+constexpr int gather_wpe_fwd() {
+  return !SAVE && (KM >= 16 || (kNQ >= 12 && KM >= 8) || (kNQ >= 16 && KM >= 5)) ? 1 : gather_wpe<kNQ, KM>();
+}
 template <int kNQ, int KM, bool PF = agg_prefetch<kNQ>()>
 constexpr int sddmm_wpe() {
   // without the batch prefetch (PF false, DSTAGNN_SDDMM_NOPF=1): one batch of rows fewer in
@@ -92,8 +99,9 @@ constexpr int kAs = 33;    // LDS row stride of a 32 x 32 operand tile
 // ---------------------------------------------------------------------------------------
 // forward: one wave per (b, j, time chunk)
 // ---------------------------------------------------------------------------------------
-template <int kNQ, int KM>  // kNQ >= F * Tc / 64, KM >= K
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(gather_wpe<kNQ, KM>(), 8))) void cheb_agg_fwd_kernel(ChebAg a) {
+// SAVE = false (the forward-only block): agg_k only staged in LDS, a.agg neither stored nor read
+template <int kNQ, int KM, bool SAVE = true>  // kNQ >= F * Tc / 64, KM >= K
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(gather_wpe_fwd<kNQ, KM, SAVE>(), 8))) void cheb_agg_fwd_kernel(ChebAg a) {
   __shared__ float As[4][32 * kAs];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5, l32 = lane & 31;
   const int64_t wv = xcd_block(a.xcd_order) * 4 + w;
@@ -174,11 +182,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(gather_wpe<
     }
     // agg_k[j] saved for the Theta gradient, and staged as the MFMA A operand [f][t'] (the
     // previous k's reads of the tile precede these writes in the wave's LDS order)
-    float* sv = a.agg + (((int64_t)b * a.N + j) * a.K + k) * FT;
+    float* sv = SAVE ? a.agg + (((int64_t)b * a.N + j) * a.K + k) * FT : nullptr;
 #pragma unroll
     for (int q = 0; q < kNQ; ++q)
       if (lane + 64 * q < nel) {
-        sv[xo[q]] = ag[k][q];
+        if (SAVE) sv[xo[q]] = ag[k][q];
         at[lo[q]] = ag[k][q];
       }
     wave_lds_sync();
@@ -207,8 +215,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(gather_wpe<
 // (m = bsel T + t), so the Theta_k chain of 16 MFMAs serves both.  Per sample the same sums in
 // the same order as cheb_agg_fwd_kernel (entries in support order, orders k separately).
 // ---------------------------------------------------------------------------------------
-template <int kNQ, int KM>  // kNQ >= F * T / 64 (<= 8), KM >= K
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(gather_wpe<kNQ, 2 * KM>(), 8))) void cheb_agg_fwd2_kernel(ChebAg a) {
+template <int kNQ, int KM, bool SAVE = true>  // kNQ >= F * T / 64 (<= 8), KM >= K; SAVE as cheb_agg_fwd_kernel
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(gather_wpe_fwd<kNQ, 2 * KM, SAVE>(), 8))) void cheb_agg_fwd2_kernel(ChebAg a) {
   static_assert(kNQ <= 8, "F T <= 512");
   __shared__ float As[4][32 * kAs];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5, l32 = lane & 31;
@@ -296,11 +304,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(gather_wpe<
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       if (s >= nb) break;
-      float* sv = a.agg + (((int64_t)(b0 + s) * a.N + j) * a.K + k) * FT;  // agg_k[j], saved for dTheta
+      float* sv = SAVE ? a.agg + (((int64_t)(b0 + s) * a.N + j) * a.K + k) * FT : nullptr;  // agg_k[j], saved for dTheta
 #pragma unroll
       for (int q = 0; q < kNQ; ++q)
         if (lane + 64 * q < FT) {
-          sv[lane + 64 * q] = ag[s][k][q];
+          if (SAVE) sv[lane + 64 * q] = ag[s][k][q];
           at[lo[q] + s * T] = ag[s][k][q];
         }
     }
@@ -849,6 +857,19 @@ struct Fwd2L {
     if constexpr (NQ <= 8) hipLaunchKernelGGL((cheb_agg_fwd2_kernel<NQ, KM>), l.grid, dim3(256), 0, l.st, l.a);
   }
 };
+// the forward-only forms (a.agg null)
+template <int NQ, int KM>
+struct FwdNsL {
+  static void run(const Launch& l) {
+    hipLaunchKernelGGL((cheb_agg_fwd_kernel<NQ, KM, false>), l.grid, dim3(256), 0, l.st, l.a);
+  }
+};
+template <int NQ, int KM>
+struct Fwd2NsL {
+  static void run(const Launch& l) {
+    if constexpr (NQ <= 8) hipLaunchKernelGGL((cheb_agg_fwd2_kernel<NQ, KM, false>), l.grid, dim3(256), 0, l.st, l.a);
+  }
+};
 template <int NQ, int KM>
 struct SddmmL {
   static void run(const Launch& l) {
@@ -934,11 +955,16 @@ int op_cheb_agg_fwd(const ChebAg& a0, hipStream_t st) {
   const ChebAg a = with_order(a0);
   // T <= 16: sample pairs per wave (cheb_agg_fwd2_kernel; DSTAGNN_AGG_PAIR=0: one sample)
   static const bool pair_env = env_flag("DSTAGNN_AGG_PAIR", true);
-  if (pair_env && a.T <= 16 && a.F * a.T <= 512)
-    dispatch<Fwd2L>(nq_of(a.F * a.T), km_of(a.K), Launch{a, dim3(grid_rows((int64_t)((a.B + 1) / 2) * a.N)), 0, st});
-  else
-    dispatch<FwdL>(nq_of(a.F * std::min(32, a.T)), km_of(a.K),
-                   Launch{a, dim3(grid_rows((int64_t)a.B * a.N), (unsigned)cdiv64(a.T, 32)), 0, st});
+  const bool save = a.agg != nullptr;  // null: the forward-only block, nothing kept for dTheta
+  if (pair_env && a.T <= 16 && a.F * a.T <= 512) {
+    const Launch l{a, dim3(grid_rows((int64_t)((a.B + 1) / 2) * a.N)), 0, st};
+    if (save) dispatch<Fwd2L>(nq_of(a.F * a.T), km_of(a.K), l);
+    else dispatch<Fwd2NsL>(nq_of(a.F * a.T), km_of(a.K), l);
+  } else {
+    const Launch l{a, dim3(grid_rows((int64_t)a.B * a.N), (unsigned)cdiv64(a.T, 32)), 0, st};
+    if (save) dispatch<FwdL>(nq_of(a.F * std::min(32, a.T)), km_of(a.K), l);
+    else dispatch<FwdNsL>(nq_of(a.F * std::min(32, a.T)), km_of(a.K), l);
+  }
   DS_CHECK_LAUNCH();
   return 0;
 }

@@ -165,6 +165,8 @@ __device__ __forceinline__ float dot32(const float* x, const float (&y)[32]) {
 }
 
 // forward: P and W = T o P on the support of column j (CSC order).  One thread per (b,k,j).
+// SAVE = false (the forward-only block): W only, a.psupp not touched.
+template <bool SAVE>
 __global__ __launch_bounds__(256) void flash_psupp_kernel(ChebFl a) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (t >= (int64_t)a.B * a.K * a.N) return;
@@ -186,7 +188,7 @@ __global__ __launch_bounds__(256) void flash_psupp_kernel(ChebFl a) {
     const float w = a.apa[o];
     const float z = dot32(Q + (int64_t)i * a.ld, kv) * a.scale + (w != 0.f ? w * Mk[o] : 0.f);
     const float P = __expf(z - lse);
-    a.psupp[base + p] = P;
+    if (SAVE) a.psupp[base + p] = P;
     a.wsupp[base + p] = a.tsupp[(int64_t)k * a.nnz + p] * P;
   }
 }
@@ -363,7 +365,9 @@ constexpr int kStripE = 512;         // sparse entries of one strip staged in LD
 
 // forward: lse_j, P and W = T o P on the T support, P on the A_pa support, for one
 // (b, k, 32-column strip).  The strip's P tile goes through LDS ((32 nt) x 33 floats, dynamic).
-template <int kSmallTiles>
+// SAVE = false (the forward-only block): W only — lse, psupp and papa (and the A_pa support walk)
+// are the backward's and are neither written nor addressed.
+template <int kSmallTiles, bool SAVE>
 __global__ __launch_bounds__(256) void flash_small_fwd_kernel(ChebFl a) {
   extern __shared__ float Pt[];  // [(32 nt)][33]
   __shared__ float red_m[4][32], red_l[4][32];
@@ -377,7 +381,8 @@ __global__ __launch_bounds__(256) void flash_small_fwd_kernel(ChebFl a) {
   // the strip's support walk (8 threads per column): pointers now, first entries below
   const int jl = threadIdx.x >> 3, sub = threadIdx.x & 7, jj = min(jt * 32 + jl, a.N - 1);
   const bool jok = jt * 32 + jl < a.N;
-  const int p0 = a.csc_ptr[jj], p1 = a.csc_ptr[jj + 1], q0 = a.apa_ptr[jj], q1 = a.apa_ptr[jj + 1];
+  const int p0 = a.csc_ptr[jj], p1 = a.csc_ptr[jj + 1];
+  const int q0 = SAVE ? a.apa_ptr[jj] : 0, q1 = SAVE ? a.apa_ptr[jj + 1] : 0;
   // every operand of this wave's tiles in the same round
   float bkv[16], aq[kSmallTiles][16], am[kSmallTiles][16];
   load16(Kp + (int64_t)jc * a.ld + h * 16, bkv);
@@ -391,7 +396,7 @@ __global__ __launch_bounds__(256) void flash_small_fwd_kernel(ChebFl a) {
     }
   }
   const int pf = p0 + sub, qf = q0 + sub;  // first support entries of this thread
-  const int row_p = pf < p1 ? a.csc_row[pf] : 0, row_q = qf < q1 ? a.apa_row[qf] : 0;
+  const int row_p = pf < p1 ? a.csc_row[pf] : 0, row_q = SAVE && qf < q1 ? a.apa_row[qf] : 0;
   const float t_p = pf < p1 ? a.tsupp[(int64_t)k * a.nnz + pf] : 0.f;
   float z[kSmallTiles][16];
   float mx = -INFINITY;
@@ -425,7 +430,7 @@ __global__ __launch_bounds__(256) void flash_small_fwd_kernel(ChebFl a) {
   if (h == 0) red_l[w][l32] = l;
   __syncthreads();
   const float lse = M + __logf((red_l[0][l32] + red_l[1][l32]) + (red_l[2][l32] + red_l[3][l32]));
-  if (w == 0 && h == 0 && j < a.N) a.lse[(int64_t)bk * a.N + j] = lse;
+  if (SAVE && w == 0 && h == 0 && j < a.N) a.lse[(int64_t)bk * a.N + j] = lse;
 #pragma unroll
   for (int q = 0; q < kSmallTiles; ++q) {
     const int it = w + 4 * q;
@@ -439,11 +444,13 @@ __global__ __launch_bounds__(256) void flash_small_fwd_kernel(ChebFl a) {
   for (int p = pf; p < p1; p += 8) {
     const int i = p == pf ? row_p : a.csc_row[p];
     const float P = Pt[i * 33 + jl];
-    a.psupp[base + p] = P;
+    if (SAVE) a.psupp[base + p] = P;
     a.wsupp[base + p] = (p == pf ? t_p : a.tsupp[(int64_t)k * a.nnz + p]) * P;
   }
-  const int64_t abase = (int64_t)bk * a.apa_nnz;
-  for (int q = qf; q < q1; q += 8) a.papa[abase + q] = Pt[(q == qf ? row_q : a.apa_row[q]) * 33 + jl];
+  if (SAVE) {
+    const int64_t abase = (int64_t)bk * a.apa_nnz;
+    for (int q = qf; q < q1; q += 8) a.papa[abase + q] = Pt[(q == qf ? row_q : a.apa_row[q]) * 33 + jl];
+  }
 }
 
 // stage rows [0, N) of one (b, k) 32-float block of qk (Q' or K') into LDS X[(32 nt)][kXs]
@@ -963,12 +970,23 @@ int allow_lds(Kern k, size_t bytes) {
 
 int op_flash_forward(const ChebFl& a, hipStream_t st) {
   const int nt = (a.N + 31) >> 5;
+  // forward-only (psupp null): W alone is written; the small-graph kernel then keeps no lse or
+  // papa either (nothing in the forward reads them), the streamed pair still passes lse along
+  const bool save = a.psupp != nullptr;
+  if (!a.wsupp || (a.am ? (save ? !a.lse || !a.papa : a.lse || a.papa) : !a.lse)) {
+    set_last_error("flash_forward: saved outputs must be all set, or null for the forward-only form");
+    return DSTAGNN_E_ARG;
+  }
   if (a.am) {  // small graphs (flash_small): statistics and the support P from the same score tiles
     const size_t lds = (size_t)nt * 32 * 33 * sizeof(float);
     const dim3 grid((unsigned)((int64_t)a.B * a.K * nt));
     switch ((nt + 3) / 4) {  // tiles per wave
-#define DS_FWD(T) case T: DS_TRY(allow_lds(flash_small_fwd_kernel<T>, lds)); \
-      hipLaunchKernelGGL(flash_small_fwd_kernel<T>, grid, dim3(256), lds, st, a); break;
+#define DS_FWD(T) case T: \
+      if (save) { DS_TRY(allow_lds(flash_small_fwd_kernel<T, true>, lds)); \
+        hipLaunchKernelGGL((flash_small_fwd_kernel<T, true>), grid, dim3(256), lds, st, a); } \
+      else { DS_TRY(allow_lds(flash_small_fwd_kernel<T, false>, lds)); \
+        hipLaunchKernelGGL((flash_small_fwd_kernel<T, false>), grid, dim3(256), lds, st, a); } \
+      break;
       DS_FWD(1) DS_FWD(2) DS_FWD(3) DS_FWD(4)
 #undef DS_FWD
       default: set_last_error("flash: graph too large for the small-graph kernels"); return DSTAGNN_E_SHAPE;
@@ -978,7 +996,9 @@ int op_flash_forward(const ChebFl& a, hipStream_t st) {
   }
   hipLaunchKernelGGL(flash_stats_kernel, dim3(grid_waves((int64_t)a.B * a.K * nt)), dim3(256), 0, st, a);
   DS_CHECK_LAUNCH();
-  hipLaunchKernelGGL(flash_psupp_kernel, dim3((unsigned)cdiv64((int64_t)a.B * a.K * a.N, 256)), dim3(256), 0, st, a);
+  const dim3 pgrid((unsigned)cdiv64((int64_t)a.B * a.K * a.N, 256));
+  if (save) hipLaunchKernelGGL(flash_psupp_kernel<true>, pgrid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(flash_psupp_kernel<false>, pgrid, dim3(256), 0, st, a);
   DS_CHECK_LAUNCH();
   return 0;
 }

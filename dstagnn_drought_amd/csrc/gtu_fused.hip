@@ -65,8 +65,8 @@ __device__ __forceinline__ float gf_row16_sum(float x) {
 // half h = w & 1 (16 tanh columns and the same 16 sigmoid columns) for row tiles w/2 + 4u; the
 // gates go to Gs, conv_k (+ bias) to HBM.  p0 / q0 hold the first B fragments on entry (issued
 // by the caller ahead of the previous GTU's stores); on exit they hold the next GTU's (KN = 0:
-// none).
-template <int KS, int KN>
+// none).  SAVE = false (the forward-only block): conv_k is not stored and a.conv is not read.
+template <int KS, int KN, bool SAVE>
 __device__ __forceinline__ void gf_gtu(const GtuFusedArgs& a, int q, int s_off, int64_t bn0, int nn, const float* Xs,
                                        float* Gs, int w, int i, int lq, float4& p0, float4& q0) {
   constexpr int Tg = kGT - KS + 1, KK = KS * kGC, NCH = KK / 16;
@@ -128,7 +128,7 @@ __device__ __forceinline__ void gf_gtu(const GtuFusedArgs& a, int q, int s_off, 
   const int c0 = h * 16 + 4 * lq;
   const float4 bp4 = *reinterpret_cast<const float4*>(a.bias[q] + c0);
   const float4 bq4 = *reinterpret_cast<const float4*>(a.bias[q] + kGC + c0);
-  float* conv = a.conv[q];
+  float* conv = SAVE ? a.conv[q] : nullptr;
 #pragma unroll
   for (int u = 0; u < kGMTW; ++u) {
     if (mt0 + 4 * u >= MT) continue;
@@ -137,16 +137,20 @@ __device__ __forceinline__ void gf_gtu(const GtuFusedArgs& a, int q, int s_off, 
     const int n = m / Tg, tp = m - n * Tg;
     const float4 P = make_float4(accp[u][0] + bp4.x, accp[u][1] + bp4.y, accp[u][2] + bp4.z, accp[u][3] + bp4.w);
     const float4 Q = make_float4(accq[u][0] + bq4.x, accq[u][1] + bq4.y, accq[u][2] + bq4.z, accq[u][3] + bq4.w);
-    float* row = conv + ((bn0 + n) * Tg + tp) * (2 * kGC);
-    *reinterpret_cast<float4*>(row + c0) = P;
-    *reinterpret_cast<float4*>(row + kGC + c0) = Q;
+    if (SAVE) {
+      float* row = conv + ((bn0 + n) * Tg + tp) * (2 * kGC);
+      *reinterpret_cast<float4*>(row + c0) = P;
+      *reinterpret_cast<float4*>(row + kGC + c0) = Q;
+    }
     float* g = Gs + (n * kGC + c0) * kGSP + s_off + tp;
 #pragma unroll
     for (int r = 0; r < 4; ++r) g[r * kGSP] = gf_tanh(g4at(P, r)) * gf_sigmoid(g4at(Q, r));
   }
 }
 
-template <bool FIRST>
+// SAVE = false: the forward-only block's variant — the same arithmetic, none of the stores that
+// only the backward reads (conv_k, tco, r, mu, rs, G) and none of their pointers
+template <bool FIRST, bool SAVE>
 __global__ __launch_bounds__(kGW * 64, 1) void gtu_fwd_fused_kernel(GtuFusedArgs a) {
   constexpr int NT = kGW * 64;
   extern __shared__ float4 lds4[];
@@ -215,11 +219,11 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_fwd_fused_kernel(GtuFusedArgs
   TF_MARK(1);
 
   // ---- 2. the three convolutions and their gates --------------------------------------------
-  gf_gtu<3, 5>(a, 0, 0, bn0, nn, Xs, Gs, w, i, lq, p0, q0);
+  gf_gtu<3, 5, SAVE>(a, 0, 0, bn0, nn, Xs, Gs, w, i, lq, p0, q0);
   TF_MARK(2);
-  gf_gtu<5, 7>(a, 1, kGT - 2, bn0, nn, Xs, Gs, w, i, lq, p0, q0);
+  gf_gtu<5, 7, SAVE>(a, 1, kGT - 2, bn0, nn, Xs, Gs, w, i, lq, p0, q0);
   TF_MARK(3);
-  gf_gtu<7, 0>(a, 2, 2 * kGT - 6, bn0, nn, Xs, Gs, w, i, lq, p0, q0);
+  gf_gtu<7, 0, SAVE>(a, 2, 2 * kGT - 6, bn0, nn, Xs, Gs, w, i, lq, p0, q0);
   TF_MARK(4);
   __syncthreads();
   TF_MARK(5);
@@ -264,7 +268,7 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_fwd_fused_kernel(GtuFusedArgs
         }
         rv[v][r] = fmaxf(xres + tco[r], 0.f);
       }
-      if (tv) {
+      if (SAVE && tv) {
         *reinterpret_cast<float4*>(a.tco + ge0) = make_float4(tco[0], tco[1], tco[2], tco[3]);
         *reinterpret_cast<float4*>(a.r + ge0) = make_float4(rv[v][0], rv[v][1], rv[v][2], rv[v][3]);
       }
@@ -289,7 +293,7 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_fwd_fused_kernel(GtuFusedArgs
         *reinterpret_cast<float4*>(a.out + bn0 * kGCT + n * kGCT + (16 * v + i) * kGT + t0) =
             make_float4(o[0], o[1], o[2], o[3]);
       }
-      if (i == 0) {
+      if (SAVE && i == 0) {
         *reinterpret_cast<float4*>(a.mu + (bn0 + n) * kGT + t0) = make_float4(mean[0], mean[1], mean[2], mean[3]);
         *reinterpret_cast<float4*>(a.rs + (bn0 + n) * kGT + t0) = make_float4(rs[0], rs[1], rs[2], rs[3]);
       }
@@ -297,7 +301,7 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_fwd_fused_kernel(GtuFusedArgs
   }
   TF_MARK(6);
   // G out (the fcmy weight gradient's operand): the nodes' [c][s] rows are one contiguous block
-  {
+  if (SAVE) {
     float4* gout = reinterpret_cast<float4*>(a.G + bn0 * kGC * kGS);
     for (int e4 = tid; e4 < nn * kGC * (kGS / 4); e4 += NT) {
       const int nc = e4 / (kGS / 4), s = 4 * (e4 - nc * (kGS / 4));
@@ -823,6 +827,14 @@ int op_gtu_fused_fwd(const GtuFusedArgs& a, hipStream_t st) {
     set_last_error("gtu_fused_fwd: unsupported shape");
     return DSTAGNN_E_SHAPE;
   }
+  // forward-only: every saved-for-backward output null (the SAVE = false kernel); a mix is an error
+  const int nsave = (a.G != nullptr) + (a.tco != nullptr) + (a.r != nullptr) + (a.mu != nullptr) + (a.rs != nullptr) +
+                    (a.conv[0] != nullptr) + (a.conv[1] != nullptr) + (a.conv[2] != nullptr);
+  if (nsave != 0 && nsave != 8) {
+    set_last_error("gtu_fused_fwd: saved outputs must be all set or all null");
+    return DSTAGNN_E_ARG;
+  }
+  const bool save = nsave == 8;
   bool al = gf_al16(a.X) && gf_al16(a.x) && gf_al16(a.G) && gf_al16(a.tco) && gf_al16(a.r) && gf_al16(a.mu) &&
             gf_al16(a.rs) && gf_al16(a.out) && gf_al16(a.fcmy_b);
   for (int q = 0; q < 3; ++q) al = al && gf_al16(a.conv[q]) && gf_al16(a.wt[q]) && gf_al16(a.bias[q]);
@@ -831,7 +843,8 @@ int op_gtu_fused_fwd(const GtuFusedArgs& a, hipStream_t st) {
     return DSTAGNN_E_ARG;
   }
   using Kern = void (*)(GtuFusedArgs);
-  const Kern k = a.first ? gtu_fwd_fused_kernel<true> : gtu_fwd_fused_kernel<false>;
+  const Kern k = save ? (a.first ? gtu_fwd_fused_kernel<true, true> : gtu_fwd_fused_kernel<false, true>)
+                      : (a.first ? gtu_fwd_fused_kernel<true, false> : gtu_fwd_fused_kernel<false, false>);
   const size_t lds = gtu_fused_lds();
   {
     static std::mutex mu;

@@ -166,8 +166,10 @@ __device__ __forceinline__ void col_sums_over_c(const float* v, int C, int T, in
 }
 
 // PH: 0 = fused, 2 = split path: from the GEMM's tc (in tco) to the output (the gates run
-// in gtu_gates_kernel)
-template <bool WL, int PH = 0, int NT = kNT>
+// in gtu_gates_kernel).  SAVE = false (the forward-only block): no store of G, tco, r, mu or rs
+// (PH == 2 still reads the GEMM's tc through a.tco, which may then be the out buffer itself: a
+// workgroup reads its node's tc before the barriers that precede its out stores)
+template <bool WL, int PH = 0, int NT = kNT, bool SAVE = true>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 8))) void gtu_tail_fwd_kernel(GtuTailArgs a) {
   extern __shared__ float lds[];
   const int C = a.C, T = a.T, S = 3 * T - 12, CT = C * T, C2 = 2 * C, CS = C * S;
@@ -217,7 +219,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 8))) void
     if (!a.first)
       for (int e = tid; e < CT; e += NT) Xs[(e / C) * CP + e % C] = a.X[base + e];  // X rows (t, c)
     __syncthreads();
-    if (PH != 2)
+    if (SAVE && PH != 2)
       for (int e = tid; e < CS; e += NT) a.G[bn * CS + e] = Gs[(e / S) * SP + e % S];  // [c][s], coalesced
     // fcmy + dropout + residual + ReLUs; element e = (c, t) of the (C, T) output
     #pragma unroll 1
@@ -253,8 +255,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 8))) void
           xres = xv[u];
         }
         const float r = fmaxf(xres + tco, 0.f);
-        a.tco[base + e] = tco;
-        a.r[base + e] = r;
+        if (SAVE) {
+          a.tco[base + e] = tco;
+          a.r[base + e] = r;
+        }
         rl[e] = r;
       }
     }
@@ -276,8 +280,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 8))) void
       for (int q = 0; q < L.P; ++q) var += red[q * T + t];
       const float rs = rsqrtf(var * (1.f / C) + 1e-5f);
       rss[t] = rs;
-      a.mu[bn * T + t] = mus[t];
-      a.rs[bn * T + t] = rs;
+      if (SAVE) {
+        a.mu[bn * T + t] = mus[t];
+        a.rs[bn * T + t] = rs;
+      }
     }
     __syncthreads();
     for (int e = tid; e < CT; e += NT) {
@@ -616,7 +622,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 8))) void
 // FIRST (compile-time a.first): no uniform branch among the node's loads — a branch there made
 // the compiler wait for every load issued before it (vmcnt(0) at the join), splitting the one
 // round into three dependent ones
-template <int C, int T, int NT, bool FIRST>
+template <int C, int T, int NT, bool FIRST, bool SAVE = true>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 8))) void gtu_tail_fwd_ct_kernel(GtuTailArgs a) {
   constexpr int S = 3 * T - 12, CT = C * T, C2 = 2 * C, CS = C * S, SP = S + 1, CP = C + 1;
   constexpr int P = T < NT ? NT / T : 1, NRED = P * T > NT ? P * T : NT;
@@ -679,7 +685,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 8))) void
       }
     }
     __syncthreads();
-    for (int e = tid; e < CS; e += NT) a.G[bn * CS + e] = Gs[(e / S) * SP + e % S];  // [c][s], coalesced
+    if (SAVE)
+      for (int e = tid; e < CS; e += NT) a.G[bn * CS + e] = Gs[(e / S) * SP + e % S];  // [c][s], coalesced
     // fcmy + dropout + residual + ReLUs; element e = (c, t) of the (C, T) output
 #pragma unroll
     for (int u = 0; u < NE; ++u) {
@@ -700,8 +707,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 8))) void
         xres = xv[u];
       }
       const float r = fmaxf(xres + tco, 0.f);
-      a.tco[base + e] = tco;
-      a.r[base + e] = r;
+      if (SAVE) {
+        a.tco[base + e] = tco;
+        a.r[base + e] = r;
+      }
       rl[e] = r;
     }
     __syncthreads();
@@ -722,8 +731,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 8))) void
       for (int q = 0; q < P; ++q) var += red[q * T + t];
       const float rs = rsqrtf(var * (1.f / C) + 1e-5f);
       rss[t] = rs;
-      a.mu[bn * T + t] = mus[t];
-      a.rs[bn * T + t] = rs;
+      if (SAVE) {
+        a.mu[bn * T + t] = mus[t];
+        a.rs[bn * T + t] = rs;
+      }
     }
     __syncthreads();
 #pragma unroll
@@ -1013,14 +1024,40 @@ bool tail_split_bwd(const GtuTailArgs& a) {
 // threads each keep 8 waves per CU in flight instead of 2
 constexpr int kSplitNT = 256;
 
+bool gtu_tail_fwd_split(int C, int T) {
+  GtuTailArgs a;
+  a.C = C; a.T = T;
+  return tail_split_fwd(a);
+}
+
 bool gtu_tail_bwd_split(int C, int T) {
   GtuTailArgs a;
   a.C = C; a.T = T;
   return tail_split_bwd(a);
 }
 
+template <int T>
+static void launch_tail_ct(const GtuTailArgs& a, bool save, hipStream_t st) {
+  const dim3 g(node_grid(a.BN));
+  if (save) {
+    if (a.first) hipLaunchKernelGGL((gtu_tail_fwd_ct_kernel<32, T, 256, true>), g, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((gtu_tail_fwd_ct_kernel<32, T, 256, false>), g, dim3(256), 0, st, a);
+  } else {
+    if (a.first) hipLaunchKernelGGL((gtu_tail_fwd_ct_kernel<32, T, 256, true, false>), g, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((gtu_tail_fwd_ct_kernel<32, T, 256, false, false>), g, dim3(256), 0, st, a);
+  }
+}
+
 int op_gtu_tail_fwd(const GtuTailArgs& a, hipStream_t st) {
-  if (tail_split_fwd(a)) {  // long series: gates | fcmy GEMM | tail
+  // forward-only (r null): none of the saved-for-backward outputs is written, so all of them
+  // must be null — but for the split path's G and tc (a.tco), which its own GEMM reads
+  const bool save = a.r != nullptr;
+  const bool split = tail_split_fwd(a);
+  if (save ? (!a.G || !a.tco || !a.mu || !a.rs) : (a.mu || a.rs || (split ? (!a.G || !a.tco) : (a.G || a.tco)))) {
+    set_last_error("gtu_tail_fwd: saved outputs must be all set, or null for the forward-only form");
+    return DSTAGNN_E_ARG;
+  }
+  if (split) {  // long series: gates | fcmy GEMM | tail
     const int S = 3 * a.T - 12;
     if (fwd_lds(a, false, false) > kLdsMax) { set_last_error("gtu_tail: C*T too large for LDS"); return DSTAGNN_E_SHAPE; }
     {
@@ -1032,21 +1069,18 @@ int op_gtu_tail_fwd(const GtuTailArgs& a, hipStream_t st) {
       DS_CHECK_LAUNCH();
     }
     DS_TRY(rows_gemm(a.G, S, a.fcmy_w, idx1(1), idx1(S), a.tco, a.T, a.BN * a.C, a.T, S, a.fcmy_b, st));
-    return launch_node_kernel(gtu_tail_fwd_kernel<false, 2, kSplitNT>, fwd_lds(a, false, false, kSplitNT), a, st, kSplitNT);
+    const size_t lds = fwd_lds(a, false, false, kSplitNT);
+    if (save) return launch_node_kernel(gtu_tail_fwd_kernel<false, 2, kSplitNT>, lds, a, st, kSplitNT);
+    return launch_node_kernel(gtu_tail_fwd_kernel<false, 2, kSplitNT, false>, lds, a, st, kSplitNT);
   }
   if (tail_ct(a)) {
-    const dim3 g(node_grid(a.BN));
-    if (a.T == 24) {
-      if (a.first) hipLaunchKernelGGL((gtu_tail_fwd_ct_kernel<32, 24, 256, true>), g, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((gtu_tail_fwd_ct_kernel<32, 24, 256, false>), g, dim3(256), 0, st, a);
-    } else {
-      if (a.first) hipLaunchKernelGGL((gtu_tail_fwd_ct_kernel<32, 12, 256, true>), g, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((gtu_tail_fwd_ct_kernel<32, 12, 256, false>), g, dim3(256), 0, st, a);
-    }
+    if (a.T == 24) launch_tail_ct<24>(a, save, st);
+    else launch_tail_ct<12>(a, save, st);
     DS_CHECK_LAUNCH();
     return 0;
   }
-  return launch_node_kernel(gtu_tail_fwd_kernel<true>, fwd_lds(a, true), a, st);
+  if (save) return launch_node_kernel(gtu_tail_fwd_kernel<true>, fwd_lds(a, true), a, st);
+  return launch_node_kernel(gtu_tail_fwd_kernel<true, 0, kNT, false>, fwd_lds(a, true), a, st);
 }
 
 // workgroups of the folding backward's grid-stride grid

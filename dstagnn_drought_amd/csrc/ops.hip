@@ -593,7 +593,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(LnFwd a) {
   }
   var = wave_sum(var) / L;
   const float rs = rsqrtf(var + a.eps);
-  if (lane == 0) { a.mu[row] = mean; a.rs[row] = rs; }
+  if (lane == 0 && a.mu) { a.mu[row] = mean; a.rs[row] = rs; }  // (null: forward-only, a scalar branch)
   const int64_t yo = ioff(a.yrow, row);
 #pragma unroll
   for (int q = 0; q < VPT; ++q) {
@@ -653,7 +653,7 @@ __global__ __launch_bounds__(256) void ln_fwd_v4_kernel(LnFwd a) {
     }
   var = wave_sum(var) / L;
   const float rs = rsqrtf(var + a.eps);
-  if (lane == 0) { a.mu[row] = mean; a.rs[row] = rs; }
+  if (lane == 0 && a.mu) { a.mu[row] = mean; a.rs[row] = rs; }  // (null: forward-only, a scalar branch)
   const int64_t yo = ioff(a.yrow, row);
   const DropKey dk = drop_key(a.seed, a.which);
   const float dscale = 1.0f / (1.0f - a.drop_p);
@@ -836,7 +836,7 @@ __global__ __launch_bounds__(256) void ln_fwd_wg_kernel(LnFwd a) {
     if (tid + 256 * q < L) { const float d = v[q] - mean; var += d * d; }
   var = wg_sum4(var, red4) / L;
   const float rs = rsqrtf(var + a.eps);
-  if (tid == 0) { a.mu[row] = mean; a.rs[row] = rs; }
+  if (tid == 0 && a.mu) { a.mu[row] = mean; a.rs[row] = rs; }  // (null: forward-only, a scalar branch)
   const int64_t yo = ioff(a.yrow, row);
 #pragma unroll
   for (int q = 0; q < VPT; ++q) {
@@ -1990,6 +1990,8 @@ static void launch_ln_fwd(const LnFwd& a, dim3 grid, hipStream_t st) {
 
 int op_ln_fwd(const LnFwd& a, hipStream_t st) {
   if (a.nsrc < 1 || a.nsrc > 3 || a.L < 1) { set_last_error("ln_fwd: 1..3 sources, L >= 1"); return DSTAGNN_E_ARG; }
+  // the statistics are kept together or (the forward-only block) not at all
+  if ((a.mu == nullptr) != (a.rs == nullptr)) { set_last_error("ln_fwd: mu and rs must both be set or both null"); return DSTAGNN_E_ARG; }
   dim3 grid((unsigned)cdiv64(a.R, 4));
   if (ln_fwd_v4_ok(a)) {  // float4 rows
 #define DS_LN4(V) \

@@ -384,5 +384,8 @@ int op_gtu_tail_fwd(const GtuTailArgs& a, hipStream_t st);
 int op_gtu_tail_bwd(const GtuTailArgs& a, hipStream_t st);
 // true when the backward runs split (LN | dG GEMM | gates) and needs GtuTailArgs::dG
 bool gtu_tail_bwd_split(int C, int T);
+// true when the forward runs split (gates | fcmy GEMM | tail): G and tc (GtuTailArgs::tco) are
+// then intermediates of the forward itself
+bool gtu_tail_fwd_split(int C, int T);
 int op_param_prep(const ParamPrep& a, hipStream_t st);
 int op_dropout_mask(float* out, int64_t n, uint64_t seed, uint32_t which, float p, uint64_t off, hipStream_t st);

@@ -226,7 +226,9 @@ __device__ __forceinline__ void tf_load_e_tile(const TatFusedArgs& a, int64_t R0
 // RA [PW h T^2] re_At | AT [PW h T^2] softmax — re_At / A / Q|K|V / ctx go out at the end
 // W waves (4: one per SIMD; 8: two per SIMD — each phase's work split over twice the waves, so
 // one wave's latency (LDS fragment loads, L2 weight loads, shuffles) hides behind its SIMD twin's)
-template <int T, int NTW, int W>  // NTW: LayerNorm values per lane (ceil(NP / 64))
+// SAVE = false (the forward-only block): only re_At and O leave the chip — no store of Q|K|V, A,
+// ctx, u, mu or rs, and none of their pointers
+template <int T, int NTW, int W, bool SAVE>  // NTW: LayerNorm values per lane (ceil(NP / 64))
 __global__ __launch_bounds__(64 * W, 1) void tat_fused_fwd_kernel(TatFusedArgs a) {
   static_assert(T % 4 == 0 && T <= 16 && kTfRows % T == 0, "whole problems per workgroup, one 16 x 16 tile");
   static_assert(W == 4 || W == 8, "four or eight waves");
@@ -454,18 +456,18 @@ __global__ __launch_bounds__(64 * W, 1) void tat_fused_fwd_kernel(TatFusedArgs a
       if (r >= nrows) continue;
       const int64_t R = R0 + r;
       const float rs = rsqrtf(s16[k] / N + a.eps);
-      if (l == 0) {
+      if (SAVE && l == 0) {
         a.mu[R] = mean[k];
         a.rs[R] = rs;
       }
       const uint32_t bb = (uint32_t)R / (uint32_t)a.FT, ft = (uint32_t)R - bb * (uint32_t)a.FT;
       float* orow = a.O + (int64_t)ft * a.BN + (int64_t)bb * N;
-      float* urow = a.u + R * N;
+      float* urow = SAVE ? a.u + R * N : nullptr;
 #pragma unroll
       for (int j = 0; j < NTW; ++j) {
         const int n = l + 64 * j;
         if (n < N) {
-          urow[n] = v[k][j];
+          if (SAVE) urow[n] = v[k][j];
           orow[n] = (v[k][j] - mean[k]) * rs * gv[j] + bv[j];
         }
       }
@@ -473,11 +475,13 @@ __global__ __launch_bounds__(64 * W, 1) void tat_fused_fwd_kernel(TatFusedArgs a
   }
   TF_MARK(5);
   // ---- 6. the saved tiles: Q|K|V, ctx, re_At, A (contiguous blocks for the workgroup) --------
-  tf_copy_out<NTH>(a.qkv + R0 * kTfQW, Qs, nrows, kTfQW, kTfLQ, tid);
-  tf_copy_out<NTH>(a.ctx + R0 * kTfHV, Cs, nrows, kTfHV, kTfLC, tid);
+  if (SAVE) {
+    tf_copy_out<NTH>(a.qkv + R0 * kTfQW, Qs, nrows, kTfQW, kTfLQ, tid);
+    tf_copy_out<NTH>(a.ctx + R0 * kTfHV, Cs, nrows, kTfHV, kTfLC, tid);
+  }
   const int np = nrows / T;
   tf_copy_out<NTH>(a.re_at + P0 * kTfH * T * T, RA, 1, np * kTfH * T * T, 0, tid);
-  tf_copy_out<NTH>(a.att + P0 * kTfH * T * T, AT, 1, np * kTfH * T * T, 0, tid);
+  if (SAVE) tf_copy_out<NTH>(a.att + P0 * kTfH * T * T, AT, 1, np * kTfH * T * T, 0, tid);
   TF_MARK(6);
   TF_PRINT("tat_fused_fwd", 7);
 }
@@ -1043,6 +1047,14 @@ int op_tat_fused_fwd(const TatFusedArgs& a0, hipStream_t st, ForkSig* sig) {
     set_last_error("tat_fused_fwd: unsupported shape");
     return DSTAGNN_E_SHAPE;
   }
+  // forward-only: every saved-for-backward output null (the SAVE = false kernels); a mix is an error
+  const int nsave = (a0.qkv != nullptr) + (a0.att != nullptr) + (a0.ctx != nullptr) + (a0.u != nullptr) +
+                    (a0.mu != nullptr) + (a0.rs != nullptr);
+  if ((nsave != 0 && nsave != 6) || !a0.re_at || !a0.O) {
+    set_last_error("tat_fused_fwd: saved outputs must be all set or all null (re_at and O always set)");
+    return DSTAGNN_E_ARG;
+  }
+  const bool save = nsave == 6;
   TatFusedArgs a = a0;  // carries the caller's fork signal (common.hpp)
   if (sig) { a.sig = sig->p; a.sig_v = sig->v; }
   const int64_t grid = cdiv64(a.BFT, kTfRows);
@@ -1056,13 +1068,14 @@ int op_tat_fused_fwd(const TatFusedArgs& a0, hipStream_t st, ForkSig* sig) {
   Kern k = nullptr;
   // DSTAGNN_TF_WAVES=4|8: the forward's workgroup size (A/B)
   static const int waves = env_int("DSTAGNN_TF_WAVES", 8) == 4 ? 4 : 8;
+#define TF_SV(TT, NN, WW) k = save ? tat_fused_fwd_kernel<TT, NN, WW, true> : tat_fused_fwd_kernel<TT, NN, WW, false>
 #define TF_NTW(TT, WW)                                        \
   switch (ntw) {                                              \
-    case 1: k = tat_fused_fwd_kernel<TT, 1, WW>; break;       \
-    case 2: k = tat_fused_fwd_kernel<TT, 2, WW>; break;       \
-    case 3: k = tat_fused_fwd_kernel<TT, 3, WW>; break;       \
-    case 4: k = tat_fused_fwd_kernel<TT, 4, WW>; break;       \
-    default: k = tat_fused_fwd_kernel<TT, 5, WW>; break;      \
+    case 1: TF_SV(TT, 1, WW); break;                          \
+    case 2: TF_SV(TT, 2, WW); break;                          \
+    case 3: TF_SV(TT, 3, WW); break;                          \
+    case 4: TF_SV(TT, 4, WW); break;                          \
+    default: TF_SV(TT, 5, WW); break;                         \
   }
 #define TF_T(TT)                                              \
   if (waves == 8) { TF_NTW(TT, 8) } else { TF_NTW(TT, 4) }   \
@@ -1074,6 +1087,7 @@ int op_tat_fused_fwd(const TatFusedArgs& a0, hipStream_t st, ForkSig* sig) {
   }
 #undef TF_T
 #undef TF_NTW
+#undef TF_SV
   if (lds > 64 * 1024) {  // once per instantiation: dynamic LDS above 64 KB needs the opt-in
     static std::mutex mu;
     static std::set<Kern> done;

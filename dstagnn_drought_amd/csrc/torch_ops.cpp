@@ -6,7 +6,11 @@
 //   dstagnn::block          DSTAGNN_block.forward (:225-253) + its autograd backward, as ONE
 //                           C++ autograd node (torch::autograd::Function): forward = one
 //                           dstagnn_block_forward call, backward = one dstagnn_block_backward
+//                           — and, where no autograd node would be recorded (grad mode off,
+//                           or nothing differentiable requires grad), one
+//                           dstagnn_block_forward_only call: no backward state written or kept
 //   dstagnn::block_fwd/bwd  the same two calls as plain ops (tests, tools)
+//   dstagnn::block_fwd_only / block_fwd_only_bytes  the forward-only call and its workspace size
 //   dstagnn::cheb_sat_fwd/bwd  cheb_conv_withSAt.forward (:117-133) and its gradient
 //   dstagnn::head_fwd/bwd   DSTAGNN_submodule's cat + final_conv + final_fc (:272-280)
 //   dstagnn::gemm_f32       the strided f32-MFMA GEMM (tests / tools)
@@ -71,9 +75,11 @@ static_assert(sizeof(dstagnn_block_grads) == kSlots * sizeof(void*), "grads stru
 bool unused_inner(int64_t slot) { return slot == 2 || slot == 3 || slot == 4 || slot == 38 || slot == 39; }
 
 // cfg = [n_heads, d_k, d_v, d_model, K, C]; flags: 1 train, 2 sparse, 4 direct grads, 8 poison,
-// 16 fused (flash) Chebyshev attention; bits 32.. carry the call's first global sample index
-// (dstagnn_block_dims::sample_base: a data-parallel shard's offset, keys the dropout masks)
-enum { kTrain = 1, kSparse = 2, kDirect = 4, kPoison = 8, kFlash = 16 };
+// 16 fused (flash) Chebyshev attention, 32 full forward (save / scratch written) even where no
+// autograd node is recorded (DSTAGNN_block.forward_only = False; A/B tools); bits 32.. carry the
+// call's first global sample index (dstagnn_block_dims::sample_base: a data-parallel shard's
+// offset, keys the dropout masks)
+enum { kTrain = 1, kSparse = 2, kDirect = 4, kPoison = 8, kFlash = 16, kFullFwd = 32 };
 constexpr int kSampleShift = 32;
 
 int res_mode_of(const c10::optional<Tensor>& res, int64_t F) {
@@ -163,6 +169,32 @@ std::tuple<Tensor, Tensor, Tensor> run_forward(const BlockCall& c, const Tensor&
                                  re_at.data_ptr<float>(), save.data_ptr(), sv, scratch.data_ptr(), sc, stream_of(x)),
            "dstagnn_block_forward");
   return {out, re_at, save};
+}
+
+size_t forward_only_bytes(const BlockCall& c) {
+  size_t wb = 0;
+  check_rc(dstagnn_block_forward_only_size(&c.d, &wb), "dstagnn_block_forward_only_size");
+  return wb;
+}
+
+// forward-only: (out, re_at); ONE workspace, released on return (stream-ordered by the allocator)
+std::tuple<Tensor, Tensor> run_forward_only(const BlockCall& c, const Tensor& x, const c10::optional<Tensor>& res) {
+  c10::DeviceGuard guard(x.device());
+  const size_t wb = forward_only_bytes(c);
+  const auto& d = c.d;
+  Tensor work = bytes(wb, x);
+  Tensor out = at::empty({d.B, d.N, d.C, d.T}, f32(x));
+  Tensor re_at = at::empty({d.B, d.F, d.n_heads, d.T, d.T}, f32(x));
+  if (c.flags & kPoison) {  // every library-written buffer starts as NaN (all-ones bytes)
+    work.fill_(255);
+    out.fill_(NAN);
+    re_at.fill_(NAN);
+  }
+  const float* ra = c.mode != DSTAGNN_RES_NONE ? res->data_ptr<float>() : nullptr;
+  check_rc(dstagnn_block_forward_only(&c.d, &c.p, &c.g, x.data_ptr<float>(), ra, out.data_ptr<float>(),
+                                      re_at.data_ptr<float>(), work.data_ptr(), wb, stream_of(x)),
+           "dstagnn_block_forward_only");
+  return {out, re_at};
 }
 
 // backward: d_x, d_res (undefined for mode 0), the flat gradient buffer, per-parameter
@@ -359,11 +391,22 @@ class BlockPlanFunction : public torch::autograd::Function<BlockPlanFunction> {
   }
 };
 
-std::tuple<Tensor, Tensor> block_planned_autograd(const Tensor& x, const c10::optional<Tensor>& res,
-                                                  const c10::intrusive_ptr<BlockPlan>& plan, const Tensor& anchor,
-                                                  double drop_p, int64_t seed, int64_t flags) {
-  auto o = BlockPlanFunction::apply(x, res, plan, anchor, drop_p, seed, flags);
-  return {o[0], o[1]};
+// (out, re_at) with no autograd node: the forward-only call; kFullFwd keeps the full forward
+std::tuple<Tensor, Tensor> run_no_grad(const BlockCall& c, const Tensor& x, const c10::optional<Tensor>& res) {
+  if (c.flags & kFullFwd) {
+    auto [out, re_at, save] = run_forward(c, x, res);
+    return {out, re_at};
+  }
+  return run_forward_only(c, x, res);
+}
+
+// would apply() record a node?  Grad mode on and a differentiable input that requires grad
+bool records_node(const Tensor& x, const c10::optional<Tensor>& res, at::TensorList diff) {
+  if (!at::GradMode::is_enabled()) return false;
+  if (x.requires_grad() || (res.has_value() && res->defined() && res->requires_grad())) return true;
+  for (const Tensor& t : diff)
+    if (t.defined() && t.requires_grad()) return true;
+  return false;
 }
 
 std::tuple<Tensor, Tensor> block_planned_infer(const Tensor& x, const c10::optional<Tensor>& res,
@@ -371,14 +414,15 @@ std::tuple<Tensor, Tensor> block_planned_infer(const Tensor& x, const c10::optio
                                                double drop_p, int64_t seed, int64_t flags) {
   (void)anchor;
   BlockCall c = make_call(x, res, plan->params, plan->slots, plan->graph, plan->cfg, drop_p, seed, flags);
-  auto [out, re_at, save] = run_forward(c, x, res);
-  return {out, re_at};
+  return run_no_grad(c, x, res);
 }
 
-std::tuple<Tensor, Tensor> block_autograd(const Tensor& x, const c10::optional<Tensor>& res, at::TensorList params,
-                                          at::IntArrayRef slots, at::TensorList graph, at::IntArrayRef cfg,
-                                          double drop_p, int64_t seed, int64_t flags) {
-  auto o = BlockFunction::apply(x, res, params, slots, graph, cfg, drop_p, seed, flags);
+std::tuple<Tensor, Tensor> block_planned_autograd(const Tensor& x, const c10::optional<Tensor>& res,
+                                                  const c10::intrusive_ptr<BlockPlan>& plan, const Tensor& anchor,
+                                                  double drop_p, int64_t seed, int64_t flags) {
+  // (the plan's parameters are no autograd inputs: the anchor stands for them)
+  if (!records_node(x, res, {anchor})) return block_planned_infer(x, res, plan, anchor, drop_p, seed, flags);
+  auto o = BlockPlanFunction::apply(x, res, plan, anchor, drop_p, seed, flags);
   return {o[0], o[1]};
 }
 
@@ -387,8 +431,29 @@ std::tuple<Tensor, Tensor> block_infer(const Tensor& x, const c10::optional<Tens
                                        at::IntArrayRef slots, at::TensorList graph, at::IntArrayRef cfg, double drop_p,
                                        int64_t seed, int64_t flags) {
   BlockCall c = make_call(x, res, params, slots, graph, cfg, drop_p, seed, flags);
-  auto [out, re_at, save] = run_forward(c, x, res);
-  return {out, re_at};
+  return run_no_grad(c, x, res);
+}
+
+std::tuple<Tensor, Tensor> block_autograd(const Tensor& x, const c10::optional<Tensor>& res, at::TensorList params,
+                                          at::IntArrayRef slots, at::TensorList graph, at::IntArrayRef cfg,
+                                          double drop_p, int64_t seed, int64_t flags) {
+  if (!records_node(x, res, params)) return block_infer(x, res, params, slots, graph, cfg, drop_p, seed, flags);
+  auto o = BlockFunction::apply(x, res, params, slots, graph, cfg, drop_p, seed, flags);
+  return {o[0], o[1]};
+}
+
+// the forward-only call as a plain op (tests, tools), whatever the grad mode, and its workspace size
+std::tuple<Tensor, Tensor> block_fwd_only(const Tensor& x, const c10::optional<Tensor>& res, at::TensorList params,
+                                          at::IntArrayRef slots, at::TensorList graph, at::IntArrayRef cfg,
+                                          double drop_p, int64_t seed, int64_t flags) {
+  BlockCall c = make_call(x, res, params, slots, graph, cfg, drop_p, seed, flags);
+  return run_forward_only(c, x, res);
+}
+int64_t block_fwd_only_bytes(const Tensor& x, const c10::optional<Tensor>& res, at::TensorList params,
+                             at::IntArrayRef slots, at::TensorList graph, at::IntArrayRef cfg, double drop_p,
+                             int64_t seed, int64_t flags) {
+  BlockCall c = make_call(x, res, params, slots, graph, cfg, drop_p, seed, flags);
+  return (int64_t)forward_only_bytes(c);
 }
 
 std::tuple<Tensor, Tensor, Tensor> block_fwd(const Tensor& x, const c10::optional<Tensor>& res,
@@ -870,6 +935,8 @@ TORCH_LIBRARY(dstagnn, m) {
   "Tensor x, Tensor? res_att, Tensor[] params, int[] slots, Tensor[] graph, int[] cfg, float drop_p, int seed, int flags"
   m.def("block(" DSTAGNN_BLK_ARGS ") -> (Tensor, Tensor)");
   m.def("block_fwd(" DSTAGNN_BLK_ARGS ") -> (Tensor, Tensor, Tensor)");
+  m.def("block_fwd_only(" DSTAGNN_BLK_ARGS ") -> (Tensor, Tensor)");
+  m.def("block_fwd_only_bytes(" DSTAGNN_BLK_ARGS ") -> int");
   m.def("block_bwd(Tensor x, Tensor? res_att, Tensor d_out, Tensor? d_re_at, Tensor save, Tensor[] params, "
         "int[] slots, Tensor[] graph, int[] cfg, float drop_p, int seed, int flags) -> (Tensor, Tensor, Tensor)");
   m.def("block_time_stage(" DSTAGNN_BLK_ARGS ", int stage, int iters) -> float");
@@ -908,6 +975,8 @@ TORCH_LIBRARY_IMPL(dstagnn, CUDA, m) {
   m.impl("block", block_infer);
   m.impl("block_planned", block_planned_infer);
   m.impl("block_fwd", block_fwd);
+  m.impl("block_fwd_only", block_fwd_only);
+  m.impl("block_fwd_only_bytes", block_fwd_only_bytes);
   m.impl("block_bwd", block_bwd);
   m.impl("block_time_stage", block_time_stage);
   m.impl("dropout_masks", dropout_masks);

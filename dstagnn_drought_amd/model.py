@@ -210,6 +210,11 @@ def _default_sample_base(B):
 class DSTAGNN_block(nn.Module):
     """One spatial-temporal block (model/DSTAGNN_my.py:199-253), forward/backward on the HIP path."""
 
+    # a call that records no autograd node (torch.no_grad(), torch.inference_mode(), nothing
+    # requiring grad) takes the forward-only library call: no backward state written or
+    # allocated, same output bits.  False keeps the full forward there (tools/bench_infer.py A/B)
+    forward_only = True
+
     def __init__(self, DEVICE, num_of_d, in_channels, K, nb_chev_filter, nb_time_filter, time_strides,
                  cheb_polynomials, adj_pa, adj_TMD, num_of_vertices, num_of_timesteps, d_model, d_k, d_v, n_heads):
         super().__init__()
@@ -272,7 +277,7 @@ class DSTAGNN_block(nn.Module):
             graph = self._flash_graph(graph)
         out, re_at = block_call(x, res_att, params, slots, graph, meta, meta["train"], meta["seed"],
                                 self.direct_grads, flash=self.flash_cheb, plan_cache=self.__dict__.setdefault("_pcache", {}),
-                                sample_base=base)
+                                sample_base=base, forward_only=self.forward_only)
         if self.grads_ready is not None and out.requires_grad:
             # DP overlap (dp.GradAllReducer.attach): once this block's backward node has run,
             # its parameter gradients are final — hand them over from a post-hook on the node

@@ -160,6 +160,20 @@ int dstagnn_block_forward(const dstagnn_block_dims* d, const dstagnn_block_param
                           void* save, size_t save_bytes, void* scratch, size_t scratch_bytes,
                           dstagnn_stream_t stream);
 
+/* Forward-only form of the block (validation, test, prediction): the same `out` and `re_at`
+ * bits as dstagnn_block_forward for the same arguments, but no tensor that only the backward
+ * reads is written or allocated.  One workspace holds what a later forward kernel reads plus
+ * the GEMM workspaces; its size comes from dstagnn_block_forward_only_size().  Conventions as
+ * above: asynchronous on `stream`, no allocation, DSTAGNN_E_SPACE when `work` is too small, the
+ * dims / graph errors (and texts) of dstagnn_block_forward.  d->train = 1 is legal: the dropout
+ * masks are those of the training forward for the same seed and sample_base.  The forward bits
+ * of dstagnn_block_paths() describe this call as well.  `work` holds nothing of use afterwards
+ * and no backward can follow.                                                             */
+int dstagnn_block_forward_only_size(const dstagnn_block_dims* d, size_t* work_bytes);
+int dstagnn_block_forward_only(const dstagnn_block_dims* d, const dstagnn_block_params* p, const dstagnn_graph* g,
+                               const float* x, const float* res_att, float* out, float* re_at,
+                               void* work, size_t work_bytes, dstagnn_stream_t stream);
+
 /* Introspection for parity tests: byte offset (from the 256-aligned start of `save`) and
  * element count of a tensor the forward keeps in `save`; the sign pattern of each is one of
  * the block's ReLU decisions, which an fp64 oracle can adopt where the pre-activation is
