@@ -15,4 +15,14 @@ __all__ = ["make_model", "DSTAGNN_block", "DSTAGNN_submodule", "cheb_conv_withSA
            "MultiHeadAttention", "SMultiHeadAttention", "ScaledDotProductAttention", "SScaledDotProductAttention",
            "scaled_Laplacian", "cheb_polynomial", "load_weighted_adjacency_matrix", "load_weighted_adjacency_matrix2",
            "load_PA", "get_adjacency_matrix2", "load_graphdata_channel1", "read_and_generate_dataset",
-           "masked_mape_np", "re_normalization", "set_dropout", "set_direct_grads", "set_sample_base"]
+           "masked_mape_np", "re_normalization", "set_dropout", "set_direct_grads", "set_sample_base",
+           "HipAdam", "clip_grad_norm_"]
+
+
+def __getattr__(name):
+    # the optimiser surface lives in train.py, loaded on first use (`python -m
+    # dstagnn_drought_amd.train` then still runs train.py once, as __main__)
+    if name in ("HipAdam", "clip_grad_norm_"):
+        from . import train
+        return getattr(train, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

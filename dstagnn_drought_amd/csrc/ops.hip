@@ -1121,20 +1121,6 @@ struct Colsum2dArgs {
   int* cnt = nullptr;      // [nsrc*G][R2] level-1 tickets, then [nsrc*G] level-2 tickets
 };
 
-__device__ __forceinline__ float ld_agent(const float* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_agent(float* p, float v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// consumer side of the hand-off: agent acquire, then wait for the invalidate to complete
-// (the caller's workgroup barrier holds the other waves behind it)
-__device__ __forceinline__ void colsum_acquire() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
 // sum of n <= 32 partial rows p[q*256 + t] in fixed order; all loads issued before the
 // first add (one memory round trip: the sc1 loads are served beyond the XCD's L2)
 __device__ __forceinline__ float sum_partials(const float* p, int n, int t) {

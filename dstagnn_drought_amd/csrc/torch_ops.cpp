@@ -766,38 +766,60 @@ std::vector<Tensor> head_bwd(at::TensorList outs, const Tensor& w1, const Tensor
 // go through a pinned host buffer and an asynchronous copy on the current stream (the
 // caching host allocator keeps the buffer alive until the copy has run)
 // -------------------------------------------------------------------------------------
-void adam_step(at::TensorList params, at::TensorList grads, at::TensorList exp_avgs, at::TensorList exp_avg_sqs,
-               double beta1, double beta2, double eps, double step_size, double bc2_sqrt) {
-  const size_t n = params.size();
-  TORCH_CHECK(grads.size() == n && exp_avgs.size() == n && exp_avg_sqs.size() == n, "adam_step: list lengths differ");
-  if (n == 0) return;
-  c10::DeviceGuard guard(params[0].device());
-  const int64_t ce = dstagnn_adam_chunk_elems();
-  std::vector<dstagnn_adam_seg> segs(n);
-  std::vector<Tensor> gcopy;  // contiguous copies of strided gradients, alive until the launch is queued
-  gcopy.reserve(n);
+struct AdamTables {
+  Tensor dev;                // device bytes: the segments, then the (segment, offset) pairs
+  size_t sb = 0;
   int64_t nchunk = 0;
+  std::vector<Tensor> gcopy;  // contiguous copies of strided gradients, alive until the launch is queued
+  std::vector<std::pair<Tensor, Tensor>> back;  // (gradient, its scaled copy) to copy back (grad_scale)
+  const dstagnn_adam_seg* segs() const { return reinterpret_cast<const dstagnn_adam_seg*>(dev.data_ptr<uint8_t>()); }
+  const int64_t* chunks() const { return reinterpret_cast<const int64_t*>(dev.data_ptr<uint8_t>() + sb); }
+};
+
+// state == nullptr: gradients only (grad_sumsq, grad_scale; p / m / v stay null).  inplace: the
+// kernel writes the gradients, so a strided one that covers its storage densely (a transpose)
+// is scaled where it lies, and any other through a copy that the caller copies back.
+AdamTables adam_tables(const char* who, at::TensorList grads, const at::TensorList* state, bool inplace = false) {
+  const size_t n = grads.size();
+  const at::Device dev0 = state ? state[0][0].device() : grads[0].device();
+  const int64_t ce = dstagnn_adam_chunk_elems();
+  AdamTables t;
+  std::vector<dstagnn_adam_seg> segs(n);
+  t.gcopy.reserve(n);
   for (size_t i = 0; i < n; ++i) {
     const Tensor* g = &grads[i];
-    if (g->defined() && g->is_cuda() && !g->is_contiguous()) {
-      gcopy.push_back(g->contiguous());
-      g = &gcopy.back();
+    const bool dense = inplace && g->defined() && g->is_non_overlapping_and_dense();
+    if (g->defined() && g->is_cuda() && !g->is_contiguous() && !dense) {
+      t.gcopy.push_back(g->contiguous());
+      if (inplace) t.back.emplace_back(*g, t.gcopy.back());
+      g = &t.gcopy.back();
     }
-    for (const Tensor* t : {&params[i], g, &exp_avgs[i], &exp_avg_sqs[i]}) {
-      check_dev(*t, at::kFloat, "adam_step tensor");
-      TORCH_CHECK(t->device() == params[0].device(), "adam_step: tensors on different devices");
-      TORCH_CHECK(t->numel() == params[i].numel(), "adam_step: param / grad / state sizes differ");
-    }
-    segs[i] = {params[i].data_ptr<float>(), g->data_ptr<float>(), exp_avgs[i].data_ptr<float>(),
-               exp_avg_sqs[i].data_ptr<float>(), params[i].numel()};
-    nchunk += (params[i].numel() + ce - 1) / ce;
+    TORCH_CHECK(g->defined(), who, " tensor: undefined tensor");
+    TORCH_CHECK(g->is_cuda(), who, " tensor: must be a HIP device tensor (there is no CPU path)");
+    TORCH_CHECK(g->scalar_type() == at::kFloat, who, " tensor: expected Float, got ", g->scalar_type());
+    TORCH_CHECK(g->device() == dev0, who, ": tensors on different devices");
+    const int64_t numel = state ? state[0][i].numel() : g->numel();
+    if (state)
+      for (int k = 0; k < 3; ++k) {
+        const Tensor& x = state[k][i];
+        check_dev(x, at::kFloat, "adam_step tensor");
+        TORCH_CHECK(x.device() == dev0, who, ": tensors on different devices");
+        TORCH_CHECK(x.numel() == numel, who, ": param / grad / state sizes differ");
+      }
+    if (!dense) check_dev(*g, at::kFloat, "adam_step tensor");
+    TORCH_CHECK(g->numel() == numel, who, ": param / grad / state sizes differ");
+    segs[i] = {state ? state[0][i].data_ptr<float>() : nullptr, g->data_ptr<float>(),
+               state ? state[1][i].data_ptr<float>() : nullptr, state ? state[2][i].data_ptr<float>() : nullptr,
+               numel};
+    t.nchunk += (numel + ce - 1) / ce;
   }
-  TORCH_CHECK(nchunk < (1ll << 31), "adam_step: too many chunks");
-  const size_t sb = n * sizeof(dstagnn_adam_seg), cb = (size_t)nchunk * 2 * sizeof(int64_t);
-  Tensor host = at::empty({(int64_t)(sb + cb)}, at::TensorOptions().dtype(at::kByte).pinned_memory(true));
+  TORCH_CHECK(t.nchunk < (1ll << 31), who, ": too many chunks");
+  t.sb = n * sizeof(dstagnn_adam_seg);
+  const size_t cb = (size_t)t.nchunk * 2 * sizeof(int64_t);
+  Tensor host = at::empty({(int64_t)(t.sb + cb)}, at::TensorOptions().dtype(at::kByte).pinned_memory(true));
   uint8_t* hp = host.data_ptr<uint8_t>();
-  std::memcpy(hp, segs.data(), sb);
-  int64_t* ch = reinterpret_cast<int64_t*>(hp + sb);
+  std::memcpy(hp, segs.data(), t.sb);
+  int64_t* ch = reinterpret_cast<int64_t*>(hp + t.sb);
   int64_t k = 0;
   for (size_t i = 0; i < n; ++i)
     for (int64_t off = 0; off < segs[i].n; off += ce) {
@@ -805,12 +827,80 @@ void adam_step(at::TensorList params, at::TensorList grads, at::TensorList exp_a
       ch[2 * k + 1] = off;
       ++k;
     }
-  Tensor dev = host.to(params[0].device(), /*non_blocking=*/true);
-  const uint8_t* dp = dev.data_ptr<uint8_t>();
-  check_rc(dstagnn_adam_step(reinterpret_cast<const dstagnn_adam_seg*>(dp), reinterpret_cast<const int64_t*>(dp + sb),
-                             (int)nchunk, (float)beta1, (float)beta2, (float)eps, (float)step_size, (float)bc2_sqrt,
-                             stream_of(params[0])),
+  t.dev = host.to(dev0, /*non_blocking=*/true);
+  return t;
+}
+
+void adam_step(at::TensorList params, at::TensorList grads, at::TensorList exp_avgs, at::TensorList exp_avg_sqs,
+               double beta1, double beta2, double eps, double step_size, double bc2_sqrt) {
+  const size_t n = params.size();
+  TORCH_CHECK(grads.size() == n && exp_avgs.size() == n && exp_avg_sqs.size() == n, "adam_step: list lengths differ");
+  if (n == 0) return;
+  c10::DeviceGuard guard(params[0].device());
+  const at::TensorList state[3] = {params, exp_avgs, exp_avg_sqs};
+  const AdamTables t = adam_tables("adam_step", grads, state);
+  check_rc(dstagnn_adam_step(t.segs(), t.chunks(), (int)t.nchunk, (float)beta1, (float)beta2, (float)eps,
+                             (float)step_size, (float)bc2_sqrt, stream_of(params[0])),
            "dstagnn_adam_step");
+}
+
+// sum of squares of every listed gradient: a 0-dim fp64 tensor, element 0 of a two-double
+// buffer whose element 1 holds the root (the global L2 norm); no host sync
+Tensor grad_sumsq(at::TensorList grads) {
+  TORCH_CHECK(grads.size() > 0, "grad_sumsq: empty gradient list");
+  c10::DeviceGuard guard(grads[0].device());
+  const AdamTables t = adam_tables("grad_sumsq", grads, nullptr);
+  Tensor stat = at::empty({2}, grads[0].options().dtype(at::kDouble));
+  Tensor part = at::empty({std::max<int64_t>(t.nchunk, 1)}, f32(grads[0]));
+  check_rc(dstagnn_grad_sumsq(t.segs(), t.chunks(), (int)t.nchunk, part.data_ptr<float>(), stat.data_ptr<double>(),
+                              stream_of(grads[0])),
+           "dstagnn_grad_sumsq");
+  return stat.select(0, 0);
+}
+
+const double* stat_ptr(const Tensor& stat, const Tensor& like, const char* who) {
+  if (!stat.defined() || stat.numel() == 0) return nullptr;
+  check_dev(stat, at::kDouble, "stat");
+  TORCH_CHECK(stat.device() == like.device(), who, ": stat on another device");
+  return stat.data_ptr<double>();
+}
+
+// stat: grad_sumsq's result (an empty tensor when neither clipping nor the non-finite skip is
+// on); skipped: one int32 on the device, or empty for a launch that must not count (the later
+// launches of one optimiser step)
+void adam_step_ex(at::TensorList params, at::TensorList grads, at::TensorList exp_avgs, at::TensorList exp_avg_sqs,
+                  double beta1, double beta2, double eps, double step_size, double bc2_sqrt, double lr,
+                  double weight_decay, bool decoupled, double max_norm, bool skip_nonfinite, const Tensor& stat,
+                  Tensor skipped) {
+  const size_t n = params.size();
+  TORCH_CHECK(grads.size() == n && exp_avgs.size() == n && exp_avg_sqs.size() == n,
+              "adam_step_ex: list lengths differ");
+  if (n == 0) return;
+  c10::DeviceGuard guard(params[0].device());
+  const at::TensorList state[3] = {params, exp_avgs, exp_avg_sqs};
+  const AdamTables t = adam_tables("adam_step_ex", grads, state);
+  int* sk = nullptr;
+  if (skipped.defined() && skipped.numel() > 0) {
+    check_dev(skipped, at::kInt, "skipped");
+    TORCH_CHECK(skipped.device() == params[0].device(), "adam_step_ex: skipped on another device");
+    sk = skipped.data_ptr<int>();
+  }
+  const dstagnn_adam_hyper h = {(float)beta1, (float)beta2, (float)eps, (float)step_size, (float)bc2_sqrt,
+                                (float)lr, (float)weight_decay, decoupled ? 1 : 0, (float)max_norm,
+                                skip_nonfinite ? 1 : 0};
+  check_rc(dstagnn_adam_step_ex(t.segs(), t.chunks(), (int)t.nchunk, &h, stat_ptr(stat, params[0], "adam_step_ex"), sk,
+                                stream_of(params[0])),
+           "dstagnn_adam_step_ex");
+}
+
+void grad_scale(at::TensorList grads, const Tensor& stat, double max_norm) {
+  if (grads.size() == 0) return;
+  c10::DeviceGuard guard(grads[0].device());
+  const AdamTables t = adam_tables("grad_scale", grads, nullptr, /*inplace=*/true);
+  check_rc(dstagnn_grad_scale(t.segs(), t.chunks(), (int)t.nchunk, stat_ptr(stat, grads[0], "grad_scale"),
+                              (float)max_norm, stream_of(grads[0])),
+           "dstagnn_grad_scale");
+  for (const auto& b : t.back) b.first.copy_(b.second);
 }
 
 // -------------------------------------------------------------------------------------
@@ -956,6 +1046,11 @@ TORCH_LIBRARY(dstagnn, m) {
   m.def("head_bwd(Tensor[] outs, Tensor w1, Tensor w2, Tensor h, Tensor dy, int[] need) -> Tensor[]");
   m.def("adam_step(Tensor(a!)[] params, Tensor[] grads, Tensor(b!)[] exp_avgs, Tensor(c!)[] exp_avg_sqs, "
         "float beta1, float beta2, float eps, float step_size, float bc2_sqrt) -> ()");
+  m.def("grad_sumsq(Tensor[] grads) -> Tensor");
+  m.def("adam_step_ex(Tensor(a!)[] params, Tensor[] grads, Tensor(b!)[] exp_avgs, Tensor(c!)[] exp_avg_sqs, "
+        "float beta1, float beta2, float eps, float step_size, float bc2_sqrt, float lr, float weight_decay, "
+        "bool decoupled, float max_norm, bool skip_nonfinite, Tensor stat, Tensor(d!) skipped) -> ()");
+  m.def("grad_scale(Tensor(a!)[] grads, Tensor stat, float max_norm) -> ()");
   m.def("stag_prep(Tensor data) -> (Tensor, Tensor, Tensor)");
   m.def("stag_emd_pairs(Tensor xhat, Tensor p, Tensor psum, Tensor pairs, bool with_pivots) -> (Tensor, Tensor, Tensor)");
   m.def("stag_emd_lds_bytes(int T, int F) -> int", stag_emd_lds_bytes);
@@ -990,6 +1085,9 @@ TORCH_LIBRARY_IMPL(dstagnn, CUDA, m) {
   m.impl("head_fwd", head_fwd);
   m.impl("head_bwd", head_bwd);
   m.impl("adam_step", adam_step);
+  m.impl("grad_sumsq", grad_sumsq);
+  m.impl("adam_step_ex", adam_step_ex);
+  m.impl("grad_scale", grad_scale);
   m.impl("stag_prep", stag_prep);
   m.impl("stag_emd_pairs", stag_emd_pairs);
   m.impl("emd_dense", emd_dense);

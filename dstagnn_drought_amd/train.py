@@ -188,23 +188,76 @@ class HipAdam(torch.optim.Optimizer):
     (``dstagnn::adam_step``, csrc/optim.hip) over every parameter that has a gradient — torch's
     fused Adam takes four ~43 us launches after ~0.2 ms of host-side grouping at PEMS08
     nb_block=4.  fp32 CUDA parameters only; state per parameter as torch's Adam
-    (``step``, ``exp_avg``, ``exp_avg_sq``)."""
+    (``step``, ``exp_avg``, ``exp_avg_sq``).
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
-        # per group, after a step whose gradient-carrying parameters all shared one step count:
-        # (params list, which params had a gradient, those params, their state dicts,
-        # exp_avgs, exp_avg_sqs, step).  The per-parameter grouping below costs ~2 us per
-        # Parameter in Python (~0.3 ms at nb_block=4, with the GPU idle); the cached path
-        # gathers the gradients and launches while the same parameters carry gradients.
+    Opt-in, on the data the launch already streams (``dstagnn::adam_step_ex``; with none of them
+    given the step is the single ``adam_step`` launch above, bit for bit):
+
+    * ``max_grad_norm``: clipping by the global L2 norm, torch.nn.utils.clip_grad_norm_'s
+      ``coef = min(1, max_norm / (norm + 1e-6))``.  The norm is taken ONCE per ``step()`` over
+      every parameter with a gradient in ALL param groups (one ``dstagnn::grad_sumsq`` launch,
+      fp64 fold) before any update launch, also where differing step counts split a group into
+      several launches.  The gradients themselves are not written: the kernel uses ``coef * g``.
+    * ``weight_decay`` with ``decoupled_weight_decay=False``: ``g += wd * p`` after clipping
+      (torch.optim.Adam(weight_decay=)); ``True``: ``p *= 1 - lr * wd`` before the update
+      (torch.optim.AdamW).
+    * ``skip_nonfinite``: when the squared norm is inf / nan the update launches store nothing
+      (``p``, ``exp_avg``, ``exp_avg_sq`` keep their values) and ``skipped_steps`` (a device
+      int32) goes up by one.  The host never learns of it (no sync), so the per-parameter
+      ``step`` counts still advance: the bias corrections of the next step are those of t + 1.
+
+    ``grad_norm``: a 0-dim fp64 device tensor, the pre-clip global norm of the last step that
+    needed it (clipping or skipping on; None before).  The new hyper-parameters live in
+    ``param_groups`` (the norm is global, each group clips to its own ``max_grad_norm``) and
+    travel through ``state_dict`` / ``load_state_dict``."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 decoupled_weight_decay=False, max_grad_norm=None, skip_nonfinite=False):
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                        decoupled_weight_decay=decoupled_weight_decay, max_grad_norm=max_grad_norm,
+                        skip_nonfinite=skip_nonfinite)
+        self._check_options(defaults)
+        super().__init__(params, defaults)
+        # per group, after a step through the grouping below: (params list, which params had a
+        # gradient, and per step count — one launch each — [positions in the params list, those
+        # params, their state dicts, exp_avgs, exp_avg_sqs, step]).  The per-parameter grouping
+        # costs ~2 us per Parameter in Python (~0.3 ms at nb_block=4, with the GPU idle); the
+        # cached path gathers the gradients and launches while the same parameters carry gradients.
         self._plans = {}
+        self._sumsq = None
+        self._count = True
+        first = self.param_groups[0]["params"][0]
+        self.skipped_steps = torch.zeros((), dtype=torch.int32, device=first.device)
+        self._none = {}  # per device: (empty fp64 stat, empty int32 counter) for "not given"
+
+    @staticmethod
+    def _check_options(group):
+        wd, mn = group["weight_decay"], group["max_grad_norm"]
+        if not (isinstance(wd, (int, float)) and wd >= 0.0):  # (a NaN fails too)
+            raise ValueError(f"HipAdam: invalid weight_decay {wd!r}")
+        if mn is not None and not (isinstance(mn, (int, float)) and mn > 0.0):
+            raise ValueError(f"HipAdam: invalid max_grad_norm {mn!r} (None: no clipping)")
+
+    @property
+    def grad_norm(self):
+        """Element 1 of grad_sumsq's two-double buffer (the kernel stores the root beside the
+        sum): a view, no launch."""
+        return None if self._sumsq is None else _norm_of(self._sumsq)
 
     def load_state_dict(self, state_dict):
-        """Accepts HipAdam's and torch.optim.Adam's state_dicts alike: torch keeps ``step`` as a
-        (float) tensor, HipAdam as a Python int (a tensor step would key ``by_step`` below by
-        identity: one launch per parameter and no cached plan), so it is converted here."""
+        """Accepts HipAdam's and torch.optim.Adam's / AdamW's state_dicts alike: torch keeps
+        ``step`` as a (float) tensor, HipAdam as a Python int (a tensor step would key ``by_step``
+        below by identity: one launch per parameter and no cached plan), so it is converted here.
+        torch's groups carry ``weight_decay`` (and, newer ones, ``decoupled_weight_decay``), which
+        are taken over; the options they lack keep this optimiser's defaults."""
         self._plans = {}
         super().load_state_dict(state_dict)
+        for group in self.param_groups:
+            if group.get("amsgrad") or group.get("maximize"):
+                raise ValueError("HipAdam: amsgrad / maximize are not supported")
+            for k, v in self.defaults.items():
+                group.setdefault(k, v)
+            self._check_options(group)
         for st in self.state.values():
             if "step" in st and torch.is_tensor(st["step"]):
                 st["step"] = int(st["step"].item())
@@ -228,23 +281,50 @@ class HipAdam(torch.optim.Optimizer):
             for p in group["params"]:
                 p.grad = None
 
-    def _fast_step(self, ops, group):
+    @staticmethod
+    def _plain(group):
+        return (group["weight_decay"] == 0.0 and group["max_grad_norm"] is None and not group["skip_nonfinite"])
+
+    def _launch(self, ops, group, ps, gs, ms, vs, t, stat):
+        """One update launch at step count t: today's ``adam_step`` when the group has no option
+        on, else ``adam_step_ex``.  Of the launches of one step() the first with skip_nonfinite
+        set is handed the ``skipped_steps`` counter, so a skipped step counts once."""
+        b1, b2 = group["betas"]
+        step_size, bc2_sqrt = group["lr"] / (1.0 - b1 ** t), math.sqrt(1.0 - b2 ** t)
+        if self._plain(group):
+            ops.adam_step(ps, gs, ms, vs, b1, b2, group["eps"], step_size, bc2_sqrt)
+            return
+        dev = ps[0].device
+        none = self._none.get(dev)
+        if none is None:
+            none = self._none[dev] = (torch.empty(0, dtype=torch.float64, device=dev),
+                                      torch.empty(0, dtype=torch.int32, device=dev))
+        mn, skip = group["max_grad_norm"], bool(group["skip_nonfinite"])
+        count = skip and self._count
+        if count:
+            self._count = False
+            if self.skipped_steps.device != dev:
+                self.skipped_steps = self.skipped_steps.to(dev)
+        ops.adam_step_ex(ps, gs, ms, vs, b1, b2, group["eps"], step_size, bc2_sqrt, group["lr"],
+                         float(group["weight_decay"]), bool(group["decoupled_weight_decay"]),
+                         0.0 if mn is None else float(mn), skip,
+                         stat if (mn is not None or skip) else none[0],
+                         self.skipped_steps if count else none[1])
+
+    def _fast_step(self, ops, group, grads, stat):
         plan = self._plans.get(id(group))
         params = group["params"]
         if plan is None or plan[0] is not params or len(plan[1]) != len(params):
             return False
-        grads = [p.grad for p in params]
         if [g is not None for g in grads] != plan[1]:
             return False
-        _, present, ps, states, ms, vs, t = plan
-        gs = [g for g in grads if g is not None]
-        t += 1
-        b1, b2 = group["betas"]
-        ops.adam_step(ps, gs, ms, vs, b1, b2, group["eps"], group["lr"] / (1.0 - b1 ** t),
-                      math.sqrt(1.0 - b2 ** t))
-        for st in states:
-            st["step"] = t
-        self._plans[id(group)] = plan[:6] + (t,)
+        for launch in plan[2]:
+            idx, ps, states, ms, vs, t = launch
+            t += 1
+            self._launch(ops, group, ps, [grads[i] for i in idx], ms, vs, t, stat)
+            for st in states:
+                st["step"] = t
+            launch[5] = t
         return True
 
     @torch.no_grad()
@@ -255,15 +335,20 @@ class HipAdam(torch.optim.Optimizer):
                 loss = closure()
         from . import _lib
         ops = _lib.load()
-        for group in self.param_groups:
-            if self._fast_step(ops, group):
+        groups = self.param_groups
+        grads = [[p.grad for p in group["params"]] for group in groups]
+        stat = None
+        if any(g["max_grad_norm"] is not None or g["skip_nonfinite"] for g in groups):
+            every = [g for gl in grads for g in gl if g is not None]
+            if every:  # the global norm: once, over all groups, before any update launch
+                stat = self._sumsq = ops.grad_sumsq(every)
+        self._count = True
+        for group, glist in zip(groups, grads):
+            if self._fast_step(ops, group, glist, stat):
                 continue
             self._plans.pop(id(group), None)
-            b1, b2 = group["betas"]
-            lr, eps = group["lr"], group["eps"]
             by_step = {}
-            for p in group["params"]:
-                g = p.grad
+            for i, (p, g) in enumerate(zip(group["params"], glist)):
                 if g is None:
                     continue
                 if g.is_sparse or not p.is_cuda or p.dtype != torch.float32:
@@ -274,44 +359,100 @@ class HipAdam(torch.optim.Optimizer):
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                 st["step"] = int(st["step"]) + 1  # (a tensor step from a foreign state_dict)
-                lists = by_step.setdefault(st["step"], ([], [], [], []))
+                lists = by_step.setdefault(st["step"], ([], [], [], [], []))
                 lists[0].append(p if p.is_contiguous() else p.data)
                 lists[1].append(g)  # a strided gradient is copied contiguous by the op
                 lists[2].append(st["exp_avg"])
                 lists[3].append(st["exp_avg_sq"])
-            for t, (ps, gs, ms, vs) in by_step.items():
+                lists[4].append(i)
+            for t, (ps, gs, ms, vs, _) in by_step.items():
                 if any(not q.is_contiguous() for q in ps):
                     raise RuntimeError("HipAdam: non-contiguous parameter")
-                step_size = lr / (1.0 - b1 ** t)
-                bc2_sqrt = math.sqrt(1.0 - b2 ** t)
-                ops.adam_step(ps, gs, ms, vs, b1, b2, eps, step_size, bc2_sqrt)
-            if len(by_step) == 1:
-                (t, (ps, _, ms, vs)), = by_step.items()
-                present = [p.grad is not None for p in group["params"]]
-                self._plans[id(group)] = (group["params"], present, ps, [self.state[p] for p in ps], ms, vs, t)
+                self._launch(ops, group, ps, gs, ms, vs, t, stat)
+            if by_step:
+                present = [g is not None for g in glist]
+                self._plans[id(group)] = (group["params"], present,
+                                          [[idx, ps, [self.state[group["params"][i]] for i in idx], ms, vs, t]
+                                           for t, (ps, _, ms, vs, idx) in by_step.items()])
         return loss
 
 
-def make_adam(params, lr):
+def _norm_of(sumsq):
+    """The norm beside ``dstagnn::grad_sumsq``'s sum: the op returns element 0 of a two-double
+    buffer and the kernel stores the root in element 1."""
+    return sumsq.as_strided((), (), 1)
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm):
+    """torch.nn.utils.clip_grad_norm_(parameters, max_norm) (L2: ``g *= min(1, max_norm / (norm +
+    1e-6))`` over all gradients, the pre-clip norm returned) in two launches and no host sync:
+    ``dstagnn::grad_sumsq`` (fp64 fold, the same bits on every call) and ``dstagnn::grad_scale``.
+    For users of other optimisers; HipAdam(max_grad_norm=) clips inside its update launch.
+    Returns a 0-dim fp64 device tensor.  fp32 CUDA gradients only."""
+    if torch.is_tensor(parameters):
+        parameters = [parameters]
+    max_norm = float(max_norm)
+    if not max_norm > 0.0:
+        raise ValueError(f"clip_grad_norm_: invalid max_norm {max_norm!r}")
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        return torch.zeros((), dtype=torch.float64)
+    from . import _lib
+    ops = _lib.load()
+    sumsq = ops.grad_sumsq(grads)
+    ops.grad_scale(grads, sumsq, max_norm)
+    return _norm_of(sumsq)
+
+
+def training_options(tc):
+    """Optional [Training] keys of a configuration (a ConfigParser section): ``max_grad_norm``,
+    ``weight_decay``, ``decoupled_weight_decay`` -> (float or None, float, bool).  The
+    reference's .conf files have none of them: (None, 0.0, False), today's behaviour."""
+    mn = tc.get('max_grad_norm', None)
+    return (None if mn is None else float(mn), float(tc.get('weight_decay', 0.0)),
+            tc.getboolean('decoupled_weight_decay', fallback=False))
+
+
+def make_adam(params, lr, weight_decay=0.0, decoupled=False, max_grad_norm=None):
     """The driver's optimiser (train_DSTAGNN_my.py:126): HipAdam (one launch) when every
     parameter is an fp32 GPU tensor; DSTAGNN_ADAM=torch-fused / torch for torch's fused or
-    default Adam (A/B)."""
+    default Adam (A/B).  weight_decay / decoupled / max_grad_norm: HipAdam's options; under the
+    torch modes (and off the GPU) the same options as torch.optim.Adam(weight_decay=) or
+    torch.optim.AdamW, and torch.nn.utils.clip_grad_norm_ in a step pre-hook (which, unlike
+    HipAdam, writes the clipped gradients back)."""
     params = list(params)
     mode = os.environ.get("DSTAGNN_ADAM", "hip")
     on_gpu = bool(params) and all(p.is_cuda and p.dtype == torch.float32 for p in params)
     if on_gpu and mode == "hip":
-        return HipAdam(params, lr=lr)
-    if on_gpu and mode == "torch-fused":
-        return torch.optim.Adam(params, lr=lr, fused=True)
-    return torch.optim.Adam(params, lr=lr)
+        return HipAdam(params, lr=lr, weight_decay=weight_decay, decoupled_weight_decay=decoupled,
+                       max_grad_norm=max_grad_norm)
+    if weight_decay < 0.0 or (max_grad_norm is not None and not max_grad_norm > 0.0):
+        raise ValueError("make_adam: invalid weight_decay / max_grad_norm")
+    kw = dict(fused=True) if on_gpu and mode == "torch-fused" else {}
+    if weight_decay and decoupled:
+        opt = torch.optim.AdamW(params, lr=lr, weight_decay=weight_decay, **kw)
+    else:
+        opt = torch.optim.Adam(params, lr=lr, weight_decay=weight_decay, **kw)
+    if max_grad_norm is not None:
+        def clip(*_):
+            torch.nn.utils.clip_grad_norm_(params, max_grad_norm)
+        opt.register_step_pre_hook(clip)
+    return opt
 
 
 def fit(net, train_x, train_y, val_x, val_y, *, epochs, start_epoch=0, batch_size, lr, params_path,
-        double_step=True, max_batches=None, log=print):
-    """The epoch loop of train_DSTAGNN_my.py:136-178.  Returns (best_epoch, best_val, history)."""
+        double_step=True, max_batches=None, log=print, max_grad_norm=None, weight_decay=0.0,
+        decoupled_weight_decay=False):
+    """The epoch loop of train_DSTAGNN_my.py:136-178.  Returns (best_epoch, best_val, history).
+    max_grad_norm / weight_decay / decoupled_weight_decay: make_adam's options (off by default,
+    as in the reference).  Under data parallelism ``reducer.all_reduce()`` precedes
+    ``optimizer.step()``, so the clipping norm is taken on the averaged gradients and is the
+    same on every rank: the ranks clip alike and their parameters stay equal."""
     rank, world = _world()
     criterion = nn.SmoothL1Loss().to(train_x.device)
-    optimizer = make_adam(net.parameters(), lr)
+    optimizer = make_adam(net.parameters(), lr, weight_decay=weight_decay, decoupled=decoupled_weight_decay,
+                          max_grad_norm=max_grad_norm)
     reducer = None
     if world > 1:  # block gradients all-reduced beside the backward (attach)
         reducer = GradAllReducer(net.named_parameters(), mask_support=mask_support_of(net)).attach(net)
@@ -320,7 +461,7 @@ def fit(net, train_x, train_y, val_x, val_y, *, epochs, start_epoch=0, batch_siz
     def optimizer_step(reduce=True):  # xm.optimizer_step
         if reducer is not None and reduce:
             reducer.all_reduce()
-        optimizer.step()
+        optimizer.step()  # (the global-norm clip, if any, after the all-reduce)
 
     best_val, best_epoch, history = float('inf'), 0, []
     for epoch in range(start_epoch, epochs):
@@ -368,8 +509,10 @@ def load_best(net, path):
 
 
 def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches=None, root='myexperiments',
-        log=print):
-    """Whole script: data, graphs, model, training, best-checkpoint test loss."""
+        log=print, max_grad_norm=None, weight_decay=None):
+    """Whole script: data, graphs, model, training, best-checkpoint test loss.  The optional
+    [Training] keys of training_options() switch clipping / weight decay on; max_grad_norm /
+    weight_decay given here override them."""
     config = configparser.ConfigParser()
     config.read(config_path)
     dc, tc = config['Data'], config['Training']
@@ -393,10 +536,14 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
         log(f'Params path: {params_path}')
     bs = int(tc['batch_size'])
     n_epochs = int(tc['epochs']) if epochs is None else int(epochs)
+    cfg_norm, cfg_wd, decoupled = training_options(tc)
     best_epoch, best_val, history = fit(net, train_x, train_y, val_x, val_y, epochs=n_epochs,
                                         start_epoch=int(tc['start_epoch']), batch_size=bs,
                                         lr=float(tc['learning_rate']), params_path=params_path,
-                                        double_step=double_step, max_batches=max_batches, log=log)
+                                        double_step=double_step, max_batches=max_batches, log=log,
+                                        max_grad_norm=cfg_norm if max_grad_norm is None else max_grad_norm,
+                                        weight_decay=cfg_wd if weight_decay is None else weight_decay,
+                                        decoupled_weight_decay=decoupled)
     load_best(net, os.path.join(params_path, f'epoch_{best_epoch}.params'))
     net.eval()
     test_loss = eval_batches(net, test_x, test_y, bs, nn.SmoothL1Loss())
@@ -415,6 +562,11 @@ def main(argv=None):
                     help="one optimizer step per batch (the reference steps twice: quirk 14)")
     ap.add_argument("--dropout", type=float, default=None, help="override the blocks' Dropout(0.05)")
     ap.add_argument("--out-root", default="myexperiments")
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="clip the gradients to this global L2 norm (overrides [Training] max_grad_norm)")
+    ap.add_argument("--weight-decay", type=float, default=None,
+                    help="Adam weight decay (overrides [Training] weight_decay; AdamW style with "
+                         "[Training] decoupled_weight_decay = true)")
     a = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
@@ -424,7 +576,8 @@ def main(argv=None):
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     try:
         run(a.config, epochs=a.epochs, double_step=not a.no_double_step, dropout=a.dropout,
-            max_batches=a.max_batches, root=a.out_root)
+            max_batches=a.max_batches, root=a.out_root, max_grad_norm=a.max_grad_norm,
+            weight_decay=a.weight_decay)
     finally:
         if world > 1:
             dist.destroy_process_group()

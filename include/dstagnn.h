@@ -307,6 +307,46 @@ int dstagnn_adam_chunk_elems(void);
 int dstagnn_adam_step(const dstagnn_adam_seg* segs, const int64_t* chunks, int nchunk, float beta1, float beta2,
                       float eps, float step_size, float bc2_sqrt, dstagnn_stream_t stream);
 
+/* Opt-in extras of the optimiser step, over the same segment / chunk tables (optim.hip).
+ *
+ * dstagnn_grad_sumsq: stat[0] = sum of g^2 over every segment (double), stat[1] = sqrt(stat[0]),
+ * the global L2 norm torch.nn.utils.clip_grad_norm_(norm_type=2) takes (there in fp32).  Only
+ * the segments' g and n are read.  partials: nchunk floats of device scratch; stat: two doubles
+ * on the device.  One launch, fixed summation order: the same bits on every call.  nchunk == 0
+ * stores zeros.
+ *
+ * dstagnn_adam_step_ex: dstagnn_adam_step with, per element and in this order,
+ *   max_norm > 0:    g = coef g, coef = min(1, max_norm / (sqrt(stat[0]) + 1e-6))
+ *                    (torch.nn.utils.clip_grad_norm_; the gradient itself is not written);
+ *   weight_decay > 0, decoupled == 0:  g += weight_decay p   (torch.optim.Adam(weight_decay=));
+ *   weight_decay > 0, decoupled != 0:  p *= 1 - lr weight_decay before the update
+ *                    (torch.optim.AdamW; lr is read for this only);
+ *   skip_nonfinite != 0 and stat[0] not finite: nothing is stored (p, m, v keep their values)
+ *                    and *skipped (device int, may be NULL) is incremented once.  The caller's
+ *                    step count t still advances: step_size / bc2_sqrt of the next call are
+ *                    those of t + 1, as if the skipped step had seen a zero update.
+ * stat may be NULL when max_norm == 0 and skip_nonfinite == 0.
+ *
+ * dstagnn_grad_scale: g *= min(1, max_norm / (sqrt(stat[0]) + 1e-6)) in place over every
+ * segment's g (written through the const pointer); with dstagnn_grad_sumsq in front, a
+ * stand-alone clip_grad_norm_ in two launches.  A coefficient of 1 leaves every bit. */
+typedef struct {
+  float beta1, beta2, eps;
+  float step_size, bc2_sqrt; /* as dstagnn_adam_step */
+  float lr;                  /* decoupled weight decay only */
+  float weight_decay;        /* 0: none */
+  int decoupled;             /* 0: L2 (Adam), else decoupled (AdamW) */
+  float max_norm;            /* 0: no clipping */
+  int skip_nonfinite;
+} dstagnn_adam_hyper;
+int dstagnn_grad_sumsq(const dstagnn_adam_seg* segs, const int64_t* chunks, int nchunk, float* partials,
+                       double* stat, dstagnn_stream_t stream);
+int dstagnn_adam_step_ex(const dstagnn_adam_seg* segs, const int64_t* chunks, int nchunk,
+                         const dstagnn_adam_hyper* hyper, const double* stat, int* skipped,
+                         dstagnn_stream_t stream);
+int dstagnn_grad_scale(const dstagnn_adam_seg* segs, const int64_t* chunks, int nchunk, const double* stat,
+                       float max_norm, dstagnn_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * Graph builders (stag.hip).  fp64 throughout, like the reference's numpy/scipy code.
  * ------------------------------------------------------------------------------------- */
