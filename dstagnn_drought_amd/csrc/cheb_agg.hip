@@ -30,13 +30,6 @@ namespace {
 
 __device__ __forceinline__ int frow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
-__device__ __forceinline__ floatx16 zero16() {
-  floatx16 z;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) z[r] = 0.f;
-  return z;
-}
-
 // 16 consecutive floats of a row (4 x 16-B loads); zeros when !ok
 __device__ __forceinline__ void row16(const float* p, bool ok, float (&v)[16]) {
 #pragma unroll
@@ -44,12 +37,6 @@ __device__ __forceinline__ void row16(const float* p, bool ok, float (&v)[16]) {
     const float4 t = ok ? *reinterpret_cast<const float4*>(p + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
     v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
   }
-}
-
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // XCD-aware row-block order (cheb_sparse.hip): each XCD walks one contiguous eighth of the rows

@@ -37,22 +37,8 @@ __device__ __forceinline__ void load16(const float* p, float (&v)[16]) {
 
 __device__ __forceinline__ int frag_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
-// Each wave stages its tile in its own LDS slice and only its own lanes read it back, so the
-// hand-off needs no workgroup barrier: a wavefront-scope release/acquire orders the LDS
-// accesses (the compiler may not move a read of another lane's element above this lane's
-// writes) and waves run independently.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ floatx16 zero16() {
-  floatx16 z;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) z[r] = 0.f;
-  return z;
-}
+// (Each wave stages its tile in its own LDS slice and only its own lanes read it back: the
+// hand-offs are wave_lds_sync, no workgroup barrier, and waves run independently.)
 
 // the A_pa o M_k term of z_ij (A_pa is a weight matrix; read only where its bit is set)
 __device__ __forceinline__ float apa_term(const ChebFl& a, const float* Mk, int i, int j) {

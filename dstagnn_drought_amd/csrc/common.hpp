@@ -215,6 +215,54 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// max / sum over each aligned group of 16 lanes (xor butterfly), every lane ending with the result
+__device__ __forceinline__ float xor_max_16(float v) {
+  v = fmaxf(v, __shfl_xor(v, 1, 64));
+  v = fmaxf(v, __shfl_xor(v, 2, 64));
+  v = fmaxf(v, __shfl_xor(v, 4, 64));
+  return fmaxf(v, __shfl_xor(v, 8, 64));
+}
+__device__ __forceinline__ float xor_sum_16(float v) {
+  v += __shfl_xor(v, 1, 64);
+  v += __shfl_xor(v, 2, 64);
+  v += __shfl_xor(v, 4, 64);
+  return v + __shfl_xor(v, 8, 64);
+}
+// sum over the 16 lanes of a DPP row, the same value in every lane (quad swaps, then the half-row
+// and row mirrors)
+__device__ __forceinline__ float row16_sum(float x) {
+  x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));
+  x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true));
+  x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x141, 0xF, 0xF, true));
+  x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x140, 0xF, 0xF, true));
+  return x;
+}
+
+// ---------------------------------------------------------------------------------
+// Matrix-core and single-wave helpers shared by the MFMA kernels.
+// ---------------------------------------------------------------------------------
+// v_mfma_f32_16x16x4_f32: lane (i = l & 15, q = l >> 4) holds A[i][q], B[q][i], D[4 q + r][i]
+__device__ __forceinline__ floatx4 mfma16(float a, float b, floatx4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+// component s of a float4 (s known after unrolling: a register pick, not an indexed access)
+__device__ __forceinline__ float f4at(const float4& v, int s) {
+  return s == 0 ? v.x : s == 1 ? v.y : s == 2 ? v.z : v.w;
+}
+__device__ __forceinline__ floatx16 zero16() {
+  floatx16 z;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) z[r] = 0.f;
+  return z;
+}
+// LDS hand-off inside ONE wave: a wave that stages a tile in its own LDS slice and only reads it
+// back itself needs no workgroup barrier; a wavefront-scope release/acquire orders the LDS
+// accesses (the compiler may not move a read of another lane's element above this lane's writes)
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // ---------------------------------------------------------------------------------
 // Counter-based dropout RNG: a splitmix64 key per (seed, mask), two 32-bit finalisers per element.

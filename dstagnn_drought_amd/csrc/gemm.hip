@@ -20,6 +20,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "handoff.hpp"
 #include "ops.hpp"
 
 #include "gemm_kern.hpp"
@@ -84,9 +85,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmG gin) {
 // (v_mfma_f32_16x16x4_f32, lane (q = l>>4, i = l&15): A[mt*16 + i][k + q] and
 // B[k + q][nt*16 + i]), then MT x NT MFMAs per quad into 16x16 accumulators.  One
 // 1024-thread workgroup per CU (<= 256 of them): its 16 accumulators fold in LDS in a fixed
-// order, and the workgroups' partials fold by tickets (colsum2d's hand-off: sc1 stores drained
-// by every storing wave, a barrier, one agent-scope ticket per workgroup; the last arrival
-// acquires, then all its 1024 threads sum the partials in a fixed order).  Small outputs
+// order, and the workgroups' partials fold by tickets (handoff.hpp: all 1024 threads of the
+// last arrival sum the partials in a fixed order).  Small outputs
 // (fcmy: 300 floats) fold in ONE level — the acquire's price grows with the workgroups per CU
 // (MI355X_MICROARCH.md), so one per CU pays it once; large ones (dTheta: 3 072 floats x 256
 // partials = 3 MB would take one CU ~20 us to read) fold in two: the last of each group of
@@ -109,34 +109,10 @@ struct SkinnyK {
   int stop;     // profiling probe (DSTAGNN_SKINNY_STOP): 1 = after the loads + MFMAs, 2 = after the ticket
 };
 
-__device__ __forceinline__ float sk_ld(const float* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void sk_st(float* p, float v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// ticket of one workgroup on *c among n arrivals (call after every storing wave drained its
-// sc1 stores and a barrier): true in every thread of the last arrival, which has acquired
-__device__ __forceinline__ bool sk_ticket(int* c, int n, int* last) {
-  if (threadIdx.x == 0) {
-    *last = atomicAdd(c, 1) == n - 1;
-    if (*last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(c, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
-    }
-  }
-  __syncthreads();
-  return *last != 0;
-}
-
 // sum of rows [0, nrows) of src (rows of P4 floats, 16-B aligned) in a fixed order: thread t
 // < C4 = P4/4 gets column quad t.  S = 1024 / C4 subsets of the rows per quad (sub, sub + S,
 // ...), sixteen 16-B loads in flight per round, then the subsets in order via LDS (sums:
-// >= 1024 float4).  relaxed: agent-scope loads (the rows came from other workgroups' sc1
-// stores and are read without this workgroup having acquired them at load time)
-template <bool RELAXED>
+// >= 1024 float4).  Plain 16-B loads: the caller is a last arrival, behind its acquire.
 __device__ __forceinline__ float4 sk_fold_rows(const float* src, int nrows, int P4, float4* sums) {
   const int t = threadIdx.x;
   const int C4 = P4 / 4, S = max(1, 1024 / C4);
@@ -147,19 +123,8 @@ __device__ __forceinline__ float4 sk_fold_rows(const float* src, int nrows, int 
     for (int q = sub; q < nrows; q += 16 * S) {
       float4 u[16];
 #pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        if (q + j * S < nrows) {
-          const float4* a = p + (int64_t)(q + j * S) * C4;
-          if (RELAXED) {
-            const float* f = reinterpret_cast<const float*>(a);
-            u[j] = make_float4(sk_ld(f), sk_ld(f + 1), sk_ld(f + 2), sk_ld(f + 3));
-          } else {
-            u[j] = *a;
-          }
-        } else {
-          u[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-      }
+      for (int j = 0; j < 16; ++j)
+        u[j] = q + j * S < nrows ? p[(int64_t)(q + j * S) * C4] : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
       for (int j = 0; j < 16; ++j) { v.x += u[j].x; v.y += u[j].y; v.z += u[j].z; v.w += u[j].w; }
     }
@@ -279,10 +244,8 @@ __global__ __launch_bounds__(1024) void skinny_dw_kernel(SkinnyK s) {
     float v = red[0][o];
 #pragma unroll
     for (int q = 1; q < kS; ++q) v += red[q][o];
-    sk_st(p1 + e, v);
+    st_agent(p1 + e, v);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
   float4* sums = reinterpret_cast<float4*>(&red[0][0]);
   const int C4 = s.P4 / 4;
   const float* rows = s.part;
@@ -290,20 +253,19 @@ __global__ __launch_bounds__(1024) void skinny_dw_kernel(SkinnyK s) {
   if (s.ngrp > 0) {
     // first level: the last arrival of this workgroup's group sums the group's partials
     const int grp = blockIdx.x / kSkGroup, g0 = grp * kSkGroup, gn = min(kSkGroup, s.nwg - g0);
-    if (!sk_ticket(s.cnt + 1 + grp, gn, &last) || s.stop == 2) return;
-    const float4 tot = sk_fold_rows<false>(s.part + (int64_t)g0 * s.P4, gn, s.P4, sums);
+    if (!last_arrival(s.cnt + 1 + grp, gn, &last) || s.stop == 2) return;
+    const float4 tot = sk_fold_rows(s.part + (int64_t)g0 * s.P4, gn, s.P4, sums);
     float* gs = s.part + ((int64_t)s.nwg + grp) * s.P4;
     if (t < C4) {
-      sk_st(gs + 4 * t, tot.x); sk_st(gs + 4 * t + 1, tot.y); sk_st(gs + 4 * t + 2, tot.z); sk_st(gs + 4 * t + 3, tot.w);
+      st_agent(gs + 4 * t, tot.x); st_agent(gs + 4 * t + 1, tot.y);
+      st_agent(gs + 4 * t + 2, tot.z); st_agent(gs + 4 * t + 3, tot.w);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
     rows = s.part + (int64_t)s.nwg * s.P4;
     nrows = s.ngrp;
   }
-  if (!sk_ticket(s.cnt, nrows, &last) || (s.stop == 2 && s.ngrp == 0)) return;
+  if (!last_arrival(s.cnt, nrows, &last) || (s.stop == 2 && s.ngrp == 0)) return;
   // the last arrival (plain loads behind its acquire)
-  const float4 tot = sk_fold_rows<false>(rows, nrows, s.P4, sums);
+  const float4 tot = sk_fold_rows(rows, nrows, s.P4, sums);
   if (t < C4) {
     const float tv[4] = {tot.x, tot.y, tot.z, tot.w};
 #pragma unroll

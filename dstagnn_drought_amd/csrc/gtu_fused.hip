@@ -25,6 +25,7 @@
 #include <set>
 
 #include "common.hpp"
+#include "handoff.hpp"
 #include "ops.hpp"
 
 namespace {
@@ -37,28 +38,12 @@ constexpr int kGSP = kGS + 1;   // ... of a node channel's concat row in G
 constexpr int kGMT = (kGNB * (kGT - 2) + 15) / 16;  // row tiles of the widest output (k = 3): 14
 constexpr int kGMTW = (kGMT + 3) / 4;                // per wave (four waves per channel half): 4
 
-__device__ __forceinline__ floatx4 gmf16(float a, float b, floatx4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float g4at(const float4& v, int s) {
-  return s == 0 ? v.x : s == 1 ? v.y : s == 2 ? v.z : v.w;
-}
 // the gates with the hardware reciprocal (v_rcp_f32, 1 ulp): gtu_tail.hip's fast_tanh /
 // fast_sigmoid up to the last bit of the reciprocal
 __device__ __forceinline__ float gf_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 __device__ __forceinline__ float gf_tanh(float x) {
   const float e = __expf(2.f * fminf(fmaxf(x, -15.f), 15.f));
   return 1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f);
-}
-
-// sum over the 16 lanes of a DPP row, the same value in every lane (quad swaps, then the half-row
-// and row mirrors)
-__device__ __forceinline__ float gf_row16_sum(float x) {
-  x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));
-  x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true));
-  x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x141, 0xF, 0xF, true));
-  x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x140, 0xF, 0xF, true));
-  return x;
 }
 
 // one GTU (kernel width KS): conv rows m = node * Tg + t' of this workgroup; wave w owns channel
@@ -95,8 +80,8 @@ __device__ __forceinline__ void gf_gtu(const GtuFusedArgs& a, int q, int s_off, 
 #pragma unroll
       for (int u = 0; u < kGMTW; ++u) {
         if (mt0 + 4 * u >= MT) continue;  // (wave-uniform)
-        accp[u] = gmf16(g4at(bp, s), g4at(av[u], s), accp[u]);
-        accq[u] = gmf16(g4at(bq, s), g4at(av[u], s), accq[u]);
+        accp[u] = mfma16(f4at(bp, s), f4at(av[u], s), accp[u]);
+        accq[u] = mfma16(f4at(bq, s), f4at(av[u], s), accq[u]);
       }
   };
   float4 p1, q1;
@@ -144,7 +129,7 @@ __device__ __forceinline__ void gf_gtu(const GtuFusedArgs& a, int q, int s_off, 
     }
     float* g = Gs + (n * kGC + c0) * kGSP + s_off + tp;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) g[r * kGSP] = gf_tanh(g4at(P, r)) * gf_sigmoid(g4at(Q, r));
+    for (int r = 0; r < 4; ++r) g[r * kGSP] = gf_tanh(f4at(P, r)) * gf_sigmoid(f4at(Q, r));
   }
 }
 
@@ -241,8 +226,8 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_fwd_fused_kernel(GtuFusedArgs
     const float* g0 = Gs + (n * kGC + i) * kGSP + lq;
 #pragma unroll
     for (int kk = 0; kk < kGS / 4; ++kk) {
-      acc[0] = gmf16(aw[kk], g0[4 * kk], acc[0]);
-      acc[1] = gmf16(aw[kk], g0[16 * kGSP + 4 * kk], acc[1]);
+      acc[0] = mfma16(aw[kk], g0[4 * kk], acc[0]);
+      acc[1] = mfma16(aw[kk], g0[16 * kGSP + 4 * kk], acc[1]);
     }
     float rv[2][4];
     float sum[4];
@@ -256,7 +241,7 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_fwd_fused_kernel(GtuFusedArgs
       float tco[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float tc = acc[v][r] + g4at(fb, r);
+        float tc = acc[v][r] + f4at(fb, r);
         if (a.drop_p > 0.f) tc *= drop_scale(a.seed, 1, (uint64_t)(ge0 + r) + a.drop_off, a.drop_p);
         float xres;
         if (FIRST) {
@@ -264,7 +249,7 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_fwd_fused_kernel(GtuFusedArgs
           xres = rw[v] * Rl[n * kGT + t0 + r] + rb[v];
         } else {
           tco[r] = fmaxf(Xs[(n * kGT + t0 + r) * kGXS + c] + tc, 0.f);
-          xres = g4at(xres4, r);
+          xres = f4at(xres4, r);
         }
         rv[v][r] = fmaxf(xres + tco[r], 0.f);
       }
@@ -275,7 +260,7 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_fwd_fused_kernel(GtuFusedArgs
     }
     float mean[4], rs[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) sum[r] = gf_row16_sum(rv[0][r] + rv[1][r]);
+    for (int r = 0; r < 4; ++r) sum[r] = row16_sum(rv[0][r] + rv[1][r]);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       mean[r] = sum[r] * (1.f / kGC);
@@ -283,7 +268,7 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_fwd_fused_kernel(GtuFusedArgs
       rs[r] = d0 * d0 + d1 * d1;
     }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) rs[r] = rsqrtf(gf_row16_sum(rs[r]) * (1.f / kGC) + 1e-5f);
+    for (int r = 0; r < 4; ++r) rs[r] = rsqrtf(row16_sum(rs[r]) * (1.f / kGC) + 1e-5f);
     if (tv) {
 #pragma unroll
       for (int v = 0; v < 2; ++v) {
@@ -311,13 +296,6 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_fwd_fused_kernel(GtuFusedArgs
   }
   TF_MARK(7);
   TF_PRINT("gtu_fused", 8);
-}
-
-__device__ __forceinline__ float gf_ld_agent(const float* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void gf_st_agent(float* p, float v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 bool gf_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -440,7 +418,7 @@ __device__ __forceinline__ void gb_tconv(int nn, float* Ds, float* dXs, int w, i
 #pragma unroll
       for (int s = 0; s < 4; ++s)
 #pragma unroll
-        for (int j = 0; j < KS; ++j) acc[uu][j] = gmf16(g4at(aq[ch & 1][j], s), g4at(bq[ch & 1], s), acc[uu][j]);
+        for (int j = 0; j < KS; ++j) acc[uu][j] = mfma16(f4at(aq[ch & 1][j], s), f4at(bq[ch & 1], s), acc[uu][j]);
       __builtin_amdgcn_sched_barrier(0);
     }
   }
@@ -565,13 +543,13 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_bwd_fused_kernel(GtuFusedBwdA
     for (int v = 0; v < 2; ++v)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        xh[v][r] = (g4at(r4[v], r) - g4at(mu4, r)) * g4at(rs4, r);
-        dxh[v][r] = g4at(dy4[v], r) * lg[v];
+        xh[v][r] = (f4at(r4[v], r) - f4at(mu4, r)) * f4at(rs4, r);
+        dxh[v][r] = f4at(dy4[v], r) * lg[v];
       }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      s1[r] = gf_row16_sum(dxh[0][r] + dxh[1][r]) * (1.f / kGC);
-      s2[r] = gf_row16_sum(dxh[0][r] * xh[0][r] + dxh[1][r] * xh[1][r]) * (1.f / kGC);
+      s1[r] = row16_sum(dxh[0][r] + dxh[1][r]) * (1.f / kGC);
+      s2[r] = row16_sum(dxh[0][r] * xh[0][r] + dxh[1][r] * xh[1][r]) * (1.f / kGC);
     }
     float dtc[2][4], dr[2][4];
 #pragma unroll
@@ -580,18 +558,18 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_bwd_fused_kernel(GtuFusedBwdA
       float dtco[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float d = g4at(rs4, r) * (dxh[v][r] - s1[r] - xh[v][r] * s2[r]);
-        d = g4at(r4[v], r) > 0.f ? d : 0.f;             // relu(xres + tco)
+        float d = f4at(rs4, r) * (dxh[v][r] - s1[r] - xh[v][r] * s2[r]);
+        d = f4at(r4[v], r) > 0.f ? d : 0.f;             // relu(xres + tco)
         dr[v][r] = d;
-        dtco[r] = g4at(tc4[v], r) > 0.f ? d : 0.f;      // tco = relu(...)
+        dtco[r] = f4at(tc4[v], r) > 0.f ? d : 0.f;      // tco = relu(...)
         float dt = dtco[r];
         if (a.drop_p > 0.f) dt *= drop_scale(a.seed, 1, (uint64_t)(e0 + r) + a.drop_off, a.drop_p);
         dtc[v][r] = tv ? dt : 0.f;
         if (tv) {
-          acc_s[0][v] += g4at(dy4[v], r) * xh[v][r];
-          acc_s[1][v] += g4at(dy4[v], r);
+          acc_s[0][v] += f4at(dy4[v], r) * xh[v][r];
+          acc_s[1][v] += f4at(dy4[v], r);
           if (FIRST) {
-            acc_s[NS > 2 ? 2 : 0][v] += FIRST ? d * g4at(x4, r) : 0.f;
+            acc_s[NS > 2 ? 2 : 0][v] += FIRST ? d * f4at(x4, r) : 0.f;
             acc_s[NS > 3 ? 3 : 0][v] += FIRST ? d : 0.f;
           }
         }
@@ -607,7 +585,7 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_bwd_fused_kernel(GtuFusedBwdA
     if (FIRST) {  // dx[n][t] = sum_c res_w[c] dr[c][t]
       float dxs[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) dxs[r] = gf_row16_sum(rw[0] * dr[0][r] + rw[1] * dr[1][r]);
+      for (int r = 0; r < 4; ++r) dxs[r] = row16_sum(rw[0] * dr[0][r] + rw[1] * dr[1][r]);
       if (tv && i == 0) *reinterpret_cast<float4*>(a.dx + nb * kGT + t0) = make_float4(dxs[0], dxs[1], dxs[2], dxs[3]);
     }
     // dG[c][s] = sum_t dtc[c][t] W[t][s] (k step r contracts t = 4 lq + r: the A fragment of
@@ -619,7 +597,7 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_bwd_fused_kernel(GtuFusedBwdA
       for (int ct = 0; ct < 2; ++ct) {
         g[st][ct] = floatx4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int r = 0; r < 4; ++r) g[st][ct] = gmf16(dtc[ct][r], aw[st][r], g[st][ct]);
+        for (int r = 0; r < 4; ++r) g[st][ct] = mfma16(dtc[ct][r], aw[st][r], g[st][ct]);
       }
     // the gate derivatives: o = c (tanh side) and o = C + c (sigmoid side) of conv row (n, t');
     // the gates themselves are the fcmy weight gradient's B fragments (below): G is not re-read
@@ -641,7 +619,7 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_bwd_fused_kernel(GtuFusedBwdA
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float dg = g[st][ct][r];
-          const float th = gf_tanh(g4at(pv[st][ct], r)), sg = gf_sigmoid(g4at(qv[st][ct], r));
+          const float th = gf_tanh(f4at(pv[st][ct], r)), sg = gf_sigmoid(f4at(qv[st][ct], r));
           dp[r] = dg * (1.f - th * th) * sg;
           dq[r] = dg * th * sg * (1.f - sg);
           gbv[st][ct][r] = th * sg;
@@ -662,7 +640,7 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_bwd_fused_kernel(GtuFusedBwdA
         for (int r = 0; r < 4; ++r) {
           const float av = i < kGT ? tt[(16 * ct + 4 * lq + r) * 13 + i] : 0.f;
 #pragma unroll
-          for (int st = 0; st < 2; ++st) accf[st] = gmf16(av, gbv[st][ct][r], accf[st]);
+          for (int st = 0; st < 2; ++st) accf[st] = mfma16(av, gbv[st][ct][r], accf[st]);
         }
       asm volatile("" ::: "memory");
     }
@@ -694,13 +672,13 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_bwd_fused_kernel(GtuFusedBwdA
     float x = 0.f;
 #pragma unroll
     for (int ww = 0; ww < kGW; ++ww) x += red[(q * kGW + ww) * kGC + c];
-    gf_st_agent(a.part + (int64_t)blockIdx.x * kGBP + q * kGC + c, x);
+    st_agent(a.part + (int64_t)blockIdx.x * kGBP + q * kGC + c, x);
   }
   if (tid < kGBF) {
     float x = 0.f;
 #pragma unroll
     for (int ww = 0; ww < kGW; ++ww) x += redf[ww * kGBF + tid];
-    gf_st_agent(a.part + (int64_t)blockIdx.x * kGBP + 4 * kGC + tid, x);
+    st_agent(a.part + (int64_t)blockIdx.x * kGBP + 4 * kGC + tid, x);
   }
 
   // ---- B. the transposed convolutions (each GTU's operands loaded during the previous one) ---
@@ -748,48 +726,17 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_bwd_fused_kernel(GtuFusedBwdA
   TF_PRINT("gtu_fused_bwd", 7);
 
   // ---- D. the parameter gradients: the last of each group of 16 workgroups sums the group's
-  //         partial rows (agent-scope stores above, agent acquire here) into a level-2 row, the
-  //         last group sums the level-2 rows in order: deterministic, no column-sum launches ---
+  //         partial rows (the hand-off of handoff.hpp) into a level-2 row, the last group sums
+  //         the level-2 rows in order: deterministic, no column-sum launches -----------------
   int* flag = reinterpret_cast<int*>(red);  // (red is free after step A)
   const int nwg = (int)gridDim.x, ng = (nwg + kGBG1 - 1) / kGBG1, g1 = (int)blockIdx.x / kGBG1;
   const int gsz = min(kGBG1, nwg - g1 * kGBG1);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    const int lg = atomicAdd(a.cnt + g1, 1) == gsz - 1;
-    if (lg) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(a.cnt + g1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
-    }
-    flag[0] = lg;
-  }
-  __syncthreads();
-  if (!flag[0]) return;
+  if (!last_arrival(a.cnt + g1, gsz, flag)) return;
   float* l2 = a.part + (int64_t)nwg * kGBP;  // level-2 rows [ng][P]
-  for (int e = tid; e < kGBP; e += NT) {
-    const float* src = a.part + (int64_t)g1 * kGBG1 * kGBP + e;
-    float u[kGBG1];
-#pragma unroll
-    for (int k = 0; k < kGBG1; ++k) u[k] = k < gsz ? gf_ld_agent(src + (int64_t)k * kGBP) : 0.f;
-    float v = 0.f;
-#pragma unroll
-    for (int k = 0; k < kGBG1; ++k) v += u[k];
-    gf_st_agent(l2 + (int64_t)g1 * kGBP + e, v);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    const int last2 = atomicAdd(a.cnt + ng, 1) == ng - 1;
-    if (last2) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(a.cnt + ng, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    flag[1] = last2;
-  }
-  __syncthreads();
-  if (!flag[1]) return;
+  for (int e = tid; e < kGBP; e += NT)
+    st_agent(l2 + (int64_t)g1 * kGBP + e,
+             sum_rows_agent<kGBG1>(a.part + (int64_t)g1 * kGBG1 * kGBP + e, kGBP, gsz));
+  if (!last_arrival(a.cnt + ng, ng, flag + 1)) return;
   for (int e = tid; e < kGBP; e += NT) {
     float* out;
     int o;
@@ -803,15 +750,7 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_bwd_fused_kernel(GtuFusedBwdA
       o = sidx < kGS ? t * kGS + sidx : t;
     }
     if (!out) continue;
-    float v = 0.f;
-    for (int k0 = 0; k0 < ng; k0 += kGBG1) {
-      float u[kGBG1];
-#pragma unroll
-      for (int k = 0; k < kGBG1; ++k) u[k] = k0 + k < ng ? gf_ld_agent(l2 + (int64_t)(k0 + k) * kGBP + e) : 0.f;
-#pragma unroll
-      for (int k = 0; k < kGBG1; ++k) v += u[k];
-    }
-    out[o] = v;
+    out[o] = sum_rows_agent<kGBG1>(l2 + e, kGBP, ng);
   }
 }
 

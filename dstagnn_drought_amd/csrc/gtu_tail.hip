@@ -21,22 +21,17 @@
 // (node kernel, PH 2); backward: LN / residual -> dtc (node kernel, PH 1), dG = dtc W as
 // one GEMM, the gates backward from dG (gtu_gates_bwd_kernel).
 #include "common.hpp"
+#include "handoff.hpp"
 #include "ops.hpp"
 
 namespace {
 
-// agent-scope stores / loads of the in-kernel partial hand-off (colsum2d's protocol)
-__device__ __forceinline__ void gt_st_agent(float* p, float v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float gt_ld_agent(const float* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 constexpr int kGtG1 = 64;  // workgroups (nodes) per level-1 group of the partial-sum ticket tree
 
 // the last workgroup of each kGtG1 group sums the group's rows of the NS partial arrays (fixed
 // order) into level-2 rows; the last group sums those into fold_out.  Called by every
-// workgroup after its partial rows went out with agent-scope stores.
+// workgroup after its partial rows went out with agent-scope stores (the hand-off of handoff.hpp;
+// the row sums are split over SPL lanes per item, so they are loops of their own).
 template <int C, int NT, int NS>
 __device__ __forceinline__ void tail_fold(const GtuTailArgs& a, float* red, int* flag) {
   const int tid = threadIdx.x;
@@ -45,50 +40,26 @@ __device__ __forceinline__ void tail_fold(const GtuTailArgs& a, float* red, int*
   const int gsz = min(kGtG1, nwg - g1 * kGtG1);
   constexpr int ITEMS = NS * C, SPL = NT / ITEMS > 0 ? NT / ITEMS : 1;  // (item, row-split) per thread
   static_assert(NT % ITEMS == 0 || ITEMS % NT == 0, "thread layout");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    const int last = atomicAdd(a.fold_cnt + g1, 1) == gsz - 1;
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(a.fold_cnt + g1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
-    }
-    *flag = last;
-  }
-  __syncthreads();
-  if (!*flag) return;
+  if (!last_arrival(a.fold_cnt + g1, gsz, flag)) return;
   for (int e = tid; e < ITEMS * SPL; e += NT) {  // level 1: rows [g1 * kGtG1, + gsz) of each array
     const int it = e % ITEMS, sp = e / ITEMS, q = it / C, c = it - q * C;
     const float* src = part[q] + (int64_t)g1 * kGtG1 * C + c;
     float v = 0.f;
-    for (int r = sp; r < gsz; r += SPL) v += gt_ld_agent(src + (int64_t)r * C);
+    for (int r = sp; r < gsz; r += SPL) v += ld_agent(src + (int64_t)r * C);
     red[e] = v;
   }
   __syncthreads();
   for (int it = tid; it < ITEMS; it += NT) {
     float v = 0.f;
     for (int sp = 0; sp < SPL; ++sp) v += red[sp * ITEMS + it];
-    gt_st_agent(a.fold_ws + ((int64_t)(it / C) * ng + g1) * C + it % C, v);
+    st_agent(a.fold_ws + ((int64_t)(it / C) * ng + g1) * C + it % C, v);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    const int last = atomicAdd(a.fold_cnt + ng, 1) == ng - 1;
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(a.fold_cnt + ng, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    *flag = last;
-  }
-  __syncthreads();
-  if (!*flag) return;
+  if (!last_arrival(a.fold_cnt + ng, ng, flag)) return;
   for (int e = tid; e < ITEMS * SPL; e += NT) {  // level 2: the ng group rows
     const int it = e % ITEMS, sp = e / ITEMS, q = it / C, c = it - q * C;
     const float* src = a.fold_ws + (int64_t)q * ng * C + c;
     float v = 0.f;
-    for (int r = sp; r < ng; r += SPL) v += gt_ld_agent(src + (int64_t)r * C);
+    for (int r = sp; r < ng; r += SPL) v += ld_agent(src + (int64_t)r * C);
     red[e] = v;
   }
   __syncthreads();
@@ -945,11 +916,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 8))) void
   }
   if (a.fold) {  // one partial row per workgroup (its grid-stride nodes), then the ticket tree
     if (tid < C) {
-      gt_st_agent(a.gpart + (int64_t)blockIdx.x * C + tid, facc[0]);
-      gt_st_agent(a.bpart + (int64_t)blockIdx.x * C + tid, facc[1]);
+      st_agent(a.gpart + (int64_t)blockIdx.x * C + tid, facc[0]);
+      st_agent(a.bpart + (int64_t)blockIdx.x * C + tid, facc[1]);
       if (FIRST) {
-        gt_st_agent(a.rpart + (int64_t)blockIdx.x * C + tid, facc[2]);
-        gt_st_agent(a.dpart + (int64_t)blockIdx.x * C + tid, facc[3]);
+        st_agent(a.rpart + (int64_t)blockIdx.x * C + tid, facc[2]);
+        st_agent(a.dpart + (int64_t)blockIdx.x * C + tid, facc[3]);
       }
     }
     __shared__ int flag;

@@ -14,6 +14,7 @@
 #include <mutex>
 
 #include "common.hpp"
+#include "handoff.hpp"
 #include "ops.hpp"
 
 namespace {
@@ -612,7 +613,6 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(LnFwd a) {
 // so a row is V4 16-B loads per source per lane instead of 4 V4 dword loads (the wave-per-row
 // kernel above at L = 512 issued 32 loads and 16 stores per lane).  The row sums go over a
 // different partition of the row (within the fp32 rounding of the other kernel).
-__device__ __forceinline__ float l4at(const float4& v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
 __device__ __forceinline__ void l4set(float4& v, int c, float x) {
   if (c == 0) v.x = x; else if (c == 1) v.y = x; else if (c == 2) v.z = x; else v.w = x;
 }
@@ -648,7 +648,7 @@ __global__ __launch_bounds__(256) void ln_fwd_v4_kernel(LnFwd a) {
   for (int q = 0; q < V4; ++q)
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const float d = l4at(v[q], c) - mean;
+      const float d = f4at(v[q], c) - mean;
       var += d * d;
     }
   var = wave_sum(var) / L;
@@ -664,7 +664,7 @@ __global__ __launch_bounds__(256) void ln_fwd_v4_kernel(LnFwd a) {
     float4 y;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      float t = (l4at(v[q], c) - mean) * rs * l4at(gv[q], c) + l4at(bv[q], c);
+      float t = (f4at(v[q], c) - mean) * rs * f4at(gv[q], c) + f4at(bv[q], c);
       if (a.drop_p > 0.f) t *= drop_u(dk, (uint64_t)row * L + 4 * e4 + c + a.drop_off) >= a.drop_p ? dscale : 0.0f;
       l4set(y, c, t);
     }
@@ -702,12 +702,12 @@ __global__ __launch_bounds__(256) void ln_bwd_v4_kernel(LnBwd a) {
       const int e4 = lane + 64 * q;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        float dy = l4at(dyl[q], c);
+        float dy = f4at(dyl[q], c);
         if (a.drop_p > 0.f) dy *= drop_u(dk, (uint64_t)row * L + 4 * e4 + c + a.drop_off) >= a.drop_p ? dscale : 0.0f;
-        const float x = (l4at(ul[q], c) - mean) * rs;
+        const float x = (f4at(ul[q], c) - mean) * rs;
         l4set(dyv[q], c, dy);
         l4set(xh[q], c, x);
-        const float dxh = dy * l4at(gl[q], c);
+        const float dxh = dy * f4at(gl[q], c);
         s1 += dxh;
         s2 += dxh * x;
         if (PART) {
@@ -726,8 +726,8 @@ __global__ __launch_bounds__(256) void ln_bwd_v4_kernel(LnBwd a) {
       float4 d;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        float t = rs * (l4at(dyv[q], c) * l4at(gl[q], c) - s1 - l4at(xh[q], c) * s2);
-        if (a.beta != 0.f) t += a.beta * l4at(xin[q], c);
+        float t = rs * (f4at(dyv[q], c) * f4at(gl[q], c) - s1 - f4at(xh[q], c) * s2);
+        if (a.beta != 0.f) t += a.beta * f4at(xin[q], c);
         l4set(d, c, t);
       }
       reinterpret_cast<float4*>(a.dx + xo)[lane + 64 * q] = d;
@@ -1101,10 +1101,9 @@ __global__ __launch_bounds__(1024) void colsum_stage2(ColsumArgs a) {
 // row lane t / E, so a pass reads RP*E consecutive floats); E > 256 -> groups of
 // W = I*floor(256/I) columns, one row per pass.  Rows: R chunks (grid.x), ~1K blocks in
 // total, 8 independent loads in flight per thread.  The cross-block sum is a two-level
-// ticket tree: the last block of each run of 32 row chunks adds their partials (fixed
-// order) into a level-2 partial; the last of those adds the <= 32 level-2 partials, folds
-// each output's I columns and stores.  Tickets are re-armed (0) by the blocks that drew the
-// last one, so the next launch on this stream finds them zero.  One launch, no float atomics.
+// ticket tree (handoff.hpp): the last block of each run of 32 row chunks adds their partials
+// (fixed order) into a level-2 partial; the last of those adds the <= 32 level-2 partials,
+// folds each output's I columns and stores.  One launch, no float atomics.
 // -------------------------------------------------------------------------------------
 constexpr int kCsW = 256;   // partial width (columns)
 constexpr int kCsL1 = 32;   // row chunks per level-1 ticket
@@ -1120,18 +1119,6 @@ struct Colsum2dArgs {
   float* part = nullptr;   // level 1: [nsrc*G][R][256], then level 2: [nsrc*G][R2][256]
   int* cnt = nullptr;      // [nsrc*G][R2] level-1 tickets, then [nsrc*G] level-2 tickets
 };
-
-// sum of n <= 32 partial rows p[q*256 + t] in fixed order; all loads issued before the
-// first add (one memory round trip: the sc1 loads are served beyond the XCD's L2)
-__device__ __forceinline__ float sum_partials(const float* p, int n, int t) {
-  float u[kCsL1];
-#pragma unroll
-  for (int k = 0; k < kCsL1; ++k) u[k] = k < n ? ld_agent(p + (int64_t)k * kCsW + t) : 0.f;
-  float v = 0.f;
-#pragma unroll
-  for (int k = 0; k < kCsL1; ++k) v += u[k];
-  return v;
-}
 
 __global__ __launch_bounds__(256) void colsum2d_kernel(Colsum2dArgs a) {
   __shared__ float red[kCsW];
@@ -1168,38 +1155,18 @@ __global__ __launch_bounds__(256) void colsum2d_kernel(Colsum2dArgs a) {
     if (t < a.E)
       for (int l = 0; l < a.RP; ++l) colv += red[l * a.E + t];
   }
-  // hand-off (MI355X_MICROARCH.md, inter-workgroup visibility, "valid forms"): producers
-  // store sc1 (agent-scope relaxed atomics), every storing wave drains them (vmcnt(0)), a
-  // barrier, then ONE lane's agent-scope ticket add.  The block whose add came last issues
-  // an agent-scope ACQUIRE (L1 invalidate, only the winning blocks pay it) before any read
-  // of the partials, so the hand-off does not rest on the measured sc1-load table (whose
-  // row assumes one workgroup per CU).  No release fence on the producers (it would write
-  // back the XCD's whole L2): sc1 stores already bypass it.
+  // the two-level hand-off (handoff.hpp): n1, R2 <= kCsL1 rows per sum
   float* p1 = a.part + ((int64_t)gidx * a.R + r) * kCsW;
   if (t < a.W) st_agent(p1 + t, colv);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
   const int c1 = r / kCsL1;
   const int n1 = min(kCsL1, a.R - c1 * kCsL1);
-  if (t == 0) {
-    last = atomicAdd(a.cnt + (int64_t)gidx * a.R2 + c1, 1) == n1 - 1;
-    if (last) colsum_acquire();
-  }
-  __syncthreads();
-  if (!last) return;
+  if (!last_arrival(a.cnt + (int64_t)gidx * a.R2 + c1, n1, &last)) return;
   float* p2 = a.part + ((int64_t)a.nsrc * a.G * a.R + (int64_t)gidx * a.R2 + c1) * kCsW;
-  if (t < a.W) st_agent(p2 + t, sum_partials(a.part + ((int64_t)gidx * a.R + (int64_t)c1 * kCsL1) * kCsW, n1, t));
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  int* cnt2 = a.cnt + (int64_t)a.nsrc * a.G * a.R2 + gidx;
-  if (t == 0) {
-    __hip_atomic_store(a.cnt + (int64_t)gidx * a.R2 + c1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last = atomicAdd(cnt2, 1) == a.R2 - 1;
-    if (last) colsum_acquire();
-  }
-  __syncthreads();
-  if (!last) return;
-  red[t] = t < a.W ? sum_partials(a.part + ((int64_t)a.nsrc * a.G * a.R + (int64_t)gidx * a.R2) * kCsW, a.R2, t)
+  if (t < a.W)
+    st_agent(p2 + t, sum_rows_agent<kCsL1>(a.part + ((int64_t)gidx * a.R + (int64_t)c1 * kCsL1) * kCsW + t, kCsW, n1));
+  if (!last_arrival(a.cnt + (int64_t)a.nsrc * a.G * a.R2 + gidx, a.R2, &last)) return;
+  red[t] = t < a.W ? sum_rows_agent<kCsL1>(a.part + ((int64_t)a.nsrc * a.G * a.R + (int64_t)gidx * a.R2) * kCsW + t,
+                                           kCsW, a.R2)
                    : 0.f;
   __syncthreads();
   const int opg = a.W / a.I;
@@ -1212,7 +1179,6 @@ __global__ __launch_bounds__(256) void colsum2d_kernel(Colsum2dArgs a) {
       *d = (a.beta != 0.f ? a.beta * *d : 0.f) + v;
     }
   }
-  if (t == 0) __hip_atomic_store(cnt2, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // =====================================================================================
@@ -1228,22 +1194,6 @@ __global__ __launch_bounds__(256) void colsum2d_kernel(Colsum2dArgs a) {
 // ~2 400 VALU and ~700 LDS instructions per problem on index arithmetic and LDS operands.)
 // =====================================================================================
 constexpr int kTmD = 32;  // d_k = d_v of the matrix-core variant
-
-__device__ __forceinline__ float xor_max_16(float v) {
-  v = fmaxf(v, __shfl_xor(v, 1, 64));
-  v = fmaxf(v, __shfl_xor(v, 2, 64));
-  v = fmaxf(v, __shfl_xor(v, 4, 64));
-  return fmaxf(v, __shfl_xor(v, 8, 64));
-}
-__device__ __forceinline__ float xor_sum_16(float v) {
-  v += __shfl_xor(v, 1, 64);
-  v += __shfl_xor(v, 2, 64);
-  v += __shfl_xor(v, 4, 64);
-  return v + __shfl_xor(v, 8, 64);
-}
-__device__ __forceinline__ floatx4 mfma16(float a, float b, floatx4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 template <int T>
 __global__ __launch_bounds__(256) void tat_fwd_mfma_kernel(TatArgs a) {
@@ -1436,22 +1386,12 @@ __global__ __launch_bounds__(256) void tat_bwd_mfma_kernel(TatArgs a) {
   }
   if (!a.dres_sum) return;
   // res_att gradient sum_f dS (deterministic): the four tiles in wave order, one partial per
-  // workgroup (sc1 stores, drained, barrier), a ticket per (b, head); the last of its nch
-  // workgroups acquires and adds the partials in chunk order (colsum2d's hand-off)
+  // workgroup, a ticket per (b, head); the last of its nch workgroups adds the partials in chunk
+  // order (handoff.hpp)
   const int t = threadIdx.x, bh = blockIdx.x / nch, ch = blockIdx.x - bh * nch;
   float* part = a.dscore + (int64_t)bh * nch * T * T;
   if (t < T * T) st_agent(part + (int64_t)ch * T * T + t, ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t]);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (t == 0) {
-    last = atomicAdd(a.cnt + bh, 1) == nch - 1;
-    if (last) {
-      colsum_acquire();
-      __hip_atomic_store(a.cnt + bh, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
-    }
-  }
-  __syncthreads();
-  if (!last || t >= T * T) return;
+  if (!last_arrival(a.cnt + bh, nch, &last) || t >= T * T) return;
   float v = 0.f;
   for (int k = 0; k < nch; ++k) v += ld_agent(part + (int64_t)k * T * T + t);
   a.dres_sum[(int64_t)bh * T * T + t] = v;

@@ -369,22 +369,8 @@ int op_tat_bwd(int B, int F, int T, int h, int dk, int dv, const float* qkv, con
 int op_ln_fwd(const LnFwd& a, hipStream_t st);
 int op_ln_bwd(const LnBwd& a, hipStream_t st);
 // zero-armed int tickets private to (current device, stream); nullptr if unavailable
+// (the in-kernel folds' hand-off, handoff.hpp, leaves every ticket it draws back at zero)
 int* stream_counters(hipStream_t st, int n);
-// the ticket hand-off's accesses (colsum2d_kernel in ops.hip, grad_sumsq_kernel in optim.hip):
-// sc1 (agent-scope relaxed) loads / stores of the partials
-__device__ __forceinline__ float ld_agent(const float* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_agent(float* p, float v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// consumer side of the hand-off: agent acquire, then wait for the invalidate to complete
-// (the caller's workgroup barrier holds the other waves behind it)
-__device__ __forceinline__ void colsum_acquire() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
 int op_colsum(const float* in, int64_t A, int O, int I, float* out, int64_t ostride, float beta, float* part,
               size_t part_floats, hipStream_t st);
 int op_colsum_multi(const float* const* ins, float* const* outs, int nsrc, int64_t A, int O, int I,

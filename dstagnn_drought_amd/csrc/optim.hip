@@ -18,8 +18,8 @@
 //                      root (the global L2 norm).  One workgroup per chunk: all 16 loads per
 //                      thread, 16 sequential fp32 adds of the squares, the wave butterfly
 //                      (6 adds), the four wave sums ((w0 + w1) + (w2 + w3)); the chunk's partial
-//                      goes out sc1, and the workgroup whose ticket came last (colsum2d's
-//                      hand-off, ops.hip) adds all partials in fp64 in one fixed order: thread t
+//                      goes out sc1, and the workgroup whose ticket came last (the hand-off
+//                      of handoff.hpp) adds all partials in fp64 in one fixed order: thread t
 //                      takes partials t, t + 256, ... in index order, then a fixed LDS tree.  No
 //                      workgroup waits for another; the same bits on every launch.
 //   adam_ex_kernel     adam_kernel's body with, per element and in this order: g = coef g
@@ -28,6 +28,7 @@
 //                      weight_decay) or p *= 1 - lr wd (torch.optim.AdamW); with skip_nonfinite
 //                      and a non-finite stat[0] every workgroup returns before its first store.
 //   grad_scale_kernel  g *= coef in place (the second half of a stand-alone clip_grad_norm_).
+#include "handoff.hpp"
 #include "ops.hpp"
 
 namespace {
@@ -98,19 +99,9 @@ __global__ __launch_bounds__(kAdamThreads) void grad_sumsq_kernel(const dstagnn_
   acc = wave_sum(acc);
   if ((t & 63) == 0) wsum[t >> 6] = acc;
   __syncthreads();
-  // hand-off as colsum2d_kernel's (ops.hip; MI355X_MICROARCH.md, inter-workgroup visibility,
-  // "valid forms"): the partial stored sc1 (agent-scope relaxed atomic) and drained, a barrier,
-  // ONE lane's agent-scope ticket add; the workgroup whose add came last takes an agent-scope
-  // acquire before it reads any partial (themselves sc1 loads)
+  // the hand-off of handoff.hpp: the last workgroup reads every partial (themselves sc1 loads)
   if (t == 0) st_agent(partials + blockIdx.x, (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]));
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (t == 0) {
-    last = atomicAdd(ticket, 1) == (int)gridDim.x - 1;
-    if (last) colsum_acquire();
-  }
-  __syncthreads();
-  if (!last) return;
+  if (!last_arrival(ticket, (int)gridDim.x, &last)) return;
   double a = 0.0;
   for (int64_t k = t; k < (int64_t)gridDim.x; k += kAdamThreads) a += (double)ld_agent(partials + k);
   dred[t] = a;
@@ -123,7 +114,6 @@ __global__ __launch_bounds__(kAdamThreads) void grad_sumsq_kernel(const dstagnn_
   if (t == 0) {
     stat[0] = dred[0];
     stat[1] = sqrt(dred[0]);
-    __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 

@@ -23,20 +23,6 @@ constexpr int kSbRT = 2, kSbRows = 16 * kSbRT, kSbW = 8, kSbD = 512, kSbK = 192;
 constexpr int kSbDT = kSbD / 16 / kSbW;                          // d-tiles per wave (4)
 constexpr int kSbKS = kSbK + 4;                                  // LDS row stride of the dqk tile
 
-__device__ __forceinline__ floatx4 smf16(float a, float b, floatx4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float s4at(const float4& v, int s) {
-  return s == 0 ? v.x : s == 1 ? v.y : s == 2 ? v.z : v.w;
-}
-__device__ __forceinline__ float sb_row16_sum(float x) {  // sum over a DPP row of 16 lanes
-  x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));
-  x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true));
-  x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x141, 0xF, 0xF, true));
-  x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x140, 0xF, 0xF, true));
-  return x;
-}
-
 __global__ __launch_bounds__(kSbW * 64, 1) void sat_ln_bwd_fused_kernel(SatLnBwdArgs a) {
   constexpr int NT = kSbW * 64;
   __shared__ float4 Qs4[kSbRows * kSbKS / 4];
@@ -119,7 +105,7 @@ __global__ __launch_bounds__(kSbW * 64, 1) void sat_ln_bwd_fused_kernel(SatLnBwd
       for (int rt = 0; rt < kSbRT; ++rt)
 #pragma unroll
         for (int t = 0; t < kSbDT; ++t)
-          acc[rt][t] = smf16(s4at(ap[ch & 1][t], s), s4at(bp[ch & 1][rt], s), acc[rt][t]);
+          acc[rt][t] = mfma16(f4at(ap[ch & 1][t], s), f4at(bp[ch & 1][rt], s), acc[rt][t]);
     if (drop)
 #pragma unroll
       for (int k = ch * PER; k < (ch + 1) * PER && k < NE; ++k) hash(k);
@@ -141,8 +127,8 @@ __global__ __launch_bounds__(kSbW * 64, 1) void sat_ln_bwd_fused_kernel(SatLnBwd
         float v = acc[rt][t][r];
         if (drop) v *= (keep >> (16 * rt + 4 * t + r)) & 1u ? dscale : 0.0f;
         dy[rt][t][r] = v;
-        xh[rt][t][r] = (s4at(uv[rt][t], r) - mean[rt]) * rs[rt];
-        const float dxh = v * s4at(gv[t], r);
+        xh[rt][t][r] = (f4at(uv[rt][t], r) - mean[rt]) * rs[rt];
+        const float dxh = v * f4at(gv[t], r);
         s1[rt] += dxh;
         s2[rt] += dxh * xh[rt][t][r];
       }
@@ -181,7 +167,7 @@ __global__ __launch_bounds__(kSbW * 64, 1) void sat_ln_bwd_fused_kernel(SatLnBwd
       float dx[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        dx[r] = rs[rt] * (dy[rt][t][r] * s4at(gv[t], r) - s1[rt] - xh[rt][t][r] * s2[rt]);
+        dx[r] = rs[rt] * (dy[rt][t][r] * f4at(gv[t], r) - s1[rt] - xh[rt][t][r] * s2[rt]);
         if (live) {  // column partials over the workgroup's rows
           gp[r] += dy[rt][t][r] * xh[rt][t][r];
           bq[r] += dy[rt][t][r];
@@ -192,9 +178,9 @@ __global__ __launch_bounds__(kSbW * 64, 1) void sat_ln_bwd_fused_kernel(SatLnBwd
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      gp[r] = sb_row16_sum(gp[r]);
-      bq[r] = sb_row16_sum(bq[r]);
-      xp[r] = sb_row16_sum(xp[r]);
+      gp[r] = row16_sum(gp[r]);
+      bq[r] = row16_sum(bq[r]);
+      xp[r] = row16_sum(xp[r]);
     }
     if (i == 0) {
       const int64_t po = (int64_t)blockIdx.x * kSbD + d0;

@@ -24,6 +24,7 @@
 #include <set>
 
 #include "common.hpp"
+#include "handoff.hpp"
 #include "ops.hpp"
 
 namespace {
@@ -42,24 +43,6 @@ constexpr int kTfDsMax = 2304;          // (48 / T) h T^2 at T = 16
 constexpr int kTfG1 = 16;               // workgroups per level-1 group of the gamma / beta ticket tree
 
 
-__device__ __forceinline__ floatx4 mf16(float a, float b, floatx4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float xmax16(float v) {
-  v = fmaxf(v, __shfl_xor(v, 1, 64));
-  v = fmaxf(v, __shfl_xor(v, 2, 64));
-  v = fmaxf(v, __shfl_xor(v, 4, 64));
-  return fmaxf(v, __shfl_xor(v, 8, 64));
-}
-__device__ __forceinline__ float xsum16(float v) {
-  v += __shfl_xor(v, 1, 64);
-  v += __shfl_xor(v, 2, 64);
-  v += __shfl_xor(v, 4, 64);
-  return v + __shfl_xor(v, 8, 64);
-}
-__device__ __forceinline__ float f4at(const float4& v, int s) {
-  return s == 0 ? v.x : s == 1 ? v.y : s == 2 ? v.z : v.w;
-}
 // NV independent full-wave sums, every lane ending with every total: the xor butterfly run
 // level by level over all NV values, so each level's NV shuffles are independent (one shuffle
 // latency per level, not per value).  Fixed order, and lanes agree bitwise (each level adds two
@@ -72,17 +55,6 @@ __device__ __forceinline__ void tf_wave_sums(float (&v)[NV]) {
   for (int o = 32; o > 0; o >>= 1)
 #pragma unroll
     for (int k = 0; k < NV; ++k) v[k] += __shfl_xor(v[k], o, 64);
-}
-__device__ __forceinline__ float tf_ld_agent(const float* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void tf_st_agent(float* p, float v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void tf_wave_sync() {  // LDS hand-off inside one wave
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 // a contiguous block of n floats from LDS (row stride ls, row length rl, both multiples of 4)
 // to global memory, float4 per lane (the stores of a kernel go out at its end: stores count in
@@ -126,7 +98,7 @@ __device__ __forceinline__ void tf_mma(floatx4 (&acc)[3][NJ], const float4 (&av)
 #pragma unroll
     for (int mt = 0; mt < 3; ++mt)
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) acc[mt][j] = mf16(f4at(av[mt], s), f4at(bq[j], s), acc[mt][j]);
+      for (int j = 0; j < NJ; ++j) acc[mt][j] = mfma16(f4at(av[mt], s), f4at(bq[j], s), acc[mt][j]);
 }
 // B fragments come from L2 (the re-laid weights): with one chunk of look-ahead every chunk waited
 // a full L2 round trip (the products ran at ~1/3 of the CU's MFMA rate, -DDSTAGNN_TF_TIMING).  A
@@ -341,14 +313,14 @@ __global__ __launch_bounds__(64 * W, 1) void tat_fused_fwd_kernel(TatFusedArgs a
       q1 = *reinterpret_cast<const float4*>(Qp + c * kTfLQ + 8 * q + 4);
     }
     floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = mf16(k0.x, q0.x, acc);
-    acc = mf16(k0.y, q0.y, acc);
-    acc = mf16(k0.z, q0.z, acc);
-    acc = mf16(k0.w, q0.w, acc);
-    acc = mf16(k1.x, q1.x, acc);
-    acc = mf16(k1.y, q1.y, acc);
-    acc = mf16(k1.z, q1.z, acc);
-    acc = mf16(k1.w, q1.w, acc);
+    acc = mfma16(k0.x, q0.x, acc);
+    acc = mfma16(k0.y, q0.y, acc);
+    acc = mfma16(k0.z, q0.z, acc);
+    acc = mfma16(k0.w, q0.w, acc);
+    acc = mfma16(k1.x, q1.x, acc);
+    acc = mfma16(k1.y, q1.y, acc);
+    acc = mfma16(k1.z, q1.z, acc);
+    acc = mfma16(k1.w, q1.w, acc);
     const float rv[4] = {rr[k].x, rr[k].y, rr[k].z, rr[k].w};
     float sc[4], pr[4];
 #pragma unroll
@@ -360,17 +332,17 @@ __global__ __launch_bounds__(64 * W, 1) void tat_fused_fwd_kernel(TatFusedArgs a
     if (vi && vj) *reinterpret_cast<float4*>(RA + tb + c * T + 4 * q) = make_float4(sc[0], sc[1], sc[2], sc[3]);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const float m = xmax16(vi ? sc[r] : -INFINITY);
+      const float m = xor_max_16(vi ? sc[r] : -INFINITY);
       const float e = vi ? __expf(sc[r] - m) : 0.f;
-      const float inv = 1.f / xsum16(e);
+      const float inv = 1.f / xor_sum_16(e);
       pr[r] = vj ? e * inv : 0.f;
     }
     if (vi && vj) *reinterpret_cast<float4*>(AT + tb + c * T + 4 * q) = make_float4(pr[0], pr[1], pr[2], pr[3]);
     floatx4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      c0 = mf16(pr[s], vv[0][s], c0);
-      c1 = mf16(pr[s], vv[1][s], c1);
+      c0 = mfma16(pr[s], vv[0][s], c0);
+      c1 = mfma16(pr[s], vv[1][s], c1);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -498,7 +470,7 @@ size_t tat_fused_lds(int NP) {
 // EmbedT LayerNorm backward follows).  Was: ln_bwd, dctx GEMM, tat_bwd_mfma, dE GEMM, transpose.
 // Saved for the weight gradients (issued after it): dU (fc) and dqkv (Q|K|V); the LayerNorm's
 // gamma / beta as one partial row per workgroup; the broadcast res_att gradient sum_f dS folded
-// in-kernel (fixed chunk order, tat_bwd_mfma's ticket hand-off).
+// in-kernel (fixed chunk order, the ticket hand-off of handoff.hpp).
 // LDS (floats): DUs [48][NP+4] | Qs [48][292] u, then the gamma / beta wave partials, then Q|K|V,
 // then dQ|dK|dV | Cs [48][100] dctx | TRs [W][16][17] | DSs [PW h T^2] dS (+ one int)
 // =====================================================================================
@@ -789,14 +761,14 @@ __global__ __launch_bounds__(64 * W, 1) void tat_fused_bwd_kernel(TatFusedBwdArg
       }
     }
     floatx4 dA = {0.f, 0.f, 0.f, 0.f};
-    dA = mf16(d0.x, v0.x, dA);
-    dA = mf16(d0.y, v0.y, dA);
-    dA = mf16(d0.z, v0.z, dA);
-    dA = mf16(d0.w, v0.w, dA);
-    dA = mf16(d1.x, v1.x, dA);
-    dA = mf16(d1.y, v1.y, dA);
-    dA = mf16(d1.z, v1.z, dA);
-    dA = mf16(d1.w, v1.w, dA);
+    dA = mfma16(d0.x, v0.x, dA);
+    dA = mfma16(d0.y, v0.y, dA);
+    dA = mfma16(d0.z, v0.z, dA);
+    dA = mfma16(d0.w, v0.w, dA);
+    dA = mfma16(d1.x, v1.x, dA);
+    dA = mfma16(d1.y, v1.y, dA);
+    dA = mfma16(d1.z, v1.z, dA);
+    dA = mfma16(d1.w, v1.w, dA);
     float cs = 0.f;
 #pragma unroll
     for (int r = 0; r < 4; ++r) cs = fmaf(at[k][r], dA[r], cs);
@@ -814,22 +786,22 @@ __global__ __launch_bounds__(64 * W, 1) void tat_fused_bwd_kernel(TatFusedBwdArg
     floatx4 gv0 = z, gv1 = z, gk0 = z, gk1 = z, gq0 = z, gq1 = z;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      gv0 = mf16(at[k][s], cb[0][s], gv0);
-      gv1 = mf16(at[k][s], cb[1][s], gv1);
-      gk0 = mf16(ds[s], qb[0][s], gk0);
-      gk1 = mf16(ds[s], qb[1][s], gk1);
+      gv0 = mfma16(at[k][s], cb[0][s], gv0);
+      gv1 = mfma16(at[k][s], cb[1][s], gv1);
+      gk0 = mfma16(ds[s], qb[0][s], gk0);
+      gk1 = mfma16(ds[s], qb[1][s], gk1);
     }
     float* tr = TRs + w * 16 * 17;
 #pragma unroll
     for (int r = 0; r < 4; ++r) tr[(4 * q + r) * 17 + c] = ds[r];
-    tf_wave_sync();
+    wave_lds_sync();
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       const float xv = tr[c * 17 + 4 * q + s];
-      gq0 = mf16(xv, kb[0][s], gq0);
-      gq1 = mf16(xv, kb[1][s], gq1);
+      gq0 = mfma16(xv, kb[0][s], gq0);
+      gq1 = mfma16(xv, kb[1][s], gq1);
     }
-    tf_wave_sync();  // (every lane's Q/K/V reads of this task precede the in-place writes below)
+    wave_lds_sync();  // (every lane's Q/K/V reads of this task precede the in-place writes below)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int ii = 4 * q + r;
@@ -917,8 +889,8 @@ __global__ __launch_bounds__(64 * W, 1) void tat_fused_bwd_kernel(TatFusedBwdArg
     const int n = tid + NTH * j;
     if (n < N) {
       if (lnf) {
-        tf_st_agent(a.gpart + (int64_t)blockIdx.x * N + n, gsum[j]);
-        tf_st_agent(a.bpart + (int64_t)blockIdx.x * N + n, bsum[j]);
+        st_agent(a.gpart + (int64_t)blockIdx.x * N + n, gsum[j]);
+        st_agent(a.bpart + (int64_t)blockIdx.x * N + n, bsum[j]);
       } else {
         if (a.gpart) a.gpart[(int64_t)blockIdx.x * N + n] = gsum[j];
         if (a.bpart) a.bpart[(int64_t)blockIdx.x * N + n] = bsum[j];
@@ -933,14 +905,14 @@ __global__ __launch_bounds__(64 * W, 1) void tat_fused_bwd_kernel(TatFusedBwdArg
     for (int e = tid; e < kTfH * T * T; e += NTH) {
       float v = 0.f;
       for (int p = 0; p < PW; ++p) v += DSs[p * kTfH * T * T + e];  // problems in order
-      tf_st_agent(a.dpart + (bwg * nch + chw) * kTfH * T * T + e, v);
+      st_agent(a.dpart + (bwg * nch + chw) * kTfH * T * T + e, v);
     }
   }
   TF_MARK(9);
   TF_PRINT("tat_fused_bwd", 10);
 
-  // ---- F. ticket folds (the partials above went out with agent-scope stores; the last arrival
-  // takes an agent acquire and sums in a fixed order: deterministic) ---------------------------
+  // ---- F. ticket folds (handoff.hpp: the partials above went out with agent-scope stores; the
+  // last arrival takes an agent acquire and sums in a fixed order: deterministic) --------------
   //   res_att (broadcast): the last workgroup of each sample b sums its nch chunks;
   //   LayerNorm gamma / beta: the last of each group of kTfG1 workgroups sums the group's rows
   //   into a level-2 row, the last group sums the level-2 rows into the parameter gradients
@@ -950,17 +922,16 @@ __global__ __launch_bounds__(64 * W, 1) void tat_fused_bwd_kernel(TatFusedBwdArg
   const int nwg = (int)gridDim.x, ng = (nwg + kTfG1 - 1) / kTfG1, g1 = (int)blockIdx.x / kTfG1;
   const int gsz = min(kTfG1, nwg - g1 * kTfG1);
   int* cnt_ln = a.cnt + a.B;  // [ng] level-1 tickets, then one level-2 ticket
+  // the res_att ticket and the level-1 LayerNorm ticket drawn together: last_arrival's steps with
+  // two draws behind one drain and ONE acquire
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (tid == 0) {
-    const int lb = a.res_mode == DSTAGNN_RES_BCAST && atomicAdd(a.cnt + bwg, 1) == nch - 1;
-    const int lg = lnf && atomicAdd(cnt_ln + g1, 1) == gsz - 1;
-    if (lb || lg) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    if (lb) __hip_atomic_store(a.cnt + bwg, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
-    if (lg) __hip_atomic_store(cnt_ln + g1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool lb = a.res_mode == DSTAGNN_RES_BCAST && ticket_draw(a.cnt + bwg, nch);
+    const bool lg = lnf && ticket_draw(cnt_ln + g1, gsz);
+    if (lb || lg) ticket_acquire();
+    if (lb) ticket_rearm(a.cnt + bwg);
+    if (lg) ticket_rearm(cnt_ln + g1);
     flag[0] = lb;
     flag[1] = lg;
   }
@@ -969,7 +940,7 @@ __global__ __launch_bounds__(64 * W, 1) void tat_fused_bwd_kernel(TatFusedBwdArg
   if (lb) {
     for (int e = tid; e < kTfH * T * T; e += NTH) {
       float v = 0.f;
-      for (int ch = 0; ch < nch; ++ch) v += tf_ld_agent(a.dpart + (bwg * nch + ch) * kTfH * T * T + e);
+      for (int ch = 0; ch < nch; ++ch) v += ld_agent(a.dpart + (bwg * nch + ch) * kTfH * T * T + e);
       a.dres[bwg * kTfH * T * T + e] = v;
     }
   }
@@ -979,41 +950,14 @@ __global__ __launch_bounds__(64 * W, 1) void tat_fused_bwd_kernel(TatFusedBwdArg
   for (int e = tid; e < 2 * N; e += NTH) {  // (column, gamma | beta): the group's rows in order
     const int n = e % N, wh = e / N;
     const float* src = (wh ? a.bpart : a.gpart) + (int64_t)g1 * kTfG1 * N + n;
-    float u[kTfG1];
-#pragma unroll
-    for (int k = 0; k < kTfG1; ++k) u[k] = k < gsz ? tf_ld_agent(src + (int64_t)k * N) : 0.f;
-    float v = 0.f;
-#pragma unroll
-    for (int k = 0; k < kTfG1; ++k) v += u[k];
-    tf_st_agent((wh ? l2b : l2g) + (int64_t)g1 * N + n, v);
+    st_agent((wh ? l2b : l2g) + (int64_t)g1 * N + n, sum_rows_agent<kTfG1>(src, N, gsz));
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    const int last2 = atomicAdd(cnt_ln + ng, 1) == ng - 1;
-    if (last2) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(cnt_ln + ng, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    flag[2] = last2;
-  }
-  __syncthreads();
-  if (!flag[2]) return;
+  if (!last_arrival(cnt_ln + ng, ng, flag + 2)) return;
   for (int e = tid; e < 2 * N; e += NTH) {
     const int n = e % N, wh = e / N;
     float* out = wh ? a.bout : a.gout;
     if (!out) continue;
-    const float* src = (wh ? l2b : l2g) + n;
-    float v = 0.f;
-    for (int k0 = 0; k0 < ng; k0 += kTfG1) {
-      float u[kTfG1];
-#pragma unroll
-      for (int k = 0; k < kTfG1; ++k) u[k] = k0 + k < ng ? tf_ld_agent(src + (int64_t)(k0 + k) * N) : 0.f;
-#pragma unroll
-      for (int k = 0; k < kTfG1; ++k) v += u[k];
-    }
-    out[n] = v;
+    out[n] = sum_rows_agent<kTfG1>((wh ? l2b : l2g) + n, N, ng);
   }
 }
 

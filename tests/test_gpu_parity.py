@@ -385,6 +385,9 @@ CONFIGS = {
     "t16h3": (40, 16, 3, 3, 64, 32, 32),
     "n320": (320, 12, 3, 3, 64, 32, 32),
     "n101": (101, 12, 3, 3, 64, 32, 32),
+    # the smallest geometry at which, with B = 141, both fused backward kernels run every branch of
+    # their two-level ticket trees (TAT_FUSED_CASES; tests/test_gpu_handoff.py)
+    "n40": (40, 12, 3, 3, 64, 32, 32),
     # an odd number of 32-node strips (5): the two-strip small-graph dQ'/dK' kernel's last pair
     # holds one strip (its second pair of waves idle), with N <= 192 so that kernel runs
     "n150": (150, 12, 3, 3, 64, 32, 32),
@@ -634,7 +637,16 @@ TAT_FUSED_CASES = [  # (name, first, res_kind, B, train, fused forward, fused ba
     # T = 12 at the LDS bound N = 320 and at an odd N (scalar row loads, partial node tile)
     ("n320", False, 1, 2, False, True, True), ("n320", True, 0, 2, True, True, True),
     ("n101", False, 1, 2, False, True, True), ("n101", False, 2, 2, True, True, True),
-    ("n101", True, 0, 3, False, True, True)]
+    ("n101", True, 0, 3, False, True, True),
+    # both in-kernel fold trees with more than 16 level-2 rows and a ragged last group (PEMS08 at
+    # B = 32 has exactly 16 rows in each, the small cases one or two groups).  B N = 5640: the fused
+    # GTU backward runs 257 workgroups of 22 nodes = 17 level-1 groups, the last of ONE workgroup,
+    # and its level 2 sums 17 rows (two chunks of 16).  B F T = 54 144: the fused TAt backward runs
+    # 1128 workgroups, 8 res_att chunks per sample, 71 level-1 groups, the last of 8, five level-2
+    # chunks.
+    ("n40", False, 1, 141, False, True, True), ("n40", False, 1, 141, True, True, True)]
+# further paths a geometry's comment names, asserted with the fused TAt ones
+TAT_FUSED_MUST = {"n40": {"gtu_fused_bwd"}}
 
 
 @pytest.mark.parametrize("name,first,res_kind,B,train,fwd,bwd", TAT_FUSED_CASES)
@@ -643,7 +655,7 @@ def test_tat_fused_variants_vs_oracle(name, first, res_kind, B, train, fwd, bwd)
     (tat_fused_fwd_ok: h = 3, d_k = 32, T in {8, 12, 16}, N <= 320) held to the fp64 oracle,
     first and inner block, eval and train, with the path asserted (block_fn.block_paths)."""
     _need_gpu()
-    must = ({TF_FWD} if fwd else set()) | ({TF_BWD} if bwd else set())
+    must = ({TF_FWD} if fwd else set()) | ({TF_BWD} if bwd else set()) | TAT_FUSED_MUST.get(name, set())
     must_not = set() if bwd else {TF_BWD}
     flips = _run_config_vs_oracle(name, first, B, train=train, res_kind=res_kind, paths=(must, must_not))
     print(f"{name} first={first} res={res_kind} B={B} train={train}: {flips} ReLU decision(s) within rounding of 0")
