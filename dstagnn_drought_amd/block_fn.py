@@ -162,7 +162,7 @@ def dropout_masks(meta, x_shape, seed, sample_base=0):
 
 # dstagnn_block_paths bits (include/dstagnn.h DSTAGNN_PATH_*)
 PATH_BITS = {"sparse": 1, "flash": 2, "flash_small": 4, "cheb_agg": 8, "tat_fused_fwd": 16, "tat_fused_bwd": 32,
-             "gtu_fused_fwd": 64, "gtu_fused_bwd": 128, "sat_ln_fused": 256}
+             "gtu_fused_fwd": 64, "gtu_fused_bwd": 128}
 
 
 def _explicit_args(blk, x, res_att, train=False, seed=0, poison=False):

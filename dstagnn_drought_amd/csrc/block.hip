@@ -56,7 +56,6 @@ struct Dims {
   bool tfused_bwd;  // ... and its backward (tat_fused.hip)
   bool gfused;      // the GTU stage forward as one kernel (gtu_fused.hip)
   bool gbfused;     // ... and its backward (gtu_fused.hip): compact gate-gradient rows, no tconv
-  bool sfused;      // the SAt projection backward + EmbedS LN backward as one kernel (sat_fused.hip)
   int64_t tf_wg;    // tfused_bwd: its workgroups (one gamma / beta partial row each)
   int64_t nnz;      // flash: union-support entries
   int64_t apa_nnz;  // small-graph flash: A_pa support entries
@@ -84,7 +83,6 @@ Dims mkdims(const dstagnn_block_dims& d) {
   m.tf_wg = m.tfused_bwd ? tat_fused_bwd_wgs(m.BFT) : 0;
   m.gfused = gtu_fused_fwd_ok(m.C, m.T);
   m.gbfused = gtu_fused_bwd_ok(m.C, m.T);
-  m.sfused = sat_ln_bwd_fused_ok(m.D, 2 * m.KD);
   return m;
 }
 
@@ -96,7 +94,6 @@ struct SaveBufs {
   float* Wqkv_p;  // tfused: [Wq; Wk; Wv] with rows zero-padded to NP
   float *WfcT, *WqT;  // tfused_bwd: W_fc^T (h dv, NP) and [Wq; Wk; Wv]^T (NP, 3 h dk), zero-padded
   float* Wgt[3];      // gfused: GTU weights (o, j, c) for the fused GTU forward
-  float* WqkT;        // sfused: [W_Q'; W_K']^T (D, 2 KD)
   float *E, *qkv, *att, *ctx, *u_tat, *mu_tat, *rs_tat, *O, *u_s, *mu_s, *rs_s, *Zd, *qk, *P, *W, *xth, *X;
   float *lse, *psupp, *wsupp;  // flash path: column log-sum-exp (B,K,N), P and T o P on the support (B,K,nnz)
   float *am, *amt, *papa;      // small-graph flash: A_pa o M_k (K,N,N) and its transpose, P on the A_pa support
@@ -111,7 +108,6 @@ SaveBufs plan_save(const Dims& m, Arena& a) {
   s.WfcT = m.tfused_bwd ? a.take(m.HV * m.NP) : nullptr;
   s.WqT = m.tfused_bwd ? a.take(m.QW * m.NP) : nullptr;
   for (int g = 0; g < 3; ++g) s.Wgt[g] = m.gfused ? a.take(2 * (int64_t)m.C * m.C * m.ks[g]) : nullptr;
-  s.WqkT = m.sfused ? a.take((int64_t)m.D * 2 * m.KD) : nullptr;
   s.Wqk = a.take(2 * m.KD * m.D);
   s.Wp = a.take((int64_t)m.D * m.FT);
   s.thcat = a.take((int64_t)m.F * m.KC);
@@ -683,10 +679,6 @@ struct Fwd {
     }
     add(0, p.sat_wq, s.Wqk, m.KD * m.D, 0, 0, 0, 0);
     add(0, p.sat_wk, s.Wqk, m.KD * m.D, 0, 0, 0, m.KD * m.D);
-    if (m.sfused && !lean) {  // [W_Q'; W_K']^T (D, 2 KD): WqkT[d][k] = W[k][d]
-      add(9, p.sat_wq, s.WqkT, m.D * m.KD, (int)m.KD, m.D, (int)(2 * m.KD), 0).p3 = (int)m.KD;
-      add(9, p.sat_wk, s.WqkT, m.D * m.KD, (int)m.KD, m.D, (int)(2 * m.KD), m.KD).p3 = (int)m.KD;
-    }
     add(1, p.pre_conv_w, s.Wp, (int64_t)m.D * m.FT, m.F, m.T);  // Wp[d][f][t] = W[d][t][0][f]
     for (int k = 0; k < m.K; ++k) add(2, p.theta[k], s.thcat, (int64_t)m.F * m.C, m.C, (int)m.KC, k);
     for (int g = 0; g < 3; ++g) {
@@ -770,15 +762,6 @@ struct Fwd {
     return g;
   }
 
-  // DSTAGNN_GTU_GCONV=1: the forward convolutions by the sliding-window kernel instead of the
-  // grouped implicit-im2col GEMM.  Opt-in: 45.2 vs 39.6 us serialised at PEMS08 (0.711 vs
-  // 0.701 ms/step same box) — with only k x 16 MFMAs per wave the window staging and weight
-  // loads are not amortised, while the GEMM's DMA pipeline overlaps them
-  static bool gconv_on() {
-    static const bool on = env_flag("DSTAGNN_GTU_GCONV", false);
-    return on;
-  }
-
   int stage_tail() {
     if (m.gfused) {  // convolutions + gates + fcmy + residual + LN in one kernel (gtu_fused.hip)
       GtuFusedArgs g;
@@ -792,17 +775,8 @@ struct Fwd {
       return op_gtu_fused_fwd(g, st);
     }
     // the three independent convolutions (kernel widths 3, 5, 7) as ONE grouped launch
-    if (gconv_on() && gtu_conv_fwd_ok(m.C, m.T, m.ks, 3)) {  // sliding-window kernel (gtu_tconv.hip)
-      GconvArgs gc{};
-      gc.X = s.X; gc.BN = m.BN; gc.T = m.T;
-      for (int q = 0; q < 3; ++q) {
-        gc.wf[q] = s.Wgf[q]; gc.bias[q] = p.gtu_b[q]; gc.conv[q] = s.conv[q]; gc.ks[q] = m.ks[q];
-      }
-      DS_TRY(op_gtu_conv_fwd(gc, st));
-    } else {
-      const Gemm convs[3] = {gtu_conv(0), gtu_conv(1), gtu_conv(2)};
-      DS_TRY(run_gemm_group(convs, 3, w.gemm_ws, kGemmWs, st));
-    }
+    const Gemm convs[3] = {gtu_conv(0), gtu_conv(1), gtu_conv(2)};
+    DS_TRY(run_gemm_group(convs, 3, w.gemm_ws, kGemmWs, st));
     GtuTailArgs t;  // gates + fcmy + dropout + residual + LN, one workgroup per node
     t.BN = m.BN; t.C = m.C; t.T = m.T; t.first = m.first;
     for (int q = 0; q < 3; ++q) t.conv[q] = s.conv[q];
@@ -1225,18 +1199,7 @@ struct Bwd {
       g.alpha = sc;
       DS_TRY(gemm(g));
     }
-    int64_t ln_rows = ln_bwd_partials_ok(m.D) ? ln_bwd_part_blocks(m.BN) : m.BN;  // partial rows
-    if (m.sfused) {  // dZd GEMM + EmbedS LN backward in one kernel (sat_fused.hip): dZd never written
-      SatLnBwdArgs a;
-      a.R = m.BN; a.D = m.D; a.K2 = ld;
-      a.dqk = w.dqk; a.wT = s.WqkT;
-      a.u = s.u_s; a.mu = s.mu_s; a.rs = s.rs_s; a.g = p.embS_g;
-      if (d.train && d.drop_p > 0.f) { a.drop_p = d.drop_p; a.seed = d.seed; a.drop_off = drop_off(d, 0); }
-      a.dx = w.dY;
-      a.gpart = w.gcon_s; a.bpart = w.bcon_s; a.xpart = preconv_bias_part();
-      DS_TRY(op_sat_ln_bwd_fused(a, st));
-      ln_rows = sat_ln_bwd_fused_wgs(m.BN);
-    } else {
+    const int64_t ln_rows = ln_bwd_partials_ok(m.D) ? ln_bwd_part_blocks(m.BN) : m.BN;  // partial rows
     {
       Gemm g;  // dZd = dqk [W_Q'; W_K']
       g.M = (int)m.BN; g.N = m.D; g.K = (int)ld;
@@ -1261,7 +1224,6 @@ struct Bwd {
         a.gcontrib = w.gcon_s; a.bcontrib = w.bcon_s;
       }
       DS_TRY(op_ln_bwd(a, st));
-    }
     }
     // --- side: SAt projection, EmbedS gamma / beta / pos-embedding, pre_conv bias and weight
     // grads; the fork's flag rides on the pre_conv data-gradient GEMM
@@ -1295,7 +1257,7 @@ struct Bwd {
                    ln_rows, m.D, 1));
     if (!xpart) DS_TRY(colsum_on(ks.side(), w.dY, m.BN, m.D, 1, gd.pre_conv_b));
     if (gd.embS_pos) DS_TRY(op_sum_middle(w.dY, 1, m.B, (int64_t)m.N * m.D, gd.embS_pos, 0.f, ks.side()));
-    if (gd.pre_conv_w && !dwp_main()) DS_TRY(sgemm(dwp_gemm()));
+    if (gd.pre_conv_w) DS_TRY(sgemm(dwp_gemm()));
     return 0;
   }
 
@@ -1307,12 +1269,6 @@ struct Bwd {
     // written straight into pre_conv.weight's [d][t][0][f] layout: n = f*T + t
     g.C = gd.pre_conv_w; g.cm = idx1(m.FT); g.cn = idx2(m.T, m.F, 1);
     return g;
-  }
-  // DSTAGNN_DWP_MAIN=1: the pre_conv weight gradient as the main stream's last product instead of
-  // the side stream's (stream balance A/B: the side stream's tail sets the step's end)
-  static bool dwp_main() {
-    static const bool on = env_flag("DSTAGNN_DWP_MAIN", false);
-    return on;
   }
 
   int stage_preconv(ForkSig* sig) {
@@ -1328,17 +1284,16 @@ struct Bwd {
   // backward, dE accumulated into dx (inner block) or written for the EmbedT backward (first)
   int stage_tat_fused() {
     const int64_t N = m.N;
-    const bool side_any = tatln_side() || (gd.tat_fc && fc_side());
     if (!m.first) DS_TRY(wait_side(dx_ready));  // dx += the Chebyshev-path gradient (side stream) first
     TatFusedBwdArgs t;
     t.dO = w.dO; t.u = s.u_tat; t.mu = s.mu_tat; t.rs = s.rs_tat; t.g = p.tat_ln_g;
     // gamma / beta: the kernel's two-level ticket tree sums its partial rows (level-2 rows after
-    // them in the same slabs); TATLN_SIDE keeps the column-sum launch on the side stream (A/B)
+    // them in the same slabs)
     t.gpart = w.gcon_a; t.bpart = w.gcon_a + tat_bslab() * N;
 #ifdef DSTAGNN_RACEBUG_NOFORK
     t.ln_fold = 0;  // (the racy build's side-stream column sums must be the only writer)
 #else
-    t.ln_fold = !tatln_side();
+    t.ln_fold = 1;
 #endif
     t.gout = gd.tat_ln_g; t.bout = gd.tat_ln_b;
     t.dU = w.dU; t.wfcT = s.WfcT;
@@ -1356,13 +1311,6 @@ struct Bwd {
     t.F = m.F; t.T = m.T; t.N = m.N; t.NP = m.NP; t.h = m.h;
     t.scale = 1.f / sqrtf((float)m.dk);
     DS_TRY(op_tat_fused_bwd(t, st));
-    if (side_any) {
-      // (A/B knobs only) the side work reads this kernel's outputs (dU, dqkv, the LN partial
-      // rows): a fork AFTER it — a flag carried at a kernel's start would let them race
-      DS_TRY(fork());
-      if (tatln_side()) DS_TRY(tat_ln_colsums(false));
-      if (gd.tat_fc && fc_side()) DS_TRY(sgemm(fc_grad_gemm()));
-    }
     return m.first ? embedT_backward() : 0;
   }
 
@@ -1416,42 +1364,17 @@ struct Bwd {
     float* dsc = (d.res_mode == DSTAGNN_RES_FULL && dres) ? dres : w.dscore;
     float* dsum = (d.res_mode == DSTAGNN_RES_BCAST && dres) ? dres : nullptr;
     DS_TRY(op_tat_bwd(m.B, m.F, m.T, m.h, m.dk, m.dv, s.qkv, s.att, w.dctx, dre, w.dqkv, dsc, dsum, st));
-    // --- side (A/B knobs only): TAt LN gamma / beta and fc weight grads, one fork before the
-    // dE GEMM
-    const bool side_any = tatln_side() || (gd.tat_fc && fc_side());
-    auto side_work = [&]() -> int {
-      if (tatln_side()) DS_TRY(tat_ln_colsums(false));
-      if (gd.tat_fc && fc_side()) DS_TRY(sgemm(fc_grad_gemm()));
-      return 0;
-    };
     {  // dE = dU + dqkv [Wq; Wk; Wv]
       Gemm g;
       g.M = (int)m.BFT; g.N = m.N; g.K = (int)m.QW;
       g.A = w.dqkv; g.am = idx1(m.QW); g.ak = idx1(1);
       g.B = s.Wqkv; g.bk = idx1(N); g.bn = idx1(1);
-      // dU is only read (the side stream's fc weight grad also reads it): beta input C = dU
+      // dU is only read (the fc weight grad at the step's end also reads it): beta input C = dU
       g.C = w.dU; g.cm = idx1(N); g.cn = idx1(1);
       g.beta = 1.f;
-      if (m.first) {
-        g.Cout = w.dE;  // -> the EmbedT LayerNorm backward
-      } else if (dE_omap() && m.FT % 32 == 0) {
-        // inner block: E is x transposed, so dE accumulates straight into dx (B,N,F,T) through
-        // the output map (row (b, ft), column n -> b N FT + n FT + ft) once the side stream's
-        // Chebyshev-path gradient is in dx.  The main stream waits for the side before the
-        // GEMM, which no fork_on scope may do: a plain fork, its flag written ahead of the wait
-        if (side_any) DS_TRY(fork());
-        DS_TRY(wait_side(dx_ready));
-        g.Cout = dx; g.omap = true; g.obeta = 1.f;
-        g.om = idx2(m.FT, 1, N * m.FT); g.on = idx1(m.FT);
-        DS_TRY(gemm(g));
-        return side_work();
-      } else {
-        g.Cout = w.dE;
-      }
-      if (side_any) DS_TRY(ks.fork_on([&](ForkSig* sig) { return gemm(g, sig); }));  // the flag rides on the GEMM
-      else DS_TRY(gemm(g));
+      g.Cout = w.dE;  // first block: -> the EmbedT LayerNorm backward; inner: transposed into dx
+      DS_TRY(gemm(g));
     }
-    DS_TRY(side_work());
     // dE -> dx
     if (m.first) {
       DS_TRY(embedT_backward());
@@ -1469,33 +1392,15 @@ struct Bwd {
     return on;
   }
 
-  // DSTAGNN_DE_OMAP=1: the inner block's dE accumulated straight into dx by the GEMM's output
-  // map instead of a dE buffer + transpose_kernel.  Opt-in: measured 0.718 vs 0.711 ms/step
-  // (same box, 2 x 100 steps each) — the strided epilogue of that GEMM on the critical path
-  // costs more than the transpose launch it saves.
-  static bool dE_omap() {
-    static const bool on = env_flag("DSTAGNN_DE_OMAP", false);
-    return on;
-  }
-
   // [dWq; dWk; dWv] = dqkv^T E — the last product of the backward, issued on the main
   // stream after dx: the side stream is still busy with the earlier parameter gradients
   // (pre_conv, SAt), while the main chain has nothing left (measured: the side stream's tail
-  // was the step's critical path); see tat_wqkv_grad
-  // the TAt fc weight gradient on the side stream (DSTAGNN_FC_SIDE=1) or, by default, on the
-  // main stream with the Q|K|V weight gradient as one grouped launch at the step's end: with the
-  // main chain's fork flags kernel-written the side stream's tail set the step (two-stream
-  // timeline: main ended ~48 us before the side)
-  static bool fc_side() {
-    static const bool on = env_flag("DSTAGNN_FC_SIDE", false);
-    return on;
-  }
-  // the TAt LayerNorm gamma / beta column sums: likewise on the main stream at the end by default
-  // (then the TAt stage forks nothing: no side-stream wait at the step's end); DSTAGNN_TATLN_SIDE=1
-  static bool tatln_side() {
-    static const bool on = env_flag("DSTAGNN_TATLN_SIDE", false);
-    return on;
-  }
+  // was the step's critical path); see tat_wqkv_grad.  The TAt fc weight gradient rides with it
+  // as one grouped launch: with the main chain's fork flags kernel-written the side stream's
+  // tail set the step (two-stream timeline: main ended ~48 us before the side).  The TAt
+  // LayerNorm gamma / beta column sums are likewise on the main stream at the end, so the TAt
+  // stage forks nothing (no side-stream wait at the step's end)
+
   // fused TAt backward: the beta slab's first row (gamma: level-1 rows, then the ticket tree's level-2 rows)
   int64_t tat_bslab() const { return tat_fused_bwd_part_rows(m.BFT); }  // the gamma slab's rows (tat_fused.hip)
   int tat_ln_colsums(bool on_main) {
@@ -1516,7 +1421,7 @@ struct Bwd {
     return g;
   }
   int tat_wqkv_grad() {
-    const bool fc_here = !fc_side() && gd.tat_fc;
+    const bool fc_here = gd.tat_fc != nullptr;
     if (!(gd.tat_wq || gd.tat_wk || gd.tat_wv)) return fc_here ? gemm(fc_grad_gemm()) : 0;
     const int64_t N = m.N;
     Gemm g;
@@ -1567,14 +1472,13 @@ struct Bwd {
     DS_TRY(ks.order_err);
     ht.lap("tat");
     DS_TRY(tat_wqkv_grad());  // (+ the fc weight gradient)
-    if (gd.pre_conv_w && dwp_main()) DS_TRY(gemm(dwp_gemm()));
 #ifdef DSTAGNN_RACEBUG_NOFORK
     // deliberately racy build (make racebug -> abtest/racebug; tests/test_gpu_knobs.py::
     // test_race_probe_catches_a_missing_fork): the TAt LayerNorm column sums on the side stream
     // WITHOUT a fork after the LayerNorm backward that writes their partials
     DS_TRY(tat_ln_colsums(false));
 #else
-    if (!tatln_side() && !m.tfused_bwd) DS_TRY(tat_ln_colsums(true));  // (fused: summed in-kernel)
+    if (!m.tfused_bwd) DS_TRY(tat_ln_colsums(true));  // (fused: summed in-kernel)
 #endif
     DS_TRY(ks.order_err);
     DS_TRY(join());
@@ -1654,8 +1558,7 @@ int dstagnn_block_paths(const dstagnn_block_dims* d, uint32_t* bits) {
   *bits = (m.sparse ? DSTAGNN_PATH_SPARSE : 0u) | (m.flash ? DSTAGNN_PATH_FLASH : 0u) |
           (m.fsmall ? DSTAGNN_PATH_FLASH_SMALL : 0u) | (m.agg ? DSTAGNN_PATH_CHEB_AGG : 0u) |
           (m.tfused ? DSTAGNN_PATH_TAT_FUSED_FWD : 0u) | (m.tfused_bwd ? DSTAGNN_PATH_TAT_FUSED_BWD : 0u) |
-          (m.gfused ? DSTAGNN_PATH_GTU_FUSED_FWD : 0u) | (m.gbfused ? DSTAGNN_PATH_GTU_FUSED_BWD : 0u) |
-          (m.sfused ? DSTAGNN_PATH_SAT_LN_FUSED : 0u);
+          (m.gfused ? DSTAGNN_PATH_GTU_FUSED_FWD : 0u) | (m.gbfused ? DSTAGNN_PATH_GTU_FUSED_BWD : 0u);
   return 0;
 }
 

@@ -18,8 +18,6 @@
 // apart, so the 64 lanes of an A-fragment read hit 64 distinct banks with the 65-float rows) —
 // the same products as the K-concatenated GEMM, summed in this fixed order.
 // The weight fragments (≤ 57 KB per GTU, L2-resident) come from global memory one tap ahead.
-#include <algorithm>
-
 #include "common.hpp"
 #include "ops.hpp"
 
@@ -128,130 +126,7 @@ __global__ __launch_bounds__(256) void gtu_tconv_kernel(TconvArgs a) {
   }
 }
 
-// ---------------------------------------------------------------------------------------
-// Forward: the three GTU convolutions (model/DSTAGNN_my.py:190, Conv2d(C, 2C, (1, k))) by the
-// same sliding window.  Output row m = (bn, t') of GTU q (t' < Tg = T - k + 1) reads the X rows
-// (bn, t' + j), j < k — in X's (BN, T, C) layout the rows bn T + t' + j.  A 64-row output tile
-// of one GTU needs the X rows from in(m0) to in(m0 + 63) + k - 1 (in(m) = (m / Tg) T + m % Tg):
-// ONE contiguous range (a node's last rows are followed by the next node's first), staged once
-// into LDS; the A fragment of tap j for row m is staged row in(m) - in(m0) + j.  Wave w owns
-// rows 32 (w & 1) and output channels 32 (w >> 1) of the tile; step s of tap j contracts
-// c = s + 16h (the halves read columns 16 apart: fewer bank conflicts than c = 2s + h).  Output: conv_q[m][o] = bias[o] + sum.
-// ---------------------------------------------------------------------------------------
-constexpr int kGcBM = 64, kGcRowsMax = 320, kGcRow = kTcC + 1;
-constexpr int kGcStageF4 = kGcRowsMax * kTcC / 4 / 256;  // float4 loads per thread (10)
-
-__global__ __launch_bounds__(256) void gtu_conv_fwd_kernel(GconvArgs a) {
-  extern __shared__ float Xs[];  // [rows][kGcRow], rows <= the launch's bound (gconv_rows_max)
-  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, h = lane >> 5, l32 = lane & 31;
-  const int b = (int)blockIdx.x;
-  const int q = b >= a.start[2] ? 2 : (b >= a.start[1] ? 1 : 0);
-  const int ks = a.ks[q], Tg = a.Tg[q], T = a.T;
-  const int64_t Mq = a.BN * Tg;
-  const int64_t m0 = (int64_t)(b - a.start[q]) * kGcBM;
-  const int64_t mlast = min(m0 + kGcBM, Mq) - 1;
-  auto in_row = [&](int64_t m) -> int64_t { const int64_t bn = m / Tg; return bn * T + (m - bn * Tg); };
-  const int64_t r0 = in_row(m0);
-  const int rows = (int)(in_row(mlast) - r0) + ks;  // <= kGcRowsMax (host-checked)
-  const float* src = a.X + r0 * kTcC;
-  float4 v[kGcStageF4];
-#pragma unroll
-  for (int u = 0; u < kGcStageF4; ++u) {
-    const int e4 = tid + 256 * u, row = e4 >> 3;
-    v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (row < rows) v[u] = *reinterpret_cast<const float4*>(src + (int64_t)e4 * 4);
-  }
-  // this lane's output row / channel and its first tap's weight fragments
-  const int64_t m = min(m0 + 32 * (w & 1) + l32, mlast);
-  const int ar = (int)(in_row(m) - r0);
-  const int o = 32 * (w >> 1) + l32;
-  const float* wo = a.wf[q] + o;  // (j, c, o): B[kk = j C + c][n = o], lanes along o (coalesced)
-  float bc[16];
-#pragma unroll
-  for (int s = 0; s < 16; ++s) bc[s] = wo[(s + 16 * h) * (2 * kTcC)];
-#pragma unroll
-  for (int u = 0; u < kGcStageF4; ++u) {
-    const int e4 = tid + 256 * u, row = e4 >> 3, c = (e4 & 7) * 4;
-    if (row < rows) {
-      float* d = Xs + row * kGcRow + c;
-      d[0] = v[u].x; d[1] = v[u].y; d[2] = v[u].z; d[3] = v[u].w;
-    }
-  }
-  __syncthreads();
-  floatx16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  for (int j = 0; j < ks; ++j) {
-    float bn[16];
-    if (j + 1 < ks) {
-#pragma unroll
-      for (int s = 0; s < 16; ++s) bn[s] = wo[((j + 1) * kTcC + s + 16 * h) * (2 * kTcC)];
-    }
-    const float* xr = Xs + (ar + j) * kGcRow + 16 * h;
-#pragma unroll
-    for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xr[s], bc[s], acc, 0, 0, 0);
-    if (j + 1 < ks) {
-#pragma unroll
-      for (int s = 0; s < 16; ++s) bc[s] = bn[s];
-    }
-  }
-  // D[m = row frow(r, h)][n = channel l32] of the wave's 32 x 32 block
-  const int on = 32 * (w >> 1) + l32;
-  const float bias = a.bias[q] ? a.bias[q][on] : 0.f;
-  float* out = a.conv[q];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t mr = m0 + 32 * (w & 1) + tc_frow(r, h);
-    if (mr < Mq) out[mr * (2 * kTcC) + on] = acc[r] + bias;
-  }
-}
-
 }  // namespace
-
-// the largest staged X range of any 64-row tile of GTU width ks (tile rows m0..m0+63)
-static int gconv_rows_max(int T, int Tg, int ks) {
-  return (kGcBM - 1) / Tg * T + std::min(kGcBM - 1, Tg - 1) + ks + T;
-}
-
-bool gtu_conv_fwd_ok(int C, int T, const int* ks, int n) {
-  if (C != kTcC || n != 3) return false;
-  for (int q = 0; q < n; ++q) {
-    const int Tg = T - ks[q] + 1;
-    if (ks[q] < 1 || ks[q] > kTcKmax || Tg < 1 || gconv_rows_max(T, Tg, ks[q]) > kGcRowsMax) return false;
-  }
-  return true;
-}
-
-int op_gtu_conv_fwd(GconvArgs a, hipStream_t st) {
-  if (a.BN <= 0) return 0;
-  if (!gtu_conv_fwd_ok(kTcC, a.T, a.ks, 3)) {
-    set_last_error("gtu_conv_fwd: C = 32, widths 1..7, staged window <= 320 rows");
-    return DSTAGNN_E_SHAPE;
-  }
-  if ((reinterpret_cast<uintptr_t>(a.X) & 15) != 0) {
-    set_last_error("gtu_conv_fwd: X must be 16-B aligned");
-    return DSTAGNN_E_ARG;
-  }
-  double flops = 0, bytes = 4.0 * a.BN * a.T * kTcC;
-  int at = 0;
-  for (int q = 0; q < 3; ++q) {
-    a.Tg[q] = a.T - a.ks[q] + 1;
-    a.start[q] = at;
-    const int64_t Mq = a.BN * a.Tg[q];
-    at += (int)cdiv64(Mq, kGcBM);
-    flops += 2.0 * Mq * (2 * kTcC) * (double)(kTcC * a.ks[q]);
-    bytes += 4.0 * ((double)Mq * 2 * kTcC + 2.0 * kTcC * kTcC * a.ks[q]);
-  }
-  a.start[3] = at;
-  int rmax = 0;
-  for (int q = 0; q < 3; ++q) rmax = std::max(rmax, gconv_rows_max(a.T, a.Tg[q], a.ks[q]));
-  const size_t lds = (size_t)rmax * kGcRow * sizeof(float);  // <= 42 KB
-  void* rec = gemm_prof_begin(flops, bytes, st, DSTAGNN_PROF_GTU_TCONV);
-  hipLaunchKernelGGL(gtu_conv_fwd_kernel, dim3((unsigned)at), dim3(256), lds, st, a);
-  DS_CHECK_LAUNCH();
-  gemm_prof_end(rec, st);
-  return 0;
-}
 
 bool gtu_tconv_ok(int C, const int* ks, int n) {
   if (C != kTcC || n != 3) return false;

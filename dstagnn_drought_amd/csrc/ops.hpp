@@ -253,20 +253,6 @@ struct TconvArgs {
   uint32_t* sig = nullptr; uint32_t sig_v = 0;  // kernel-written stream signal (common.hpp)
 };
 bool gtu_tconv_ok(int C, const int* ks, int n);
-// the three GTU convolutions (forward) by the same sliding window (gtu_tconv.hip)
-struct GconvArgs {
-  const float* X;        // (BN, T, C) Chebyshev output
-  const float* wf[3];    // (ks, C, 2C) re-laid weights (j, c, o)
-  const float* bias[3];  // (2C) or null
-  float* conv[3];        // (BN * Tg, 2C)
-  int ks[3];
-  int Tg[3];             // set by the launcher
-  int start[4];          // first workgroup of each GTU (set by the launcher)
-  int64_t BN;
-  int T;
-};
-bool gtu_conv_fwd_ok(int C, int T, const int* ks, int n);
-int op_gtu_conv_fwd(GconvArgs a, hipStream_t st);
 int op_gtu_tconv(const TconvArgs& a, hipStream_t st, ForkSig* sig = nullptr);
 // the temporal-attention stage as one kernel (tat_fused.hip): Q|K|V projection, attention, fc,
 // residual and the LayerNorm over N; E(R, n) = src[(R % FT) s0 + (R / FT) s1 + n sN]
@@ -327,18 +313,6 @@ struct GtuFusedArgs {
   float* conv[3] = {};             // (BN (T - k + 1), 2C), bias included (saved)
   float *G = nullptr, *tco = nullptr, *r = nullptr, *mu = nullptr, *rs = nullptr, *out = nullptr;
 };
-struct SatLnBwdArgs {  // sat_fused.hip: dZd = dqk [W_Q'; W_K'] + EmbedS LayerNorm(D) backward
-  int64_t R = 0, D = 0, K2 = 0;    // rows B N, d_model, 2 K d_k
-  const float* dqk = nullptr;      // (R, K2)
-  const float* wT = nullptr;       // (D, K2) = [W_Q'; W_K']^T (param_prep kind 9)
-  const float *u = nullptr, *mu = nullptr, *rs = nullptr, *g = nullptr;
-  float drop_p = 0.f; uint64_t seed = 0; uint64_t drop_off = 0;  // the EmbedS dropout (which = 0)
-  float* dx = nullptr;             // dY (R, D)
-  float *gpart = nullptr, *bpart = nullptr, *xpart = nullptr;  // [workgroup][D] partial rows (xpart optional)
-};
-bool sat_ln_bwd_fused_ok(int64_t D, int64_t K2);
-int64_t sat_ln_bwd_fused_wgs(int64_t R);
-int op_sat_ln_bwd_fused(const SatLnBwdArgs& a, hipStream_t st);
 bool gtu_fused_fwd_ok(int C, int T);
 int op_gtu_fused_fwd(const GtuFusedArgs& a, hipStream_t st);
 struct GtuFusedBwdArgs {

@@ -194,7 +194,7 @@ enum {
   DSTAGNN_PATH_TAT_FUSED_BWD = 32,  /* ... and its backward                                      */
   DSTAGNN_PATH_GTU_FUSED_FWD = 64,  /* GTU stage as one kernel (gtu_fused.hip)                   */
   DSTAGNN_PATH_GTU_FUSED_BWD = 128, /* ... and its backward                                      */
-  DSTAGNN_PATH_SAT_LN_FUSED = 256   /* SAt projection bwd + EmbedS LN bwd fused (sat_fused.hip)  */
+  DSTAGNN_PATH_SAT_LN_FUSED = 256   /* retired (that kernel is gone): never reported             */
 };
 int dstagnn_block_paths(const dstagnn_block_dims* d, uint32_t* bits);
 
@@ -416,8 +416,8 @@ enum {
   DSTAGNN_PROF_TAT_FUSED_BWD = 3,  /* tat_fused_bwd_kernel                                      */
   DSTAGNN_PROF_GTU_FUSED_FWD = 4,  /* gtu_fwd_fused_kernel                                      */
   DSTAGNN_PROF_GTU_FUSED_BWD = 5,  /* gtu_bwd_fused_kernel                                      */
-  DSTAGNN_PROF_GTU_TCONV = 6,      /* gtu_tconv / gtu_conv_fwd sliding-window convolutions      */
-  DSTAGNN_PROF_SAT_FUSED = 7       /* sat_ln_bwd_fused kernel                                   */
+  DSTAGNN_PROF_GTU_TCONV = 6,      /* gtu_tconv sliding-window convolution gradient             */
+  DSTAGNN_PROF_SAT_FUSED = 7       /* retired (that kernel is gone): never reported             */
 };
 typedef struct dstagnn_prof_record {
   double flops;  /* algorithmic FLOP of the call   */

@@ -1,8 +1,6 @@
 """GPU: the opt-in / A-B paths that the default run does not take, each held to the fp64 oracle in
 a subprocess (the library reads its switches once per process):
 
-  DSTAGNN_DE_OMAP=1    the inner block's dE accumulated into dx by the GEMM output-map epilogue
-                       (block.hip stage_tat) instead of a dE buffer + transpose_kernel
   DSTAGNN_TAT_MFMA=0   the VALU wave kernels of the temporal attention instead of the
                        matrix-core ones (ops.hip tat_*_mfma_kernel)
   DSTAGNN_SIDE_CUMASK  the side stream confined to a CU subset (scheduling only: same results)
@@ -18,14 +16,10 @@ a subprocess (the library reads its switches once per process):
   DSTAGNN_TF_WAVES=4 / DSTAGNN_TF_BWD_WAVES=4  the fused temporal-attention kernels on four waves
                        instead of eight
   DSTAGNN_GTU_TCONV=0  the GTU input gradient as the K-concatenated GEMM (run_gemm_kcat)
-  DSTAGNN_GTU_GCONV=1  the GTU forward convolutions by the sliding-window kernel (gtu_tconv.hip)
   DSTAGNN_TAIL_CT24=0  the split GTU tail path at T = 24 instead of the compile-time kernels
   DSTAGNN_KSIG=0       main -> side stream forks signalled by hipStreamWriteValue32 instead of
                        by the prologue store of the main-stream kernel the call site names
                        (streams.hpp Streams::fork_on; the default path is held by every other GPU test)
-  DSTAGNN_FC_SIDE=1    the TAt fc weight gradient on the side stream instead of grouped with the
-                       Q|K|V weight gradient on the main stream
-  DSTAGNN_TATLN_SIDE=1 the TAt LayerNorm gamma / beta column sums on the side stream
   DSTAGNN_GATES_BWD_SCALAR=1  the split-path GTU gates backward one element per thread (T = 144)
   DSTAGNN_TAT_FUSED=0  the temporal-attention stage as separate launches (Q|K|V GEMM, attention,
                        fc GEMM, LayerNorm, x transpose) instead of tat_fused.hip's one kernel
@@ -35,11 +29,8 @@ a subprocess (the library reads its switches once per process):
                        gtu_fused.hip's one kernel (convolutions, gates, fcmy, residual, LN)
   DSTAGNN_GTU_FUSED_BWD=0  the GTU stage backward as gtu_tail_bwd_ct + gtu_tconv (zero-padded gate
                        gradient rows) instead of gtu_fused.hip's one kernel
-  DSTAGNN_SATLN_FUSED=1  the SAt projection backward (dZd GEMM) and the EmbedS LayerNorm backward as one
-                       kernel (sat_fused.hip) instead of a GEMM + ln_bwd
   DSTAGNN_LN_V4=0      the LayerNorm rows of 256 / 512 / 1024 floats by the scalar wave-per-row kernels
                        instead of the float4 ones
-  DSTAGNN_DWP_MAIN=1   the pre_conv weight gradient on the main stream instead of the side stream
   DSTAGNN_SIDE_STREAM=0  everything on the caller's stream, no fork / join (the serialised path of
                        the profiling tools)
   DSTAGNN_TAT_FUSED_BWD=0  the fused temporal-attention forward with the unfused backward launches
@@ -54,7 +45,7 @@ a subprocess (the library reads its switches once per process):
                        data (streams.hip debug_delay); results must not change
 
 PEMS08 geometry (the bench's default path otherwise; t24 for the T = 24 switches and, with h = 2,
-for the unfused TAt backward's fork with side work and its DE_OMAP branch), inner block
+the unfused TAt backward under the stream probes), inner block
 with a broadcast res_att in eval and train mode plus the first block, same bounds as
 tests/test_gpu_parity.py::test_block_vs_oracle_configs."""
 import os
@@ -78,17 +69,15 @@ print("KNOB_OK")
 """
 
 
-@pytest.mark.parametrize("env,cfg,B", [("DSTAGNN_DE_OMAP=1", "pems08", 4), ("DSTAGNN_TAT_MFMA=0", "pems08", 4),
+@pytest.mark.parametrize("env,cfg,B", [("DSTAGNN_TAT_MFMA=0", "pems08", 4),
                                        ("DSTAGNN_SIDE_CUMASK=0x11111111", "pems08", 4),
                                        ("DSTAGNN_SDDMM_NOPF=1", "pems08", 4), ("DSTAGNN_GTU_TCONV=0", "pems08", 4),
                                        ("DSTAGNN_SDDMM_PAIR=0", "pems08", 4), ("DSTAGNN_SDDMM_PAIR=1", "pems08", 3),
                                        ("DSTAGNN_AGG_PAIR=0", "pems08", 4), ("DSTAGNN_AGG_PAIR=1", "pems08", 3),
                                        ("DSTAGNN_FLASH_DQK2=0", "pems08", 4), ("DSTAGNN_FLASH_MASK2=0", "pems08", 4),
                                        ("DSTAGNN_TF_WAVES=4", "pems08", 4), ("DSTAGNN_TF_BWD_WAVES=4", "pems08", 4),
-                                       ("DSTAGNN_GTU_GCONV=1", "pems08", 4), ("DSTAGNN_GTU_GCONV=1", "t24", 2),
                                        ("DSTAGNN_TAIL_CT24=0", "t24", 2), ("DSTAGNN_KSIG=0", "pems08", 4),
-                                       ("DSTAGNN_KSIG=0", "pems07+flash", 2), ("DSTAGNN_FC_SIDE=1", "pems08", 4),
-                                       ("DSTAGNN_TATLN_SIDE=1", "pems08", 4),
+                                       ("DSTAGNN_KSIG=0", "pems07+flash", 2),
                                        ("DSTAGNN_DEBUG_MAIN_DELAY_US=1500", "pems08", 4),
                                        ("DSTAGNN_DEBUG_SIDE_DELAY_US=1500", "pems08", 4),
                                        ("DSTAGNN_DEBUG_MAIN_DELAY_US=1500", "pems07+flash", 2),
@@ -97,14 +86,12 @@ print("KNOB_OK")
                                        ("DSTAGNN_TAT_FUSED=0", "pems08", 4),
                                        ("DSTAGNN_TAIL_FOLD=1", "pems08", 4),
                                        ("DSTAGNN_GTU_FUSED=0", "pems08", 4), ("DSTAGNN_GTU_FUSED_BWD=0", "pems08", 4),
-                                       ("DSTAGNN_SATLN_FUSED=1", "pems08", 4), ("DSTAGNN_LN_V4=0", "pems08", 4),
-                                       ("DSTAGNN_DWP_MAIN=1", "pems08", 4),
+                                       ("DSTAGNN_LN_V4=0", "pems08", 4),
                                        ("DSTAGNN_DEBUG_STREAMS=1", "pems07+flash", 2),
                                        ("DSTAGNN_SIDE_STREAM=0", "pems08", 4),
                                        ("DSTAGNN_TAT_FUSED_BWD=0", "pems08", 4),
                                        ("DSTAGNN_CHEB_AGG=0", "pems08", 4),
-                                       ("DSTAGNN_FC_SIDE=1", "t24", 2), ("DSTAGNN_TATLN_SIDE=1", "t24", 2),
-                                       ("DSTAGNN_DE_OMAP=1", "t24", 2), ("DSTAGNN_DEBUG_STREAMS=1", "t24", 2),
+                                       ("DSTAGNN_DEBUG_STREAMS=1", "t24", 2),
                                        ("DSTAGNN_DEBUG_MAIN_DELAY_US=1500", "t24", 2),
                                        ("DSTAGNN_DEBUG_SIDE_DELAY_US=1500", "t24", 2)])
 def test_knob_path_vs_oracle(env, cfg, B):

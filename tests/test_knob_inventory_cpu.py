@@ -5,7 +5,8 @@ either a PATH SWITCH, which selects different code and therefore has a row in
 tests/test_gpu_knobs.py::test_knob_path_vs_oracle, or a TOOL OVERRIDE, a debug / logging /
 tuning value that a file kept under tools/ sets (TOOL_OVERRIDES below).  A switch of neither
 kind is deleted together with the code only it reaches.  The library reads the environment only
-through env_flag / env_int / env_str of common.hpp, which is what this test scans for."""
+through env_flag / env_int / env_str of common.hpp, which is what this test scans for.  The
+table of DESIGN.md §9, the third copy of the list, is held to the same set."""
 import ast
 import os
 import re
@@ -60,6 +61,19 @@ def _knob_rows():
     raise AssertionError("test_knob_path_vs_oracle's parameter table not found")
 
 
+def _design_table_names():
+    """The back-quoted DSTAGNN_* tokens of DESIGN.md §9's table rows (the lines that start with
+    "|" between the "## 9." heading and "### Experiment code removed"; the prose is not read)."""
+    with open(os.path.join(ROOT, "DESIGN.md")) as fh:
+        text = fh.read()
+    head = re.search(r"^## 9\..*$", text, re.M)
+    assert head, "DESIGN.md: the '## 9.' heading not found"
+    end = text.find("### Experiment code removed", head.end())
+    assert end > 0, "DESIGN.md: '### Experiment code removed' not found after '## 9.'"
+    rows = [l for l in text[head.end():end].splitlines() if l.startswith("|")]
+    return [t for l in rows for t in re.findall(r"`([^`]*)`", l) if "DSTAGNN_" in t]
+
+
 def test_environment_is_read_through_the_helpers_only():
     bare = [f for f, text in _sources() if f != "common.hpp" and re.search(r"\bgetenv\s*\(", text)]
     assert not bare, f"bare getenv( outside common.hpp: {bare}"
@@ -79,4 +93,15 @@ def test_no_stale_entry_in_either_list():
     assert len(set(TOOL_OVERRIDES)) == len(TOOL_OVERRIDES)
     gone = sorted((rows | set(TOOL_OVERRIDES)) - read)
     assert not gone, f"listed, but no longer read by the library: {gone}"
+
+
+def test_design_table_lists_exactly_the_variables_read():
+    tokens = _design_table_names()
+    assert tokens, "DESIGN.md §9: no DSTAGNN_* token in the table rows: the scan is broken"
+    short = [t for t in tokens if not re.fullmatch(r"DSTAGNN_[A-Z0-9_]+", t)]
+    assert not short, f"DESIGN.md §9: one full variable name per back-quoted token, got {short}"
+    assert len(set(tokens)) == len(tokens), f"DESIGN.md §9: a variable listed twice: {sorted(tokens)}"
+    read = _names_read()
+    assert set(tokens) == read, (f"DESIGN.md §9 table vs the library: only in the table "
+                                 f"{sorted(set(tokens) - read)}, only read {sorted(read - set(tokens))}")
 

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box interleaved A/B of the PEMS08 bench step: the baseline library (LD_LIBRARY_PATH=$1)
 # against this tree's library under each of the given env settings ("-" = none).
-#   bash tools/ab_step.sh abtest/base - DSTAGNN_FC_SIDE=1
+#   bash tools/ab_step.sh abtest/base - DSTAGNN_KSIG=0
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/ab
