@@ -27,6 +27,13 @@ __device__ __forceinline__ float ld_agent(const float* p) {
 __device__ __forceinline__ void st_agent(float* p, float v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// ... of an fp64 partial: one aligned 8-byte access, never two halves
+__device__ __forceinline__ double ld_agent(const double* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void st_agent(double* p, double v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
 // one lane: draw a ticket among n arrivals (step 4, no fence); true for the last arrival
 __device__ __forceinline__ bool ticket_draw(int* cnt, int n) { return atomicAdd(cnt, 1) == n - 1; }

@@ -1,0 +1,360 @@
+// loss.hip — the two ends of a training step on the GPU (gfx950): the criterion
+// (train_DSTAGNN_my.py:132 `nn.SmoothL1Loss()`, :156-157 loss + backward) with the masked
+// variants the model family uses for series with gaps, and the test-set scores
+// (lib/utils1.py:418-431: per-horizon MAE / RMSE / MAPE; lib/metrics.py:6-17 masked MAPE).
+//
+// On a (B, N, P) head output of ~65 k floats all of this is launch latency, so each is ONE launch:
+//   loss_fwd_kernel      d = y - t in fp32, the per-element term in fp32, every add from the first
+//                        one in fp64 (sum and valid count per thread; the wave butterfly; the four
+//                        wave sums ((w0 + w1) + (w2 + w3))).  A workgroup's {sum, count} goes out
+//                        sc1 and the workgroup whose ticket came last (handoff.hpp) adds all
+//                        partials in one fixed order: lane l of its first wave takes partials l,
+//                        l + 64, ... in index order, then the butterfly.  stat = {sum, count},
+//                        loss = sum / count (0 when nothing is valid).  Same bits on every launch.
+//   loss_bwd_kernel      dy = l'(d) * (gout / count) on valid entries, 0 elsewhere; count from the
+//                        forward's stat and gout from device memory: no host sync.  Recomputes d.
+//   metrics_accum_kernel (rows, P) predictions / targets -> a running (P, 4) fp64 table of
+//                        sum |e|, sum e^2, sum |e / t| over t != null, count of t != null.  Thread
+//                        rl P + p of the first (256 / P) P reads element row0 P + rl P + p
+//                        (coalesced; its p never changes), keeps four fp64 sums, LDS folds them
+//                        over rl in order, workgroups hand off as above and the last one adds the
+//                        folded sums into the table.  No floating-point atomics anywhere.
+//
+// A masked entry is selected out (never multiplied by zero): a NaN target under the NaN mask
+// leaves the loss finite and its gradient entry exactly 0.  A NaN prediction at a valid entry makes
+// the loss NaN (HipAdam's non-finite skip then sees a NaN gradient norm).
+//
+// Vector (16-byte) loads where every pointer of the launch is 16-byte aligned and the tile is
+// whole; scalar loads otherwise (a batch slice y[b:b+bs] of a contiguous tensor is often not
+// aligned; the last tile is usually partial).
+#include <cmath>
+
+#include "handoff.hpp"
+#include "ops.hpp"
+
+namespace {
+
+constexpr int kLossThreads = 256, kLossPer = 16, kLossTile = kLossThreads * kLossPer;
+constexpr int kLossMaxWg = 1024;  // beyond it a workgroup walks tiles w, w + grid, ...
+constexpr int kMetThreads = 256, kMetPasses = 8, kMetMaxWg = 256, kMetMaxP = 256;
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ bool is_valid(int mask, float null_val, float t) {
+  return mask == DSTAGNN_MASK_NONE ? true : mask == DSTAGNN_MASK_NAN ? !(t != t) : t != null_val;
+}
+
+// the per-element term of d = y - t (fp32; at most three roundings with d's own)
+__device__ __forceinline__ float loss_term(int kind, float b, float d) {
+  const float a = fabsf(d);
+  switch (kind) {
+    case DSTAGNN_LOSS_SMOOTH_L1: return a < b ? 0.5f * d * d / b : a - 0.5f * b;
+    case DSTAGNN_LOSS_HUBER: return a <= b ? 0.5f * d * d : b * (a - 0.5f * b);
+    case DSTAGNN_LOSS_MAE: return a;
+    default: return d * d;
+  }
+}
+
+// its derivative; sign(0) = 0 and a NaN d stays NaN
+__device__ __forceinline__ float loss_slope(int kind, float b, float d) {
+  const float a = fabsf(d);
+  const float s = d > 0.f ? 1.f : d < 0.f ? -1.f : d;
+  switch (kind) {
+    case DSTAGNN_LOSS_SMOOTH_L1: return a < b ? d / b : s;
+    case DSTAGNN_LOSS_HUBER: return a <= b ? d : b * s;
+    case DSTAGNN_LOSS_MAE: return s;
+    default: return 2.f * d;
+  }
+}
+
+__global__ __launch_bounds__(kLossThreads) void loss_fwd_kernel(dstagnn_loss_cfg cfg, int64_t n,
+                                                               const float* __restrict__ y,
+                                                               const float* __restrict__ tg, int vec,
+                                                               double* __restrict__ part, int* ticket,
+                                                               double* __restrict__ stat, float* __restrict__ loss) {
+  __shared__ double ws[kLossThreads / 64], wc[kLossThreads / 64];
+  __shared__ int last;
+  const int t = threadIdx.x;
+  double sum = 0.0, cnt = 0.0;
+  for (int64_t base = (int64_t)blockIdx.x * kLossTile; base < n; base += (int64_t)gridDim.x * kLossTile) {
+    float yv[kLossPer], tv[kLossPer];
+    if (vec && base + kLossTile <= n) {  // (uniform) a whole tile: four 16-byte loads per tensor
+      const float4* __restrict__ y4 = reinterpret_cast<const float4*>(y + base);
+      const float4* __restrict__ t4 = reinterpret_cast<const float4*>(tg + base);
+#pragma unroll
+      for (int u = 0; u < kLossPer / 4; ++u) {
+        const float4 a = y4[u * kLossThreads + t], b = t4[u * kLossThreads + t];
+        yv[4 * u] = a.x, yv[4 * u + 1] = a.y, yv[4 * u + 2] = a.z, yv[4 * u + 3] = a.w;
+        tv[4 * u] = b.x, tv[4 * u + 1] = b.y, tv[4 * u + 2] = b.z, tv[4 * u + 3] = b.w;
+      }
+#pragma unroll
+      for (int u = 0; u < kLossPer; ++u)
+        if (is_valid(cfg.mask_mode, cfg.null_val, tv[u])) {
+          sum += (double)loss_term(cfg.kind, cfg.param, yv[u] - tv[u]);
+          cnt += 1.0;
+        }
+    } else {
+#pragma unroll
+      for (int u = 0; u < kLossPer; ++u) {
+        const int64_t i = base + t + (int64_t)kLossThreads * u;
+        const bool ok = i < n;
+        yv[u] = ok ? y[i] : 0.f;
+        tv[u] = ok ? tg[i] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < kLossPer; ++u) {
+        const int64_t i = base + t + (int64_t)kLossThreads * u;
+        if (i < n && is_valid(cfg.mask_mode, cfg.null_val, tv[u])) {
+          sum += (double)loss_term(cfg.kind, cfg.param, yv[u] - tv[u]);
+          cnt += 1.0;
+        }
+      }
+    }
+  }
+  sum = wave_sum_f64(sum);
+  cnt = wave_sum_f64(cnt);
+  if ((t & 63) == 0) ws[t >> 6] = sum, wc[t >> 6] = cnt;
+  __syncthreads();
+  // the hand-off of handoff.hpp: {sum, count} per workgroup, every partial an 8-byte sc1 store
+  if (t == 0) {
+    st_agent(part + 2 * (int64_t)blockIdx.x, (ws[0] + ws[1]) + (ws[2] + ws[3]));
+    st_agent(part + 2 * (int64_t)blockIdx.x + 1, (wc[0] + wc[1]) + (wc[2] + wc[3]));
+  }
+  if (!last_arrival(ticket, (int)gridDim.x, &last)) return;
+  if (t >= 64) return;
+  double a = 0.0, c = 0.0;
+  for (int64_t k = t; k < (int64_t)gridDim.x; k += 64) {
+    a += ld_agent(part + 2 * k);
+    c += ld_agent(part + 2 * k + 1);
+  }
+  a = wave_sum_f64(a);
+  c = wave_sum_f64(c);
+  if (t == 0) {
+    stat[0] = a;
+    stat[1] = c;
+    loss[0] = c > 0.0 ? (float)(a / c) : 0.f;
+  }
+}
+
+__global__ __launch_bounds__(kLossThreads) void loss_bwd_kernel(dstagnn_loss_cfg cfg, int64_t n,
+                                                               const float* __restrict__ y,
+                                                               const float* __restrict__ tg, int vec,
+                                                               const double* __restrict__ stat,
+                                                               const float* __restrict__ gout, float* __restrict__ dy) {
+  const int t = threadIdx.x;
+  const double cnt = stat[1];
+  const float g = gout != nullptr ? gout[0] : 1.f;
+  const float scale = cnt > 0.0 ? (float)((double)g / cnt) : 0.f;
+  const int64_t base = (int64_t)blockIdx.x * kLossTile;
+  if (vec && base + kLossTile <= n) {
+    const float4* __restrict__ y4 = reinterpret_cast<const float4*>(y + base);
+    const float4* __restrict__ t4 = reinterpret_cast<const float4*>(tg + base);
+    float4* __restrict__ d4 = reinterpret_cast<float4*>(dy + base);
+    float4 a[kLossPer / 4], b[kLossPer / 4];
+#pragma unroll
+    for (int u = 0; u < kLossPer / 4; ++u) a[u] = y4[u * kLossThreads + t], b[u] = t4[u * kLossThreads + t];
+#pragma unroll
+    for (int u = 0; u < kLossPer / 4; ++u) {
+      float4 r;
+      r.x = is_valid(cfg.mask_mode, cfg.null_val, b[u].x) ? loss_slope(cfg.kind, cfg.param, a[u].x - b[u].x) * scale : 0.f;
+      r.y = is_valid(cfg.mask_mode, cfg.null_val, b[u].y) ? loss_slope(cfg.kind, cfg.param, a[u].y - b[u].y) * scale : 0.f;
+      r.z = is_valid(cfg.mask_mode, cfg.null_val, b[u].z) ? loss_slope(cfg.kind, cfg.param, a[u].z - b[u].z) * scale : 0.f;
+      r.w = is_valid(cfg.mask_mode, cfg.null_val, b[u].w) ? loss_slope(cfg.kind, cfg.param, a[u].w - b[u].w) * scale : 0.f;
+      d4[u * kLossThreads + t] = r;
+    }
+    return;
+  }
+  float yv[kLossPer], tv[kLossPer];
+#pragma unroll
+  for (int u = 0; u < kLossPer; ++u) {
+    const int64_t i = base + t + (int64_t)kLossThreads * u;
+    const bool ok = i < n;
+    yv[u] = ok ? y[i] : 0.f;
+    tv[u] = ok ? tg[i] : 0.f;
+  }
+#pragma unroll
+  for (int u = 0; u < kLossPer; ++u) {
+    const int64_t i = base + t + (int64_t)kLossThreads * u;
+    if (i < n)
+      dy[i] = is_valid(cfg.mask_mode, cfg.null_val, tv[u]) ? loss_slope(cfg.kind, cfg.param, yv[u] - tv[u]) * scale : 0.f;
+  }
+}
+
+__global__ __launch_bounds__(kMetThreads) void metrics_accum_kernel(int64_t n, int P, const float* __restrict__ pred,
+                                                                   const float* __restrict__ tg, float null_val,
+                                                                   int nan_mode, double* __restrict__ part,
+                                                                   int* ticket, double* __restrict__ table) {
+  __shared__ double red[4][kMetThreads];
+  __shared__ int last;
+  const int t = threadIdx.x;
+  const int RL = kMetThreads / P, A = RL * P;  // rows per pass, threads that read
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  if (t < A) {
+    // a pass is RL whole rows = A contiguous floats; workgroup w takes passes w, w + grid, ...
+    // (e0 is a multiple of P: this thread's horizon is t % P in every pass)
+    for (int64_t e0 = (int64_t)blockIdx.x * A; e0 < n; e0 += (int64_t)gridDim.x * A) {
+      const int64_t i = e0 + t;
+      if (i < n) {
+        const float pv = pred[i], tv = tg[i];
+        const float e = pv - tv;
+        s[0] += (double)fabsf(e);
+        s[1] += (double)(e * e);
+        if (nan_mode ? !(tv != tv) : tv != null_val) {
+          s[2] += (double)fabsf(e / tv);
+          s[3] += 1.0;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) red[c][t] = s[c];
+  __syncthreads();
+  // fold over the rows of equal horizon in row order; item = c P + p
+  const int items = 4 * P;
+  for (int item = t; item < items; item += kMetThreads) {
+    const int c = item / P, p = item - c * P;
+    double a = 0.0;
+    for (int rl = 0; rl < RL; ++rl) a += red[c][rl * P + p];
+    st_agent(part + (int64_t)blockIdx.x * items + item, a);
+  }
+  if (!last_arrival(ticket, (int)gridDim.x, &last)) return;
+  for (int item = t; item < items; item += kMetThreads) {
+    const int c = item / P, p = item - c * P;
+    double a = 0.0;
+    for (int64_t k = 0; k < (int64_t)gridDim.x; ++k) a += ld_agent(part + k * items + item);
+    table[p * 4 + c] += a;  // launches on one stream are ordered: the running table needs no atomics
+  }
+}
+
+int64_t loss_grid(int64_t n) {
+  const int64_t tiles = (n + kLossTile - 1) / kLossTile;
+  return tiles < 1 ? 1 : tiles > kLossMaxWg ? kLossMaxWg : tiles;
+}
+
+int64_t metrics_grid(int64_t rows, int P) {
+  const int64_t per = (int64_t)(kMetThreads / P) * kMetPasses;  // rows per workgroup before the cap
+  const int64_t g = (rows + per - 1) / per;
+  return g < 1 ? 1 : g > kMetMaxWg ? kMetMaxWg : g;
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// the checks shared by forward and backward (nothing here touches the device); cfg normalised:
+// smooth_l1 at beta = 0 is mae, and a NaN null value selects the NaN mask
+int loss_args(const char* who, const dstagnn_loss_cfg* cfg, int64_t n, const void* y, const void* target,
+              dstagnn_loss_cfg* out) {
+  const std::string w(who);
+  if (!cfg || !y || !target) {
+    set_last_error(w + ": null cfg / y / target");
+    return DSTAGNN_E_ARG;
+  }
+  if (n <= 0 || n >= (1ll << 31)) {
+    set_last_error(w + ": n must be in [1, 2^31)");
+    return DSTAGNN_E_ARG;
+  }
+  if (cfg->kind < DSTAGNN_LOSS_SMOOTH_L1 || cfg->kind > DSTAGNN_LOSS_MSE) {
+    set_last_error(w + ": unknown loss kind " + std::to_string(cfg->kind));
+    return DSTAGNN_E_ARG;
+  }
+  if (cfg->mask_mode < DSTAGNN_MASK_NONE || cfg->mask_mode > DSTAGNN_MASK_NAN) {
+    set_last_error(w + ": unknown mask mode " + std::to_string(cfg->mask_mode));
+    return DSTAGNN_E_ARG;
+  }
+  if (!(cfg->param >= 0.f)) {  // (a NaN fails too)
+    set_last_error(w + ": negative or NaN param (beta / delta)");
+    return DSTAGNN_E_ARG;
+  }
+  *out = *cfg;
+  if (out->kind == DSTAGNN_LOSS_SMOOTH_L1 && out->param == 0.f) out->kind = DSTAGNN_LOSS_MAE;
+  if (out->mask_mode == DSTAGNN_MASK_NEQ && std::isnan(out->null_val)) out->mask_mode = DSTAGNN_MASK_NAN;
+  return 0;
+}
+
+}  // namespace
+
+int dstagnn_loss_tile_elems(void) { return kLossTile; }
+
+int64_t dstagnn_loss_scratch_bytes(int64_t n) {
+  return n <= 0 ? 0 : loss_grid(n) * 2 * (int64_t)sizeof(double);
+}
+
+int dstagnn_loss_forward(const dstagnn_loss_cfg* cfg, int64_t n, const float* y, const float* target, float* loss,
+                         double* stat, void* scratch, size_t scratch_bytes, dstagnn_stream_t stream) {
+  dstagnn_loss_cfg c;
+  if (int rc = loss_args("loss_forward", cfg, n, y, target, &c)) return rc;
+  if (!loss || !stat || !scratch) {
+    set_last_error("loss_forward: null loss / stat / scratch");
+    return DSTAGNN_E_ARG;
+  }
+  if (scratch_bytes < (size_t)dstagnn_loss_scratch_bytes(n)) {
+    set_last_error("loss_forward: scratch smaller than dstagnn_loss_scratch_bytes(n)");
+    return DSTAGNN_E_SPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  int* ticket = stream_counters(st, 1);
+  if (!ticket) {
+    set_last_error("loss_forward: no ticket counter for this stream");
+    return DSTAGNN_E_ARG;
+  }
+  const int vec = aligned16(y) && aligned16(target);
+  hipLaunchKernelGGL(loss_fwd_kernel, dim3((unsigned)loss_grid(n)), dim3(kLossThreads), 0, st, c, n, y, target, vec,
+                     static_cast<double*>(scratch), ticket, stat, loss);
+  DS_CHECK_LAUNCH();
+  return 0;
+}
+
+int dstagnn_loss_backward(const dstagnn_loss_cfg* cfg, int64_t n, const float* y, const float* target,
+                          const double* stat, const float* gout, float* dy, dstagnn_stream_t stream) {
+  dstagnn_loss_cfg c;
+  if (int rc = loss_args("loss_backward", cfg, n, y, target, &c)) return rc;
+  if (!stat || !dy) {
+    set_last_error("loss_backward: null stat / dy");
+    return DSTAGNN_E_ARG;
+  }
+  const int vec = aligned16(y) && aligned16(target) && aligned16(dy);
+  const int64_t tiles = (n + kLossTile - 1) / kLossTile;
+  hipLaunchKernelGGL(loss_bwd_kernel, dim3((unsigned)tiles), dim3(kLossThreads), 0, (hipStream_t)stream, c, n, y,
+                     target, vec, stat, gout, dy);
+  DS_CHECK_LAUNCH();
+  return 0;
+}
+
+int64_t dstagnn_metrics_scratch_bytes(int64_t rows, int P) {
+  if (rows <= 0 || P < 1 || P > kMetMaxP) return 0;
+  return metrics_grid(rows, P) * 4 * (int64_t)P * (int64_t)sizeof(double);
+}
+
+int dstagnn_metrics_accumulate(int64_t rows, int P, const float* pred, const float* target, float null_val,
+                               double* table, void* scratch, size_t scratch_bytes, dstagnn_stream_t stream) {
+  if (P < 1 || P > kMetMaxP) {
+    set_last_error("metrics_accumulate: P (the last axis) must be in [1, 256], got " + std::to_string(P));
+    return DSTAGNN_E_SHAPE;
+  }
+  if (rows <= 0 || rows * (int64_t)P >= (1ll << 31)) {
+    set_last_error("metrics_accumulate: rows * P must be in [1, 2^31)");
+    return DSTAGNN_E_SHAPE;
+  }
+  if (!pred || !target || !table || !scratch) {
+    set_last_error("metrics_accumulate: null pred / target / table / scratch");
+    return DSTAGNN_E_ARG;
+  }
+  if (scratch_bytes < (size_t)dstagnn_metrics_scratch_bytes(rows, P)) {
+    set_last_error("metrics_accumulate: scratch smaller than dstagnn_metrics_scratch_bytes(rows, P)");
+    return DSTAGNN_E_SPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  int* ticket = stream_counters(st, 1);
+  if (!ticket) {
+    set_last_error("metrics_accumulate: no ticket counter for this stream");
+    return DSTAGNN_E_ARG;
+  }
+  hipLaunchKernelGGL(metrics_accum_kernel, dim3((unsigned)metrics_grid(rows, P)), dim3(kMetThreads), 0, st,
+                     rows * (int64_t)P, P, pred, target, null_val, std::isnan(null_val) ? 1 : 0,
+                     static_cast<double*>(scratch), ticket, table);
+  DS_CHECK_LAUNCH();
+  return 0;
+}

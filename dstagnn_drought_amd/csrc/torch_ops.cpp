@@ -13,6 +13,8 @@
 //   dstagnn::block_fwd_only / block_fwd_only_bytes  the forward-only call and its workspace size
 //   dstagnn::cheb_sat_fwd/bwd  cheb_conv_withSAt.forward (:117-133) and its gradient
 //   dstagnn::head_fwd/bwd   DSTAGNN_submodule's cat + final_conv + final_fc (:272-280)
+//   dstagnn::loss_fwd/bwd   the criterion (train_DSTAGNN_my.py:132, :156-157) and its masked variants
+//   dstagnn::metrics_update per-horizon MAE / RMSE / MAPE sums on the device (lib/utils1.py:418-431)
 //   dstagnn::gemm_f32       the strided f32-MFMA GEMM (tests / tools)
 //   dstagnn::colsum         the fixed-order column-sum reduction (bias / LayerNorm affine grads; tests)
 //   dstagnn::stag_* / emd_dense / fast_stag_distances / graph_topk   the graph builders
@@ -904,6 +906,77 @@ void grad_scale(at::TensorList grads, const Tensor& stat, double max_norm) {
 }
 
 // -------------------------------------------------------------------------------------
+// criterion and test-set scores (loss.hip)
+// -------------------------------------------------------------------------------------
+dstagnn_loss_cfg loss_cfg(int64_t kind, double param, int64_t mask_mode, double null_val) {
+  return {(int)kind, (float)param, (int)mask_mode, (float)null_val};
+}
+
+void check_loss_pair(const Tensor& y, const Tensor& target, const char* who) {
+  check_dev(y, at::kFloat, "y");
+  check_dev(target, at::kFloat, "target");
+  TORCH_CHECK(y.sizes() == target.sizes(), who, ": y ", y.sizes(), " and target ", target.sizes(), " differ");
+  TORCH_CHECK(y.device() == target.device(), who, ": y and target on different devices");
+}
+
+// -> (loss: 0-dim fp32, stat: {fp64 sum of the terms, valid count}); no host sync
+std::tuple<Tensor, Tensor> loss_fwd(const Tensor& y, const Tensor& target, int64_t kind, double param,
+                                    int64_t mask_mode, double null_val) {
+  check_loss_pair(y, target, "loss_fwd");
+  c10::DeviceGuard guard(y.device());
+  const int64_t n = y.numel();
+  const dstagnn_loss_cfg cfg = loss_cfg(kind, param, mask_mode, null_val);
+  // one allocation: stat's two doubles, then the per-workgroup partials
+  const int64_t sb = std::max<int64_t>(dstagnn_loss_scratch_bytes(n), 16);
+  Tensor loss = at::empty({}, f32(y)), buf = at::empty({2 + sb / 8}, y.options().dtype(at::kDouble));
+  check_rc(dstagnn_loss_forward(&cfg, n, y.data_ptr<float>(), target.data_ptr<float>(), loss.data_ptr<float>(),
+                                buf.data_ptr<double>(), buf.data_ptr<double>() + 2, (size_t)sb, stream_of(y)),
+           "dstagnn_loss_forward");
+  return {loss, buf.narrow(0, 0, 2)};
+}
+
+// dy = gout * l'(y - target) / stat[1] on valid entries, 0 elsewhere (gout: a one-element fp32
+// device tensor, None = 1)
+Tensor loss_bwd(const Tensor& y, const Tensor& target, const Tensor& stat, const c10::optional<Tensor>& gout,
+                int64_t kind, double param, int64_t mask_mode, double null_val) {
+  check_loss_pair(y, target, "loss_bwd");
+  check_dev(stat, at::kDouble, "stat");
+  TORCH_CHECK(stat.numel() == 2 && stat.device() == y.device(), "loss_bwd: stat must be loss_fwd's two doubles");
+  if (gout.has_value() && gout->defined()) {
+    check_dev(*gout, at::kFloat, "gout");
+    TORCH_CHECK(gout->numel() == 1 && gout->device() == y.device(), "loss_bwd: gout must be one float on y's device");
+  }
+  c10::DeviceGuard guard(y.device());
+  const dstagnn_loss_cfg cfg = loss_cfg(kind, param, mask_mode, null_val);
+  Tensor dy = at::empty(y.sizes(), f32(y));
+  check_rc(dstagnn_loss_backward(&cfg, y.numel(), y.data_ptr<float>(), target.data_ptr<float>(),
+                                 stat.data_ptr<double>(), ptr_or_null<float>(gout), dy.data_ptr<float>(),
+                                 stream_of(y)),
+           "dstagnn_loss_backward");
+  return dy;
+}
+
+// pred, target (..., P) added into the running (P, 4) fp64 table; one launch, no host sync
+void metrics_update(const Tensor& pred, const Tensor& target, double null_val, Tensor table) {
+  check_loss_pair(pred, target, "metrics_update");
+  check_dev(table, at::kDouble, "table");
+  TORCH_CHECK(pred.dim() >= 1, "metrics_update: pred must have a horizon axis");
+  const int64_t P = pred.size(-1), rows = P > 0 ? pred.numel() / P : 0;
+  // (a P outside [1, 256] is the library's DSTAGNN_E_SHAPE below)
+  TORCH_CHECK(P < 1 || P > 256 || table.numel() == 4 * P, "metrics_update: table must be (", P, ", 4), got ",
+              table.sizes());
+  TORCH_CHECK(table.device() == pred.device(), "metrics_update: table on another device");
+  c10::DeviceGuard guard(pred.device());
+  const int Pi = (int)std::min<int64_t>(P, INT32_MAX);
+  const int64_t sb = std::max<int64_t>(dstagnn_metrics_scratch_bytes(rows, Pi), 16);
+  Tensor scratch = at::empty({sb / 8}, pred.options().dtype(at::kDouble));
+  check_rc(dstagnn_metrics_accumulate(rows, Pi, pred.data_ptr<float>(), target.data_ptr<float>(), (float)null_val,
+                                      table.data_ptr<double>(), scratch.data_ptr<double>(), (size_t)sb,
+                                      stream_of(pred)),
+           "dstagnn_metrics_accumulate");
+}
+
+// -------------------------------------------------------------------------------------
 // graph builders (fp64)
 // -------------------------------------------------------------------------------------
 // data (T,N,F) -> (xhat (N,T,F), p (N,T), psum (N))
@@ -1051,6 +1124,10 @@ TORCH_LIBRARY(dstagnn, m) {
         "float beta1, float beta2, float eps, float step_size, float bc2_sqrt, float lr, float weight_decay, "
         "bool decoupled, float max_norm, bool skip_nonfinite, Tensor stat, Tensor(d!) skipped) -> ()");
   m.def("grad_scale(Tensor(a!)[] grads, Tensor stat, float max_norm) -> ()");
+  m.def("loss_fwd(Tensor y, Tensor target, int kind, float param, int mask_mode, float null_val) -> (Tensor, Tensor)");
+  m.def("loss_bwd(Tensor y, Tensor target, Tensor stat, Tensor? gout, int kind, float param, int mask_mode, "
+        "float null_val) -> Tensor");
+  m.def("metrics_update(Tensor pred, Tensor target, float null_val, Tensor(a!) table) -> ()");
   m.def("stag_prep(Tensor data) -> (Tensor, Tensor, Tensor)");
   m.def("stag_emd_pairs(Tensor xhat, Tensor p, Tensor psum, Tensor pairs, bool with_pivots) -> (Tensor, Tensor, Tensor)");
   m.def("stag_emd_lds_bytes(int T, int F) -> int", stag_emd_lds_bytes);
@@ -1088,6 +1165,9 @@ TORCH_LIBRARY_IMPL(dstagnn, CUDA, m) {
   m.impl("grad_sumsq", grad_sumsq);
   m.impl("adam_step_ex", adam_step_ex);
   m.impl("grad_scale", grad_scale);
+  m.impl("loss_fwd", loss_fwd);
+  m.impl("loss_bwd", loss_bwd);
+  m.impl("metrics_update", metrics_update);
   m.impl("stag_prep", stag_prep);
   m.impl("stag_emd_pairs", stag_emd_pairs);
   m.impl("emd_dense", emd_dense);

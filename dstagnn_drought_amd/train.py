@@ -25,6 +25,9 @@ process per GPU with torch.distributed over RCCL:
     first epoch visits samples in the reference's order.
   * the missing ``graph`` key of the PEMS03/07/08 configs (quirk 16: KeyError in the
     reference) defaults to 'AG'.
+  * the criterion is the reference's ``nn.SmoothL1Loss()`` unless the configuration
+    (loss_options()) or ``--loss`` / ``--missing-value`` name one: then loss.HipLoss, on the
+    HIP path, optionally leaving targets equal to a missing value out of the loss.
 """
 import argparse
 import configparser
@@ -123,6 +126,45 @@ def compute_val_loss_mstgcn(net, val_loader, criterion, sw, epoch, limit=None):
         if sw is not None:
             sw.add_scalar('validation_loss', validation_loss, epoch)
     return validation_loss
+
+
+def evaluate_on_test_mstgcn(net, test_loader, test_target_tensor, sw, epoch, _mean, _std):
+    """lib/utils1.py:381-432: MAE / RMSE / MAPE of the predictions over `test_loader` for every
+    horizon, printed as the reference prints them and written to `sw` (a SummaryWriter or None)
+    as 'MAE_{i}_points', 'RMSE_{i}_points', 'MAPE_{i}_points'.  The reference copies every
+    prediction to the host and scores with sklearn; here each batch is scored on the device
+    against its slice of `test_target_tensor` in loader order (loss.ForecastMetrics: one launch
+    per batch) and only the (P, 4) table of sums comes back.  Also returns the list
+    predict_and_save_results_mstgcn returns (the overall three last); the reference returns
+    None.  `_mean` / `_std` are unused, as in the reference."""
+    from .loss import ForecastMetrics
+    net.train(False)
+    with torch.no_grad():
+        test_loader_length = len(test_loader)
+        metrics, at = None, 0
+        for batch_index, (encoder_inputs, labels) in enumerate(test_loader):
+            outputs = net(encoder_inputs)
+            if metrics is None:
+                metrics = ForecastMetrics(outputs.shape[-1], 0.0, outputs.device)
+                test_target_tensor = test_target_tensor.to(outputs.device, torch.float32)
+            metrics.update(outputs, test_target_tensor[at:at + outputs.shape[0]])
+            at += outputs.shape[0]
+            if batch_index % 100 == 0:
+                print('predicting testing set batch %s / %s' % (batch_index + 1, test_loader_length))
+        assert metrics is not None and test_target_tensor.shape[0] == at
+        excel_list = metrics.compute()
+        for i in range(metrics.P):
+            mae, rmse, mape = excel_list[3 * i:3 * i + 3]
+            print('current epoch: %s, predict %s points' % (epoch, i))
+            print('MAE: %.2f' % (mae))
+            print('RMSE: %.2f' % (rmse))
+            print('MAPE: %.2f' % (mape))
+            print()
+            if sw:
+                sw.add_scalar('MAE_%s_points' % (i), mae, epoch)
+                sw.add_scalar('RMSE_%s_points' % (i), rmse, epoch)
+                sw.add_scalar('MAPE_%s_points' % (i), mape, epoch)
+    return excel_list
 
 
 def predict_and_save_results_mstgcn(net, data_loader, data_target_tensor, global_step, _mean, _std, params_path,
@@ -414,6 +456,30 @@ def training_options(tc):
             tc.getboolean('decoupled_weight_decay', fallback=False))
 
 
+def loss_options(tc):
+    """Optional [Training] keys of a configuration (a ConfigParser section): ``loss_function``,
+    ``missing_value``, ``smooth_l1_beta``, ``huber_delta`` -> (str or None, float or None, float,
+    float).  The reference's .conf files have none of them: (None, None, 1.0, 1.0), today's
+    criterion.  ``missing_value = nan`` masks the NaN targets."""
+    mv = tc.get('missing_value', None)
+    return (tc.get('loss_function', None), None if mv is None else float(mv),
+            float(tc.get('smooth_l1_beta', 1.0)), float(tc.get('huber_delta', 1.0)))
+
+
+def make_criterion(name=None, missing_value=None, smooth_l1_beta=1.0, huber_delta=1.0):
+    """The driver's criterion.  With no name and no missing value: ``nn.SmoothL1Loss()``
+    (train_DSTAGNN_my.py:132), the object every run without the keys of loss_options() has
+    always used.  Any explicit name (``smooth_l1`` included) or missing value: a loss.HipLoss,
+    one HIP launch per direction; a missing value alone masks the default ``smooth_l1``.  Raises
+    ValueError for an unknown name and for ``masked_mae`` / ``masked_mse`` without a missing
+    value."""
+    if name is None and missing_value is None:
+        return nn.SmoothL1Loss()
+    from .loss import HipLoss
+    return HipLoss('smooth_l1' if name is None else name, beta=smooth_l1_beta, delta=huber_delta,
+                   null_val=missing_value)
+
+
 def make_adam(params, lr, weight_decay=0.0, decoupled=False, max_grad_norm=None):
     """The driver's optimiser (train_DSTAGNN_my.py:126): HipAdam (one launch) when every
     parameter is an fp32 GPU tensor; DSTAGNN_ADAM=torch-fused / torch for torch's fused or
@@ -443,14 +509,17 @@ def make_adam(params, lr, weight_decay=0.0, decoupled=False, max_grad_norm=None)
 
 def fit(net, train_x, train_y, val_x, val_y, *, epochs, start_epoch=0, batch_size, lr, params_path,
         double_step=True, max_batches=None, log=print, max_grad_norm=None, weight_decay=0.0,
-        decoupled_weight_decay=False):
+        decoupled_weight_decay=False, criterion=None):
     """The epoch loop of train_DSTAGNN_my.py:136-178.  Returns (best_epoch, best_val, history).
     max_grad_norm / weight_decay / decoupled_weight_decay: make_adam's options (off by default,
     as in the reference).  Under data parallelism ``reducer.all_reduce()`` precedes
     ``optimizer.step()``, so the clipping norm is taken on the averaged gradients and is the
-    same on every rank: the ranks clip alike and their parameters stay equal."""
+    same on every rank: the ranks clip alike and their parameters stay equal.
+    criterion: training and validation loss (make_criterion(); None: ``nn.SmoothL1Loss()``).  A
+    masked criterion divides by the valid count of the rank's own batch and the gradients are
+    then averaged over the ranks: a mean of batch means, as the unmasked path has always been."""
     rank, world = _world()
-    criterion = nn.SmoothL1Loss().to(train_x.device)
+    criterion = (nn.SmoothL1Loss() if criterion is None else criterion).to(train_x.device)
     optimizer = make_adam(net.parameters(), lr, weight_decay=weight_decay, decoupled=decoupled_weight_decay,
                           max_grad_norm=max_grad_norm)
     reducer = None
@@ -509,10 +578,12 @@ def load_best(net, path):
 
 
 def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches=None, root='myexperiments',
-        log=print, max_grad_norm=None, weight_decay=None):
+        log=print, max_grad_norm=None, weight_decay=None, loss=None, missing_value=None):
     """Whole script: data, graphs, model, training, best-checkpoint test loss.  The optional
     [Training] keys of training_options() switch clipping / weight decay on; max_grad_norm /
-    weight_decay given here override them."""
+    weight_decay given here override them.  loss / missing_value override the keys of
+    loss_options() the same way; the criterion make_criterion() builds from them is used for
+    training, validation and the final test loss."""
     config = configparser.ConfigParser()
     config.read(config_path)
     dc, tc = config['Data'], config['Training']
@@ -537,16 +608,19 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
     bs = int(tc['batch_size'])
     n_epochs = int(tc['epochs']) if epochs is None else int(epochs)
     cfg_norm, cfg_wd, decoupled = training_options(tc)
+    cfg_loss, cfg_missing, beta, delta = loss_options(tc)
+    criterion = make_criterion(cfg_loss if loss is None else loss,
+                               cfg_missing if missing_value is None else missing_value, beta, delta)
     best_epoch, best_val, history = fit(net, train_x, train_y, val_x, val_y, epochs=n_epochs,
                                         start_epoch=int(tc['start_epoch']), batch_size=bs,
                                         lr=float(tc['learning_rate']), params_path=params_path,
                                         double_step=double_step, max_batches=max_batches, log=log,
                                         max_grad_norm=cfg_norm if max_grad_norm is None else max_grad_norm,
                                         weight_decay=cfg_wd if weight_decay is None else weight_decay,
-                                        decoupled_weight_decay=decoupled)
+                                        decoupled_weight_decay=decoupled, criterion=criterion)
     load_best(net, os.path.join(params_path, f'epoch_{best_epoch}.params'))
     net.eval()
-    test_loss = eval_batches(net, test_x, test_y, bs, nn.SmoothL1Loss())
+    test_loss = eval_batches(net, test_x, test_y, bs, criterion)
     if rank == 0:
         log(f'Final Test Loss: {test_loss:.4f}')
     return {"best_epoch": best_epoch, "best_val": best_val, "test_loss": test_loss, "history": history,
@@ -567,6 +641,12 @@ def main(argv=None):
     ap.add_argument("--weight-decay", type=float, default=None,
                     help="Adam weight decay (overrides [Training] weight_decay; AdamW style with "
                          "[Training] decoupled_weight_decay = true)")
+    ap.add_argument("--loss", default=None,
+                    help="criterion on the HIP path: smooth_l1, huber, mae, mse, masked_mae, masked_mse "
+                         "(overrides [Training] loss_function; default: torch's SmoothL1Loss)")
+    ap.add_argument("--missing-value", type=float, default=None,
+                    help="targets equal to this value (nan: NaN targets) are left out of the loss and its "
+                         "gradient (overrides [Training] missing_value)")
     a = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
@@ -577,7 +657,7 @@ def main(argv=None):
     try:
         run(a.config, epochs=a.epochs, double_step=not a.no_double_step, dropout=a.dropout,
             max_batches=a.max_batches, root=a.out_root, max_grad_norm=a.max_grad_norm,
-            weight_decay=a.weight_decay)
+            weight_decay=a.weight_decay, loss=a.loss, missing_value=a.missing_value)
     finally:
         if world > 1:
             dist.destroy_process_group()

@@ -348,6 +348,62 @@ int dstagnn_grad_scale(const dstagnn_adam_seg* segs, const int64_t* chunks, int 
                        float max_norm, dstagnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Training criterion and test-set scores (loss.hip).
+ *
+ * The criterion of train_DSTAGNN_my.py:132 (`nn.SmoothL1Loss()`) and its use at :156-157
+ * (loss, loss.backward()), mean reduction, one launch per direction, plus the masked variants
+ * the model family uses for series with gaps.  Per element, d = y - target in fp32:
+ *   DSTAGNN_LOSS_SMOOTH_L1  |d| < param: 0.5 d^2 / param, else |d| - 0.5 param   (param = beta;
+ *                           beta = 0 is DSTAGNN_LOSS_MAE)
+ *   DSTAGNN_LOSS_HUBER      |d| <= param: 0.5 d^2, else param (|d| - 0.5 param)   (param = delta)
+ *   DSTAGNN_LOSS_MAE        |d|          (derivative sign(d), sign(0) = 0)
+ *   DSTAGNN_LOSS_MSE        d^2
+ * An entry is valid under DSTAGNN_MASK_NONE always, under DSTAGNN_MASK_NEQ when
+ * target != null_val, under DSTAGNN_MASK_NAN when target is not NaN (DSTAGNN_MASK_NEQ with a
+ * NaN null_val means DSTAGNN_MASK_NAN).  loss = sum over valid entries / their count; no valid
+ * entry: loss 0, gradient 0.  Invalid entries are selected out, never multiplied by zero: a NaN
+ * target under the NaN mask leaves the loss finite and its gradient entry exactly 0.  A NaN
+ * prediction at a valid entry makes the loss NaN.
+ *
+ * dstagnn_loss_forward: y, target (n floats) -> loss (one float), stat (two doubles: the fp64
+ * sum of the terms and the valid count).  Terms in fp32, every add in fp64, fixed order: the
+ * same bits on every call.  scratch: dstagnn_loss_scratch_bytes(n) bytes of device memory
+ * (dstagnn_loss_tile_elems() elements per workgroup, the grid capped).
+ * dstagnn_loss_backward: dy[i] = gout * l'(d_i) / count on valid entries, 0 elsewhere; count is
+ * read from the forward's stat and gout (one float on the device, the upstream gradient; NULL
+ * means 1) on the device: no host synchronisation.  Recomputes d from y and target.
+ * Arguments are checked before anything touches the device: a null pointer, n outside
+ * [1, 2^31), an unknown kind or mask mode, a negative or NaN param -> DSTAGNN_E_ARG.
+ *
+ * dstagnn_metrics_accumulate: pred, target (rows, P) -> table (P, 4) doubles on the device, a
+ * RUNNING table the call adds to (zero it to start): per horizon p (the last axis) sum |e|,
+ * sum e^2, sum over target != null_val of |e / target|, count of target != null_val, with
+ * e = pred - target and e / target in fp32 (as lib/utils1.py:418-431 and lib/metrics.py:6-17
+ * compute them on the host), the sums in fp64 in a fixed order (no atomics on floats: the same
+ * bits on every call).  A NaN null_val counts the non-NaN targets.  MAE_p = table[p][0] / rows,
+ * RMSE_p = sqrt(table[p][1] / rows), MAPE_p = 100 table[p][2] / table[p][3] (0 where the count
+ * is 0).  1 <= P <= 256 and rows * P < 2^31, else DSTAGNN_E_SHAPE.  scratch:
+ * dstagnn_metrics_scratch_bytes(rows, P) bytes.
+ * ------------------------------------------------------------------------------------- */
+enum { DSTAGNN_LOSS_SMOOTH_L1 = 0, DSTAGNN_LOSS_HUBER = 1, DSTAGNN_LOSS_MAE = 2, DSTAGNN_LOSS_MSE = 3 };
+enum { DSTAGNN_MASK_NONE = 0, DSTAGNN_MASK_NEQ = 1, DSTAGNN_MASK_NAN = 2 };
+typedef struct {
+  int kind;       /* DSTAGNN_LOSS_* */
+  float param;    /* beta (smooth_l1) / delta (huber); ignored by mae / mse, still >= 0 */
+  int mask_mode;  /* DSTAGNN_MASK_* */
+  float null_val; /* DSTAGNN_MASK_NEQ only */
+} dstagnn_loss_cfg;
+int dstagnn_loss_tile_elems(void);
+int64_t dstagnn_loss_scratch_bytes(int64_t n);
+int dstagnn_loss_forward(const dstagnn_loss_cfg* cfg, int64_t n, const float* y, const float* target, float* loss,
+                         double* stat, void* scratch, size_t scratch_bytes, dstagnn_stream_t stream);
+int dstagnn_loss_backward(const dstagnn_loss_cfg* cfg, int64_t n, const float* y, const float* target,
+                          const double* stat, const float* gout, float* dy, dstagnn_stream_t stream);
+int64_t dstagnn_metrics_scratch_bytes(int64_t rows, int P);
+int dstagnn_metrics_accumulate(int64_t rows, int P, const float* pred, const float* target, float null_val,
+                               double* table, void* scratch, size_t scratch_bytes, dstagnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Graph builders (stag.hip).  fp64 throughout, like the reference's numpy/scipy code.
  * ------------------------------------------------------------------------------------- */
 
