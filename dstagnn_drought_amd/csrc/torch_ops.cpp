@@ -15,6 +15,9 @@
 //   dstagnn::head_fwd/bwd   DSTAGNN_submodule's cat + final_conv + final_fc (:272-280)
 //   dstagnn::loss_fwd/bwd   the criterion (train_DSTAGNN_my.py:132, :156-157) and its masked variants
 //   dstagnn::metrics_update per-horizon MAE / RMSE / MAPE sums on the device (lib/utils1.py:418-431)
+//   dstagnn::window_gather  a batch's input windows and targets cut from the raw series, transposed
+//                           and z-scored (prepareData.py:63-161 per batch instead of once per label)
+//   dstagnn::window_stats   the training windows' mean / std from the raw series (prepareData.py:149-161)
 //   dstagnn::gemm_f32       the strided f32-MFMA GEMM (tests / tools)
 //   dstagnn::colsum         the fixed-order column-sum reduction (bias / LayerNorm affine grads; tests)
 //   dstagnn::stag_* / emd_dense / fast_stag_distances / graph_topk   the graph builders
@@ -977,6 +980,69 @@ void metrics_update(const Tensor& pred, const Tensor& target, double null_val, T
 }
 
 // -------------------------------------------------------------------------------------
+// training windows from the raw series (windows.hip)
+// -------------------------------------------------------------------------------------
+bool series_f64(const Tensor& series, const char* who) {
+  TORCH_CHECK(series.defined() && series.is_cuda(), who, ": series must be a HIP device tensor (there is no CPU path)");
+  TORCH_CHECK(series.scalar_type() == at::kFloat || series.scalar_type() == at::kDouble, who,
+              ": series must be float32 or float64, got ", series.scalar_type());
+  TORCH_CHECK(series.dim() == 3 && series.is_contiguous(), who, ": series must be a contiguous (L, N, F), got ",
+              series.sizes());
+  TORCH_CHECK(series.numel() > 0, who, ": empty series ", series.sizes());
+  return series.scalar_type() == at::kDouble;
+}
+
+// series (L, N, F), rel (Tin) int32, labels (S) int64, idx (B) int64, mean / std (F) of the
+// series' dtype -> (x (B, N, F, Tin), y (B, N, P)) fp32; one launch, no host sync
+std::tuple<Tensor, Tensor> window_gather(const Tensor& series, const Tensor& rel, const Tensor& labels,
+                                         const Tensor& idx, const Tensor& mean, const Tensor& std, int64_t P) {
+  const bool f64 = series_f64(series, "window_gather");
+  check_dev(rel, at::kInt, "rel");
+  check_dev(labels, at::kLong, "labels");
+  check_dev(idx, at::kLong, "idx");
+  check_dev(mean, series.scalar_type(), "mean");
+  check_dev(std, series.scalar_type(), "std");
+  const int64_t L = series.size(0), N = series.size(1), F = series.size(2), Tin = rel.numel(), B = idx.numel();
+  TORCH_CHECK(rel.dim() == 1 && labels.dim() == 1 && idx.dim() == 1, "window_gather: rel, labels and idx must be 1-D");
+  TORCH_CHECK(mean.numel() == F && std.numel() == F, "window_gather: mean and std must hold F = ", F, " values, got ",
+              mean.sizes(), " and ", std.sizes());
+  TORCH_CHECK(Tin >= 1 && labels.numel() >= 1 && P >= 1, "window_gather: empty rel / labels, or P < 1");
+  for (const Tensor* t : {&rel, &labels, &idx, &mean, &std})
+    TORCH_CHECK(t->device() == series.device(), "window_gather: every tensor must be on the series' device");
+  TORCH_CHECK(std::max({L, N, F, Tin, P, B}) <= INT32_MAX, "window_gather: a dimension exceeds int32");
+  c10::DeviceGuard guard(series.device());
+  Tensor x = at::empty({B, N, F, Tin}, f32(series)), y = at::empty({B, N, P}, f32(series));
+  if (B == 0) return {x, y};
+  check_rc(dstagnn_window_gather(f64, series.data_ptr(), L, (int)N, (int)F, rel.data_ptr<int32_t>(), (int)Tin, (int)P,
+                                 labels.data_ptr<int64_t>(), labels.numel(), idx.data_ptr<int64_t>(), (int)B,
+                                 mean.data_ptr(), std.data_ptr(), x.data_ptr<float>(), y.data_ptr<float>(),
+                                 stream_of(series)),
+           "dstagnn_window_gather");
+  return {x, y};
+}
+
+// series (L, N, F), w (L) int32 -> (2, F) fp64 {mean, std}; wtotal = N * sum(w) (host-known)
+Tensor window_stats(const Tensor& series, const Tensor& w, double wtotal) {
+  const bool f64 = series_f64(series, "window_stats");
+  check_dev(w, at::kInt, "w");
+  const int64_t L = series.size(0), N = series.size(1), F = series.size(2);
+  TORCH_CHECK(w.dim() == 1 && w.numel() == L, "window_stats: w must hold one weight per time step (", L, "), got ",
+              w.sizes());
+  TORCH_CHECK(w.device() == series.device(), "window_stats: w on another device");
+  TORCH_CHECK(N <= INT32_MAX && F <= INT32_MAX, "window_stats: a dimension exceeds int32");
+  c10::DeviceGuard guard(series.device());
+  const int64_t sb = std::max<int64_t>(dstagnn_window_stats_scratch_bytes(L, (int)F), 16);
+  Tensor stats = at::empty({2, F}, series.options().dtype(at::kDouble));
+  Tensor scratch = at::empty({sb / 8}, series.options().dtype(at::kDouble));
+  check_rc(dstagnn_window_stats(f64, series.data_ptr(), L, (int)N, (int)F, w.data_ptr<int32_t>(), wtotal,
+                                stats.data_ptr<double>(), scratch.data_ptr<double>(), (size_t)sb, stream_of(series)),
+           "dstagnn_window_stats");
+  return stats;
+}
+
+int64_t window_tile_nodes(int64_t F, int64_t Tin) { return dstagnn_window_tile_nodes((int)F, (int)Tin); }
+
+// -------------------------------------------------------------------------------------
 // graph builders (fp64)
 // -------------------------------------------------------------------------------------
 // data (T,N,F) -> (xhat (N,T,F), p (N,T), psum (N))
@@ -1128,6 +1194,10 @@ TORCH_LIBRARY(dstagnn, m) {
   m.def("loss_bwd(Tensor y, Tensor target, Tensor stat, Tensor? gout, int kind, float param, int mask_mode, "
         "float null_val) -> Tensor");
   m.def("metrics_update(Tensor pred, Tensor target, float null_val, Tensor(a!) table) -> ()");
+  m.def("window_gather(Tensor series, Tensor rel, Tensor labels, Tensor idx, Tensor mean, Tensor std, int P) "
+        "-> (Tensor, Tensor)");
+  m.def("window_stats(Tensor series, Tensor w, float wtotal) -> Tensor");
+  m.def("window_tile_nodes(int F, int Tin) -> int", window_tile_nodes);
   m.def("stag_prep(Tensor data) -> (Tensor, Tensor, Tensor)");
   m.def("stag_emd_pairs(Tensor xhat, Tensor p, Tensor psum, Tensor pairs, bool with_pivots) -> (Tensor, Tensor, Tensor)");
   m.def("stag_emd_lds_bytes(int T, int F) -> int", stag_emd_lds_bytes);
@@ -1168,6 +1238,8 @@ TORCH_LIBRARY_IMPL(dstagnn, CUDA, m) {
   m.impl("loss_fwd", loss_fwd);
   m.impl("loss_bwd", loss_bwd);
   m.impl("metrics_update", metrics_update);
+  m.impl("window_gather", window_gather);
+  m.impl("window_stats", window_stats);
   m.impl("stag_prep", stag_prep);
   m.impl("stag_emd_pairs", stag_emd_pairs);
   m.impl("emd_dense", emd_dense);

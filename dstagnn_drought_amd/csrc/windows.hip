@@ -1,0 +1,285 @@
+// windows.hip — the data side of a training step on the GPU (gfx950): a batch's input windows and
+// targets cut straight from the raw (L, N, F) series, and the z-score statistics of a split.
+// Replaces, per batch, what prepareData.py materialises once for every label position
+// (prepareData.py:63-147 read_and_generate_dataset, :149-161 normalization) and what
+// lib/utils1.py:294-343 load_graphdata_channel1 then copies to the device whole.
+//
+//   window_gather_kernel<S>  one launch per batch, S = the series' dtype (float / double).
+//       x[b, n, f, t] = float((S(series[label_b + rel[t], n, f]) - mean[f]) / std[f])
+//       y[b, n, p]    = float(series[label_b + p, n, F - 1]),  label_b = labels[idx[b]]
+//     (subtraction and division in S, one rounding to fp32 at the end: numpy's
+//     `(x - mean) / std` followed by `.type(torch.FloatTensor)`).  A workgroup owns a tile of TN
+//     consecutive nodes of one sample.  For a fixed t the tile's source is ONE contiguous run of
+//     tn F elements (read with consecutive lanes on consecutive elements); its destination in
+//     x[b] is ONE contiguous run of tn F Tin floats.  The transpose happens in LDS: element
+//     (e, t), e = nl F + f, is stored at the position o = e Tin + t it has in the output run,
+//     at address o + o / 32 (one pad dword per 32: the stores of one row are Tin dwords apart,
+//     a 4-way (Tin = 12) to 16-way (Tin = 144) conflict on the linear image, 2-way and at most
+//     3-way on the padded one; the four dwords a lane then collects for its float4 sit at
+//     4 l + j + l / 8: the 32 lanes of a group on 32 different banks, 2-way at worst behind a
+//     scalar head; counted lane by lane in DESIGN.md §12).  The run goes out as
+//     float4 from the first 16-byte boundary on, with a scalar head and tail around it
+//     (N F Tin odd: x[b] itself is not 16-byte aligned for odd b).  The targets take the same
+//     road through a second, small LDS image (their source is strided by F, their run by P).
+//     An idx[b] outside [0, S) or a time step outside [0, L) is never dereferenced: that sample
+//     (that row) is NaN.  All offsets are 64-bit.
+//   window_stats_kernel<S>   the training split's mean and standard deviation (ddof = 0) per
+//     feature over its windows, axes (0, 1, 3), as the weighted moments of the raw series:
+//     w[s] = how many (training label, window offset) pairs land on time step s (host-made, L
+//     int32).  Two launches: sum w x, then sum w (x - mean)^2 around that mean (never the
+//     sum-of-squares form).  A workgroup takes whole time steps s = wg, wg + grid, ... (w[s] is
+//     uniform; a step of weight 0 is skipped unread), thread t of the first (256 / F) F reads
+//     elements t, t + A, ... of the step (its feature never changes), every add in fp64.  The
+//     workgroup folds its threads of equal feature in thread order, hands {F sums} off
+//     (handoff.hpp) and the last arrival adds the partials in workgroup order: the same bits on
+//     every call.  stats = {mean[F], std[F]} in fp64.
+#include <cmath>
+
+#include "handoff.hpp"
+#include "ops.hpp"
+
+namespace {
+
+constexpr int kWinThreads = 256, kWinUnroll = 4;
+constexpr int kWinImageFloats = 8192;  // the padded x image of a tile: <= 32 KiB
+constexpr int kWinMaxTile = 64;        // nodes; F = 1 rows are then 64 elements, one per lane
+constexpr int kWinMaxLds = 64 << 10;   // x image + targets + row table: two workgroups per CU at worst
+constexpr int kStatThreads = 256, kStatMaxWg = 512, kStatMaxF = 256;
+
+__host__ __device__ __forceinline__ int win_pad(int o) { return o + (o >> 5); }
+
+// nodes per tile: the most whose padded image fits kWinImageFloats, at most kWinMaxTile
+int win_tile_nodes(int F, int Tin) {
+  const int64_t per = (int64_t)F * Tin;  // floats of one node
+  const int64_t tn = (int64_t)kWinImageFloats * 32 / 33 / per;
+  return (int)(tn < 1 ? 1 : tn > kWinMaxTile ? kWinMaxTile : tn);
+}
+
+struct WinArgs {
+  const void* series;
+  int64_t L;
+  int N, F, Tin, P, TN, ntile;
+  int ximage;  // floats of the padded x image (the target image starts there)
+  const int32_t* rel;
+  const int64_t* labels;
+  int64_t S;
+  const int64_t* idx;
+  const void *mean, *std;
+  float *x, *y;
+};
+
+template <typename S>
+__global__ __launch_bounds__(kWinThreads) void window_gather_kernel(WinArgs a) {
+  extern __shared__ float win_lds[];
+  float* xim = win_lds;
+  float* yim = win_lds + a.ximage;
+  int* srow = reinterpret_cast<int*>(yim + a.TN * a.P);  // time step of row t, -1: not in the series
+  const int tid = threadIdx.x;
+  const int b = blockIdx.x / a.ntile, tile = blockIdx.x - b * a.ntile;
+  const int n0 = tile * a.TN, tn = min(a.TN, a.N - n0);
+  const int cnt = tn * a.F, run = cnt * a.Tin, yrun = tn * a.P;
+  const S* __restrict__ series = static_cast<const S*>(a.series);
+  const S* __restrict__ mean = static_cast<const S*>(a.mean);
+  const S* __restrict__ sd = static_cast<const S*>(a.std);
+  const int64_t NF = (int64_t)a.N * a.F;
+  const float nanv = __builtin_nanf("");
+
+  const int64_t i = a.idx[b];
+  const bool ok = i >= 0 && i < a.S;
+  const int64_t label = ok ? a.labels[i] : 0;
+  for (int t = tid; t < a.Tin; t += kWinThreads) {
+    const int64_t s = label + a.rel[t];
+    srow[t] = ok && s >= 0 && s < a.L ? (int)s : -1;
+  }
+  __syncthreads();
+
+  // stage: row t of the tile is cnt consecutive elements; j = t cnt + e walks the rows in order
+  // (t, e, f = e % F) of j are carried from j to j + 256 without a division: cnt is a multiple of F
+  const S* __restrict__ src = series + (int64_t)n0 * a.F;
+  const int tstep = kWinThreads / cnt, estep = kWinThreads - tstep * cnt, fstep = estep % a.F;  // (uniform)
+  int t = tid / cnt, e = tid - t * cnt, f = e % a.F;
+  for (int j0 = tid; j0 < run; j0 += kWinThreads * kWinUnroll) {
+    S v[kWinUnroll];
+    int tt[kWinUnroll], ee[kWinUnroll], ff[kWinUnroll], ss[kWinUnroll];
+#pragma unroll
+    for (int u = 0; u < kWinUnroll; ++u) {
+      tt[u] = t, ee[u] = e, ff[u] = f;
+      ss[u] = j0 + u * kWinThreads < run ? srow[t] : -1;
+      v[u] = ss[u] >= 0 ? src[(int64_t)ss[u] * NF + e] : S(0);
+      t += tstep, e += estep, f += fstep;
+      if (e >= cnt) e -= cnt, ++t;
+      if (f >= a.F) f -= a.F;
+    }
+#pragma unroll
+    for (int u = 0; u < kWinUnroll; ++u) {
+      if (j0 + u * kWinThreads < run)
+        xim[win_pad(ee[u] * a.Tin + tt[u])] = ss[u] >= 0 ? (float)((v[u] - mean[ff[u]]) / sd[ff[u]]) : nanv;
+    }
+  }
+  // the targets: steps label .. label + P - 1 of the last feature, un-normalised
+  const bool tgt = ok && label >= 0 && label + a.P <= a.L;
+  for (int j = tid; j < yrun; j += kWinThreads) {
+    const int p = j / tn, nl = j - p * tn;
+    yim[nl * a.P + p] = tgt ? (float)src[(label + p) * NF + (int64_t)nl * a.F + (a.F - 1)] : nanv;
+  }
+  __syncthreads();
+
+  // x[b, n0 .. n0 + tn): one run of `run` floats; float4 from its first 16-byte boundary
+  float* __restrict__ xo = a.x + ((int64_t)b * a.N + n0) * a.F * a.Tin;
+  const int head = min(run, (int)((4 - ((reinterpret_cast<uintptr_t>(xo) >> 2) & 3)) & 3));
+  const int nvec = (run - head) >> 2;
+  if (tid < head) xo[tid] = xim[win_pad(tid)];
+  float4* __restrict__ x4 = reinterpret_cast<float4*>(xo + head);
+  for (int q = tid; q < nvec; q += kWinThreads) {
+    const int o = head + 4 * q;
+    float4 r;
+    r.x = xim[win_pad(o)], r.y = xim[win_pad(o + 1)], r.z = xim[win_pad(o + 2)], r.w = xim[win_pad(o + 3)];
+    x4[q] = r;
+  }
+  {
+    const int o = head + 4 * nvec + tid;
+    if (o < run) xo[o] = xim[win_pad(o)];
+  }
+  float* __restrict__ yo = a.y + ((int64_t)b * a.N + n0) * a.P;
+  for (int j = tid; j < yrun; j += kWinThreads) yo[j] = yim[j];
+}
+
+// pass 0: stats[f] = sum w x / wtotal; pass 1: stats[F + f] = sqrt(sum w (x - stats[f])^2 / wtotal)
+template <typename S>
+__global__ __launch_bounds__(kStatThreads) void window_stats_kernel(const S* __restrict__ series, int64_t L,
+                                                                  int64_t NF, int F, const int32_t* __restrict__ w,
+                                                                  int pass, double wtotal, double* __restrict__ part,
+                                                                  int* ticket, double* stats) {
+  __shared__ double red[kStatThreads];
+  __shared__ int last;
+  const int t = threadIdx.x;
+  const int RL = kStatThreads / F, A = RL * F;  // threads that read; e = t + k A keeps feature t % F
+  double acc = 0.0;
+  if (t < A) {
+    const double m = pass ? stats[t % F] : 0.0;
+    for (int64_t s = blockIdx.x; s < L; s += gridDim.x) {
+      const int wi = w[s];
+      if (wi == 0) continue;  // (uniform)
+      const double wd = (double)wi;
+      const S* __restrict__ row = series + s * NF;
+      if (pass) {
+        for (int64_t e = t; e < NF; e += A) {
+          const double d = (double)row[e] - m;
+          acc += wd * (d * d);
+        }
+      } else {
+        for (int64_t e = t; e < NF; e += A) acc += wd * (double)row[e];
+      }
+    }
+  }
+  red[t] = acc;
+  __syncthreads();
+  if (t < F) {
+    double a = 0.0;
+    for (int r = 0; r < RL; ++r) a += red[r * F + t];
+    st_agent(part + (int64_t)blockIdx.x * F + t, a);
+  }
+  if (!last_arrival(ticket, (int)gridDim.x, &last)) return;
+  if (t < F) {
+    double a = 0.0;
+    for (int64_t k = 0; k < (int64_t)gridDim.x; ++k) a += ld_agent(part + k * F + t);
+    if (pass) stats[F + t] = sqrt(a / wtotal);
+    else stats[t] = a / wtotal;
+  }
+}
+
+int64_t stats_grid(int64_t L) { return L < 1 ? 1 : L > kStatMaxWg ? kStatMaxWg : L; }
+
+}  // namespace
+
+int dstagnn_window_tile_nodes(int F, int Tin) { return F < 1 || Tin < 1 ? 0 : win_tile_nodes(F, Tin); }
+
+int64_t dstagnn_window_gather_lds_bytes(int F, int Tin, int P) {
+  if (F < 1 || Tin < 1 || P < 1) return 0;
+  const int64_t TN = win_tile_nodes(F, Tin);
+  const int64_t run = TN * F * Tin;
+  return 4 * (run + (run >> 5) + 1 + TN * P + Tin);
+}
+
+int dstagnn_window_gather(int series_f64, const void* series, int64_t L, int N, int F, const int32_t* rel, int Tin,
+                          int P, const int64_t* labels, int64_t S, const int64_t* idx, int B, const void* mean,
+                          const void* std, float* x, float* y, dstagnn_stream_t stream) {
+  if (!series || !rel || !labels || !idx || !mean || !std || !x || !y) {
+    set_last_error("window_gather: null series / rel / labels / idx / mean / std / x / y");
+    return DSTAGNN_E_ARG;
+  }
+  if (L < 1 || L >= (1ll << 31) || N < 1 || F < 1 || Tin < 1 || P < 1 || S < 1 || B < 1) {
+    set_last_error("window_gather: L (< 2^31), N, F, Tin, P, S and B must all be >= 1");
+    return DSTAGNN_E_SHAPE;
+  }
+  const int64_t lds = dstagnn_window_gather_lds_bytes(F, Tin, P);
+  if ((int64_t)F * Tin >= (1 << 24) || lds > kWinMaxLds) {
+    set_last_error("window_gather: one node's window (F * Tin floats) and its targets need " + std::to_string(lds) +
+                   " bytes of LDS, over " + std::to_string(kWinMaxLds));
+    return DSTAGNN_E_SHAPE;
+  }
+  WinArgs a{};
+  a.series = series, a.L = L, a.N = N, a.F = F, a.Tin = Tin, a.P = P;
+  a.TN = win_tile_nodes(F, Tin);
+  a.ntile = (N + a.TN - 1) / a.TN;
+  const int64_t run = (int64_t)a.TN * F * Tin;
+  a.ximage = (int)(run + (run >> 5) + 1);
+  a.rel = rel, a.labels = labels, a.S = S, a.idx = idx, a.mean = mean, a.std = std, a.x = x, a.y = y;
+  const int64_t grid = (int64_t)B * a.ntile;
+  if (grid >= (1ll << 31)) {
+    set_last_error("window_gather: B * tiles must be below 2^31");
+    return DSTAGNN_E_SHAPE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (series_f64)
+    hipLaunchKernelGGL(window_gather_kernel<double>, dim3((unsigned)grid), dim3(kWinThreads), (size_t)lds, st, a);
+  else
+    hipLaunchKernelGGL(window_gather_kernel<float>, dim3((unsigned)grid), dim3(kWinThreads), (size_t)lds, st, a);
+  DS_CHECK_LAUNCH();
+  return 0;
+}
+
+int64_t dstagnn_window_stats_scratch_bytes(int64_t L, int F) {
+  if (L < 1 || F < 1 || F > kStatMaxF) return 0;
+  return stats_grid(L) * (int64_t)F * (int64_t)sizeof(double);
+}
+
+int dstagnn_window_stats(int series_f64, const void* series, int64_t L, int N, int F, const int32_t* w, double wtotal,
+                         double* stats, void* scratch, size_t scratch_bytes, dstagnn_stream_t stream) {
+  if (!series || !w || !stats || !scratch) {
+    set_last_error("window_stats: null series / w / stats / scratch");
+    return DSTAGNN_E_ARG;
+  }
+  if (F < 1 || F > kStatMaxF || L < 1 || N < 1) {
+    set_last_error("window_stats: L, N >= 1 and F in [1, 256], got F = " + std::to_string(F));
+    return DSTAGNN_E_SHAPE;
+  }
+  if (!(wtotal > 0.0)) {
+    set_last_error("window_stats: the total weight must be positive (an empty training split?)");
+    return DSTAGNN_E_ARG;
+  }
+  if (scratch_bytes < (size_t)dstagnn_window_stats_scratch_bytes(L, F)) {
+    set_last_error("window_stats: scratch smaller than dstagnn_window_stats_scratch_bytes(L, F)");
+    return DSTAGNN_E_SPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  int* ticket = stream_counters(st, 1);
+  if (!ticket) {
+    set_last_error("window_stats: no ticket counter for this stream");
+    return DSTAGNN_E_ARG;
+  }
+  const dim3 grid((unsigned)stats_grid(L));
+  const int64_t NF = (int64_t)N * F;
+  for (int pass = 0; pass < 2; ++pass) {  // the second launch reads the first one's mean (stream order)
+    if (series_f64)
+      hipLaunchKernelGGL(window_stats_kernel<double>, grid, dim3(kStatThreads), 0, st,
+                         static_cast<const double*>(series), L, NF, F, w, pass, wtotal,
+                         static_cast<double*>(scratch), ticket, stats);
+    else
+      hipLaunchKernelGGL(window_stats_kernel<float>, grid, dim3(kStatThreads), 0, st,
+                         static_cast<const float*>(series), L, NF, F, w, pass, wtotal,
+                         static_cast<double*>(scratch), ticket, stats);
+    DS_CHECK_LAUNCH();
+  }
+  return 0;
+}

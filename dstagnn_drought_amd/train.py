@@ -25,6 +25,9 @@ process per GPU with torch.distributed over RCCL:
     first epoch visits samples in the reference's order.
   * the missing ``graph`` key of the PEMS03/07/08 configs (quirk 16: KeyError in the
     reference) defaults to 'AG'.
+  * with ``stream_windows`` (a [Training] key, ``--stream-windows``) the raw series stays on the
+    device once and every batch's windows are gathered from it in one launch
+    (windows.WindowedSeries) instead of loading the prepared, ``len_input``-times larger file.
   * the criterion is the reference's ``nn.SmoothL1Loss()`` unless the configuration
     (loss_options()) or ``--loss`` / ``--missing-value`` name one: then loss.HipLoss, on the
     HIP path, optionally leaving targets equal to a missing value out of the loss.
@@ -94,9 +97,44 @@ class DeviceBatches:
             yield self.x.index_select(0, idx), self.y.index_select(0, idx)
 
 
+class StreamBatches(DeviceBatches):
+    """DeviceBatches over the ``x`` / ``y`` of a windows.WindowedSeries split: the same
+    permutation, global-RNG draws, sharding and wrap-around padding (DeviceBatches._order), each
+    batch gathered from the raw series in ONE launch instead of two
+    index_selects from materialised tensors."""
+
+    def __init__(self, x, y, batch_size, shuffle, rank=0, world=1):
+        if not _is_streamed(x) or not _is_streamed(y) or (x.owner, x.name) != (y.owner, y.name):
+            raise ValueError("StreamBatches: x and y must be the two arrays of one WindowedSeries split")
+        super().__init__(x, y, batch_size, shuffle, rank, world)
+
+    def __iter__(self):
+        perm = self._order().to(self.x.device)
+        for i in range(0, perm.numel(), self.bs):
+            yield self.x.owner.batch(self.x.name, perm[i:i + self.bs])
+
+
+def _is_streamed(t):
+    return hasattr(t, "owner") and hasattr(t.owner, "batch")
+
+
+def make_batches(x, y, batch_size, shuffle, rank=0, world=1):
+    """StreamBatches for the arrays of a WindowedSeries split, DeviceBatches for tensors."""
+    cls = StreamBatches if _is_streamed(x) else DeviceBatches
+    return cls(x, y, batch_size, shuffle, rank, world)
+
+
+def _cut(x, y, b, e):
+    """Samples b .. e of (x, y): views of tensors; one gather launch for a streamed split."""
+    if _is_streamed(x) and _is_streamed(y) and (x.owner, x.name) == (y.owner, y.name):
+        return x.owner.batch(x.name, slice(b, e))
+    return x[b:e], y[b:e]
+
+
 def eval_batches(net, x, y, batch_size, criterion):
     """Mean over batches of the batch-mean loss (train_DSTAGNN_my.py:164-172), with the
-    batches split round-robin over the ranks and the sums all-reduced."""
+    batches split round-robin over the ranks and the sums all-reduced.  x, y: tensors, or the
+    arrays of a windows.WindowedSeries split (each batch then gathered from the raw series)."""
     rank, world = _world()
     iter(torch.utils.data.DataLoader(range(1)))  # the global-RNG draw a DataLoader iteration makes
     n = x.shape[0]
@@ -104,7 +142,8 @@ def eval_batches(net, x, y, batch_size, criterion):
     tot = torch.zeros(2, dtype=torch.float64, device=x.device)
     with torch.no_grad():
         for b in starts[rank::world]:
-            tot[0] += criterion(net(x[b:b + batch_size]), y[b:b + batch_size]).double()
+            xb, yb = _cut(x, y, b, b + batch_size)
+            tot[0] += criterion(net(xb), yb).double()
             tot[1] += 1
     if world > 1:
         dist.all_reduce(tot)
@@ -517,7 +556,9 @@ def fit(net, train_x, train_y, val_x, val_y, *, epochs, start_epoch=0, batch_siz
     same on every rank: the ranks clip alike and their parameters stay equal.
     criterion: training and validation loss (make_criterion(); None: ``nn.SmoothL1Loss()``).  A
     masked criterion divides by the valid count of the rank's own batch and the gradients are
-    then averaged over the ranks: a mean of batch means, as the unmasked path has always been."""
+    then averaged over the ranks: a mean of batch means, as the unmasked path has always been.
+    train_x / train_y / val_x / val_y: HBM-resident tensors, or the ``x`` / ``y`` of
+    windows.WindowedSeries splits (StreamBatches: same sample order, one gather launch per batch)."""
     rank, world = _world()
     criterion = (nn.SmoothL1Loss() if criterion is None else criterion).to(train_x.device)
     optimizer = make_adam(net.parameters(), lr, weight_decay=weight_decay, decoupled=decoupled_weight_decay,
@@ -525,7 +566,7 @@ def fit(net, train_x, train_y, val_x, val_y, *, epochs, start_epoch=0, batch_siz
     reducer = None
     if world > 1:  # block gradients all-reduced beside the backward (attach)
         reducer = GradAllReducer(net.named_parameters(), mask_support=mask_support_of(net)).attach(net)
-    loader = DeviceBatches(train_x, train_y, batch_size, True, rank, world)
+    loader = make_batches(train_x, train_y, batch_size, True, rank, world)
 
     def optimizer_step(reduce=True):  # xm.optimizer_step
         if reducer is not None and reduce:
@@ -578,29 +619,46 @@ def load_best(net, path):
 
 
 def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches=None, root='myexperiments',
-        log=print, max_grad_norm=None, weight_decay=None, loss=None, missing_value=None):
+        log=print, max_grad_norm=None, weight_decay=None, loss=None, missing_value=None, stream_windows=None):
     """Whole script: data, graphs, model, training, best-checkpoint test loss.  The optional
     [Training] keys of training_options() switch clipping / weight decay on; max_grad_norm /
     weight_decay given here override them.  loss / missing_value override the keys of
     loss_options() the same way; the criterion make_criterion() builds from them is used for
-    training, validation and the final test loss."""
+    training, validation and the final test loss.
+    stream_windows (None: the [Training] key ``stream_windows``, off when absent): read the raw
+    ``graph_signal_matrix_filename`` instead of the prepared ``*_dstagnn.npz``, keep it on the
+    device once and gather every batch's windows from it (windows.WindowedSeries); none of the
+    materialised arrays is read or built.  Where the prepared file exists only its ``mean`` and
+    ``std`` are read, and the run sees the inputs of the materialised run bit for bit; otherwise
+    the statistics are computed on the device from the raw series."""
     config = configparser.ConfigParser()
     config.read(config_path)
     dc, tc = config['Data'], config['Training']
     rank, world = _world()
     device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
     seed_torch(1)
-    (train_x, train_loader, train_y, val_x, _, val_y, test_x, _, test_y, mean, std) = \
-        data_io.load_graphdata_channel1(dc['graph_signal_matrix_filename'], int(tc['num_of_hours']),
-                                        int(tc['num_of_days']), int(tc['num_of_weeks']), 'cpu',
-                                        int(tc['batch_size']))
-    next(iter(train_loader))  # the reference probes one batch (:59-61): same RNG draw before the init
+    if stream_windows is None:
+        stream_windows = tc.getboolean('stream_windows', fallback=False)
+    if stream_windows:
+        ws = _windowed_series(dc, tc, device)
+        (train_x, train_y), (val_x, val_y), (test_x, test_y) = ((ws.split(k).x, ws.split(k).y)
+                                                                for k in ('train', 'val', 'test'))
+        # the reference's one-batch probe (:59-61): its draws from the global RNG do not depend on the data
+        next(iter(torch.utils.data.DataLoader(torch.arange(train_x.shape[0]), batch_size=int(tc['batch_size']),
+                                              shuffle=True)))
+    else:
+        (train_x, train_loader, train_y, val_x, _, val_y, test_x, _, test_y, mean, std) = \
+            data_io.load_graphdata_channel1(dc['graph_signal_matrix_filename'], int(tc['num_of_hours']),
+                                            int(tc['num_of_days']), int(tc['num_of_weeks']), 'cpu',
+                                            int(tc['batch_size']))
+        next(iter(train_loader))  # the reference probes one batch (:59-61): same RNG draw before the init
     net = build(config, device)
     set_direct_grads(net)  # the loop only uses loss.backward() + .grad
     if dropout is not None:
         set_dropout(net, dropout)
-    train_x, train_y, val_x, val_y, test_x, test_y = (t.to(device) for t in
-                                                      (train_x, train_y, val_x, val_y, test_x, test_y))
+    if not stream_windows:
+        train_x, train_y, val_x, val_y, test_x, test_y = (t.to(device) for t in
+                                                          (train_x, train_y, val_x, val_y, test_x, test_y))
     params_path = params_path_of(config, root)
     if rank == 0:
         os.makedirs(params_path, exist_ok=True)
@@ -627,6 +685,20 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
             "params_path": params_path, "net": net}
 
 
+def _windowed_series(dc, tc, device):
+    """The configuration's raw series as a windows.WindowedSeries; the prepared file's mean / std
+    where that file exists (np.load reads an .npz per key: the materialised arrays stay on disk)."""
+    from .windows import WindowedSeries
+    raw = dc['graph_signal_matrix_filename']
+    nh, nd, nw = int(tc['num_of_hours']), int(tc['num_of_days']), int(tc['num_of_weeks'])
+    prepared, stats = data_io.dataset_filename(raw, nh, nd, nw) + '.npz', None
+    if os.path.exists(prepared):
+        with np.load(prepared) as f:
+            stats = (f['mean'], f['std'])
+    return WindowedSeries.from_file(raw, nw, nd, nh, int(dc['num_for_predict']),
+                                    points_per_hour=int(dc['points_per_hour']), device=device, stats=stats)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--config", default='configurations/PEMS04_dstagnn.conf', type=str)
@@ -647,6 +719,9 @@ def main(argv=None):
     ap.add_argument("--missing-value", type=float, default=None,
                     help="targets equal to this value (nan: NaN targets) are left out of the loss and its "
                          "gradient (overrides [Training] missing_value)")
+    ap.add_argument("--stream-windows", action="store_true", default=None,
+                    help="cut every batch's windows from the raw series on the device instead of loading the "
+                         "prepared *_dstagnn.npz (overrides [Training] stream_windows)")
     a = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
@@ -657,7 +732,8 @@ def main(argv=None):
     try:
         run(a.config, epochs=a.epochs, double_step=not a.no_double_step, dropout=a.dropout,
             max_batches=a.max_batches, root=a.out_root, max_grad_norm=a.max_grad_norm,
-            weight_decay=a.weight_decay, loss=a.loss, missing_value=a.missing_value)
+            weight_decay=a.weight_decay, loss=a.loss, missing_value=a.missing_value,
+            stream_windows=a.stream_windows)
     finally:
         if world > 1:
             dist.destroy_process_group()

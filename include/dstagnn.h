@@ -404,6 +404,46 @@ int dstagnn_metrics_accumulate(int64_t rows, int P, const float* pred, const flo
                                double* table, void* scratch, size_t scratch_bytes, dstagnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Training windows cut from the raw series on the device (windows.hip): what prepareData.py
+ * (:63-161) materialises once per label position, per batch instead.
+ *
+ * dstagnn_window_gather: ONE launch, no host sync.  series (L, N, F), fp64 when series_f64 else
+ * fp32 (call that type S); rel (Tin) int32 time offsets relative to a label position, in the
+ * order read_and_generate_dataset concatenates its windows (week, day, hour kinds; each kind its
+ * windows oldest first; an offset may be >= 0); labels (S) int64 label positions of a split;
+ * idx (B) int64 positions in that table (a slice of an epoch permutation as it is); mean, std
+ * (F) of type S.  Writes, with label_b = labels[idx[b]],
+ *   x (B, N, F, Tin) fp32:  x[b,n,f,t] = float((S(series[label_b + rel[t], n, f]) - mean[f]) / std[f])
+ *   y (B, N, P)      fp32:  y[b,n,p]   = float(series[label_b + p, n, F - 1])
+ * the subtraction and the (correctly rounded) division in S, rounded to fp32 once at the end: the
+ * operations of numpy's `(x - mean) / std` (prepareData.py:149-161) followed by
+ * `.type(torch.FloatTensor)` (lib/utils1.py:302-312), bit for bit.  The caller validates the
+ * tables (every label + rel[t] and label + p inside [0, L)); the kernel still never reads outside
+ * the series: an idx[b] outside [0, S) makes x[b] and y[b] NaN, a time step outside [0, L) makes
+ * that row NaN.  A workgroup handles dstagnn_window_tile_nodes(F, Tin) consecutive nodes of one
+ * sample (chosen so that its LDS image stays at 32 KiB; dstagnn_window_gather_lds_bytes(F, Tin, P)
+ * is the launch's dynamic LDS, which must not exceed 64 KiB: DSTAGNN_E_SHAPE).  All of L (< 2^31),
+ * N, F, Tin, P, S, B >= 1, else DSTAGNN_E_SHAPE.
+ *
+ * dstagnn_window_stats: the z-score statistics of a training split from the raw series, in fp64.
+ * w (L) int32: the number of (training label, window offset) pairs that land on time step s;
+ * wtotal = N * sum(w).  stats (2 F) fp64 = {mean[F], std[F]} with mean[f] = sum w x / wtotal and
+ * std[f] = sqrt(sum w (x - mean[f])^2 / wtotal) (ddof = 0): numpy's train.mean / train.std over
+ * axes (0, 1, 3) of the materialised windows.  Two launches (the second centres on the first
+ * one's mean), sums in a fixed order: the same bits on every call.  1 <= F <= 256, else
+ * DSTAGNN_E_SHAPE; wtotal > 0, else DSTAGNN_E_ARG.  scratch:
+ * dstagnn_window_stats_scratch_bytes(L, F) bytes.
+ * ------------------------------------------------------------------------------------- */
+int dstagnn_window_tile_nodes(int F, int Tin);
+int64_t dstagnn_window_gather_lds_bytes(int F, int Tin, int P);
+int dstagnn_window_gather(int series_f64, const void* series, int64_t L, int N, int F, const int32_t* rel, int Tin,
+                          int P, const int64_t* labels, int64_t S, const int64_t* idx, int B, const void* mean,
+                          const void* std, float* x, float* y, dstagnn_stream_t stream);
+int64_t dstagnn_window_stats_scratch_bytes(int64_t L, int F);
+int dstagnn_window_stats(int series_f64, const void* series, int64_t L, int N, int F, const int32_t* w, double wtotal,
+                         double* stats, void* scratch, size_t scratch_bytes, dstagnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Graph builders (stag.hip).  fp64 throughout, like the reference's numpy/scipy code.
  * ------------------------------------------------------------------------------------- */
 
