@@ -34,6 +34,13 @@ __device__ __forceinline__ double ld_agent(const double* p) {
 __device__ __forceinline__ void st_agent(double* p, double v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// ... of an int64 partial (an exact count)
+__device__ __forceinline__ long long ld_agent(const long long* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void st_agent(long long* p, long long v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
 // one lane: draw a ticket among n arrivals (step 4, no fence); true for the last arrival
 __device__ __forceinline__ bool ticket_draw(int* cnt, int n) { return atomicAdd(cnt, 1) == n - 1; }

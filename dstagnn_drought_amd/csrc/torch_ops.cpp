@@ -18,7 +18,9 @@
 //   dstagnn::window_gather  a batch's input windows and targets cut from the raw series, transposed
 //                           and z-scored (prepareData.py:63-161 per batch instead of once per label)
 //   dstagnn::window_stats   the training windows' mean / std from the raw series (prepareData.py:149-161)
-//   dstagnn::gemm_f32       the strided f32-MFMA GEMM (tests / tools)
+//   dstagnn::window_stats_masked / window_fill_forward / window_gather_masked   the same for a series
+//                           with gaps: statistics of the observed values, forward fill, in-gather imputation
+//   dstagnn::gemm_f32      the strided f32-MFMA GEMM (tests / tools)
 //   dstagnn::colsum         the fixed-order column-sum reduction (bias / LayerNorm affine grads; tests)
 //   dstagnn::stag_* / emd_dense / fast_stag_distances / graph_topk   the graph builders
 //                           (data/STAG_gen.py:17-129, data/fast_STAG_gen.py:16-74)
@@ -1042,6 +1044,81 @@ Tensor window_stats(const Tensor& series, const Tensor& w, double wtotal) {
 
 int64_t window_tile_nodes(int64_t F, int64_t Tin) { return dstagnn_window_tile_nodes((int)F, (int)Tin); }
 
+// series with gaps: window_stats over the valid elements -> ((2, F) fp64 {mean, std}, (F) int64 valid weight)
+std::tuple<Tensor, Tensor> window_stats_masked(const Tensor& series, const Tensor& w, double null_val) {
+  const bool f64 = series_f64(series, "window_stats_masked");
+  check_dev(w, at::kInt, "w");
+  const int64_t L = series.size(0), N = series.size(1), F = series.size(2);
+  TORCH_CHECK(w.dim() == 1 && w.numel() == L, "window_stats_masked: w must hold one weight per time step (", L,
+              "), got ", w.sizes());
+  TORCH_CHECK(w.device() == series.device(), "window_stats_masked: w on another device");
+  TORCH_CHECK(N <= INT32_MAX && F <= INT32_MAX, "window_stats_masked: a dimension exceeds int32");
+  c10::DeviceGuard guard(series.device());
+  const int64_t sb = std::max<int64_t>(dstagnn_window_stats_masked_scratch_bytes(L, (int)F), 16);
+  Tensor stats = at::empty({2, F}, series.options().dtype(at::kDouble));
+  Tensor wvalid = at::empty({F}, series.options().dtype(at::kLong));
+  Tensor scratch = at::empty({sb / 8}, series.options().dtype(at::kDouble));
+  check_rc(dstagnn_window_stats_masked(f64, series.data_ptr(), L, (int)N, (int)F, w.data_ptr<int32_t>(), null_val,
+                                       stats.data_ptr<double>(), wvalid.data_ptr<int64_t>(), scratch.data_ptr<double>(),
+                                       (size_t)sb, stream_of(series)),
+           "dstagnn_window_stats_masked");
+  return {stats, wvalid};
+}
+
+// the forward fill along time -> (filled (L, N, F), counts (2, F) int64 {missing, filled}); max_gap 0: unlimited
+std::tuple<Tensor, Tensor> window_fill_forward(const Tensor& series, double null_val, int64_t max_gap) {
+  const bool f64 = series_f64(series, "window_fill_forward");
+  const int64_t L = series.size(0), N = series.size(1), F = series.size(2);
+  TORCH_CHECK(max_gap >= 0, "window_fill_forward: max_gap must be >= 0 (0: unlimited), got ", max_gap);
+  TORCH_CHECK(N <= INT32_MAX && F <= INT32_MAX, "window_fill_forward: a dimension exceeds int32");
+  c10::DeviceGuard guard(series.device());
+  const int64_t sb = std::max<int64_t>(dstagnn_window_fill_scratch_bytes(L, (int)N, (int)F), 16);
+  Tensor filled = at::empty_like(series);
+  Tensor counts = at::empty({2, F}, series.options().dtype(at::kLong));
+  Tensor scratch = at::empty({(sb + 3) / 4}, series.options().dtype(at::kInt));
+  check_rc(dstagnn_window_fill_forward(f64, series.data_ptr(), L, (int)N, (int)F, null_val, max_gap, filled.data_ptr(),
+                                       counts.data_ptr<int64_t>(), scratch.data_ptr<int32_t>(), (size_t)sb,
+                                       stream_of(series)),
+           "dstagnn_window_fill_forward");
+  return {filled, counts};
+}
+
+int64_t window_fill_chunk() { return dstagnn_window_fill_chunk(); }
+int64_t window_fill_cols() { return dstagnn_window_fill_cols(); }
+
+// window_gather with the inputs from xsrc (missing -> +0.0f) and the raw targets from ysrc
+std::tuple<Tensor, Tensor> window_gather_masked(const Tensor& xsrc, const Tensor& ysrc, const Tensor& rel,
+                                                const Tensor& labels, const Tensor& idx, const Tensor& mean,
+                                                const Tensor& std, int64_t P, double null_val) {
+  const bool f64 = series_f64(ysrc, "window_gather_masked");
+  TORCH_CHECK(series_f64(xsrc, "window_gather_masked") == f64 && xsrc.sizes() == ysrc.sizes(),
+              "window_gather_masked: xsrc and ysrc must have one dtype and shape, got ", xsrc.sizes(), " and ",
+              ysrc.sizes());
+  check_dev(rel, at::kInt, "rel");
+  check_dev(labels, at::kLong, "labels");
+  check_dev(idx, at::kLong, "idx");
+  check_dev(mean, ysrc.scalar_type(), "mean");
+  check_dev(std, ysrc.scalar_type(), "std");
+  const int64_t L = ysrc.size(0), N = ysrc.size(1), F = ysrc.size(2), Tin = rel.numel(), B = idx.numel();
+  TORCH_CHECK(rel.dim() == 1 && labels.dim() == 1 && idx.dim() == 1,
+              "window_gather_masked: rel, labels and idx must be 1-D");
+  TORCH_CHECK(mean.numel() == F && std.numel() == F, "window_gather_masked: mean and std must hold F = ", F,
+              " values, got ", mean.sizes(), " and ", std.sizes());
+  TORCH_CHECK(Tin >= 1 && labels.numel() >= 1 && P >= 1, "window_gather_masked: empty rel / labels, or P < 1");
+  for (const Tensor* t : {&xsrc, &rel, &labels, &idx, &mean, &std})
+    TORCH_CHECK(t->device() == ysrc.device(), "window_gather_masked: every tensor must be on the series' device");
+  TORCH_CHECK(std::max({L, N, F, Tin, P, B}) <= INT32_MAX, "window_gather_masked: a dimension exceeds int32");
+  c10::DeviceGuard guard(ysrc.device());
+  Tensor x = at::empty({B, N, F, Tin}, f32(ysrc)), y = at::empty({B, N, P}, f32(ysrc));
+  if (B == 0) return {x, y};
+  check_rc(dstagnn_window_gather_masked(f64, xsrc.data_ptr(), ysrc.data_ptr(), L, (int)N, (int)F,
+                                        rel.data_ptr<int32_t>(), (int)Tin, (int)P, labels.data_ptr<int64_t>(),
+                                        labels.numel(), idx.data_ptr<int64_t>(), (int)B, mean.data_ptr(), std.data_ptr(),
+                                        null_val, x.data_ptr<float>(), y.data_ptr<float>(), stream_of(ysrc)),
+           "dstagnn_window_gather_masked");
+  return {x, y};
+}
+
 // -------------------------------------------------------------------------------------
 // graph builders (fp64)
 // -------------------------------------------------------------------------------------
@@ -1198,6 +1275,12 @@ TORCH_LIBRARY(dstagnn, m) {
         "-> (Tensor, Tensor)");
   m.def("window_stats(Tensor series, Tensor w, float wtotal) -> Tensor");
   m.def("window_tile_nodes(int F, int Tin) -> int", window_tile_nodes);
+  m.def("window_stats_masked(Tensor series, Tensor w, float null_val) -> (Tensor, Tensor)");
+  m.def("window_fill_forward(Tensor series, float null_val, int max_gap) -> (Tensor, Tensor)");
+  m.def("window_fill_chunk() -> int", window_fill_chunk);
+  m.def("window_fill_cols() -> int", window_fill_cols);
+  m.def("window_gather_masked(Tensor xsrc, Tensor ysrc, Tensor rel, Tensor labels, Tensor idx, Tensor mean, "
+        "Tensor std, int P, float null_val) -> (Tensor, Tensor)");
   m.def("stag_prep(Tensor data) -> (Tensor, Tensor, Tensor)");
   m.def("stag_emd_pairs(Tensor xhat, Tensor p, Tensor psum, Tensor pairs, bool with_pivots) -> (Tensor, Tensor, Tensor)");
   m.def("stag_emd_lds_bytes(int T, int F) -> int", stag_emd_lds_bytes);
@@ -1240,6 +1323,9 @@ TORCH_LIBRARY_IMPL(dstagnn, CUDA, m) {
   m.impl("metrics_update", metrics_update);
   m.impl("window_gather", window_gather);
   m.impl("window_stats", window_stats);
+  m.impl("window_stats_masked", window_stats_masked);
+  m.impl("window_fill_forward", window_fill_forward);
+  m.impl("window_gather_masked", window_gather_masked);
   m.impl("stag_prep", stag_prep);
   m.impl("stag_emd_pairs", stag_emd_pairs);
   m.impl("emd_dense", emd_dense);

@@ -30,7 +30,9 @@ process per GPU with torch.distributed over RCCL:
     (windows.WindowedSeries) instead of loading the prepared, ``len_input``-times larger file.
   * the criterion is the reference's ``nn.SmoothL1Loss()`` unless the configuration
     (loss_options()) or ``--loss`` / ``--missing-value`` name one: then loss.HipLoss, on the
-    HIP path, optionally leaving targets equal to a missing value out of the loss.
+    HIP path, optionally leaving targets equal to a missing value out of the loss.  With
+    ``input_fill`` (input_options(), ``--input-fill``) the streamed inputs equal to that value are
+    imputed in the gather launch and the statistics taken over the observed values.
 """
 import argparse
 import configparser
@@ -505,6 +507,19 @@ def loss_options(tc):
             float(tc.get('smooth_l1_beta', 1.0)), float(tc.get('huber_delta', 1.0)))
 
 
+def input_options(tc):
+    """Optional [Training] keys of a configuration (a ConfigParser section) for a series with
+    gaps: ``input_fill`` (``none`` | ``mean`` | ``ffill``) and ``input_max_gap`` -> (str or None,
+    int or None).  Absent, or ``none``: (None, None), today's behaviour.  What counts as missing
+    is loss_options()' ``missing_value``, the value the criterion masks with."""
+    fill = tc.get('input_fill', None)
+    fill = None if fill is None or fill.strip().lower() == 'none' else fill.strip().lower()
+    if fill is not None and fill not in ('mean', 'ffill'):
+        raise ValueError(f"[Training] input_fill must be none, mean or ffill, got {fill!r}")
+    gap = tc.get('input_max_gap', None)
+    return fill, None if gap is None or gap.strip().lower() in ('', 'none') else int(gap)
+
+
 def make_criterion(name=None, missing_value=None, smooth_l1_beta=1.0, huber_delta=1.0):
     """The driver's criterion.  With no name and no missing value: ``nn.SmoothL1Loss()``
     (train_DSTAGNN_my.py:132), the object every run without the keys of loss_options() has
@@ -619,7 +634,8 @@ def load_best(net, path):
 
 
 def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches=None, root='myexperiments',
-        log=print, max_grad_norm=None, weight_decay=None, loss=None, missing_value=None, stream_windows=None):
+        log=print, max_grad_norm=None, weight_decay=None, loss=None, missing_value=None, stream_windows=None,
+        input_fill=None, input_max_gap=None):
     """Whole script: data, graphs, model, training, best-checkpoint test loss.  The optional
     [Training] keys of training_options() switch clipping / weight decay on; max_grad_norm /
     weight_decay given here override them.  loss / missing_value override the keys of
@@ -630,7 +646,12 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
     device once and gather every batch's windows from it (windows.WindowedSeries); none of the
     materialised arrays is read or built.  Where the prepared file exists only its ``mean`` and
     ``std`` are read, and the run sees the inputs of the materialised run bit for bit; otherwise
-    the statistics are computed on the device from the raw series."""
+    the statistics are computed on the device from the raw series.
+    input_fill / input_max_gap override the keys of input_options(): with ``mean`` or ``ffill`` the
+    inputs equal to the missing value (the criterion's) are imputed inside the gather launch and
+    the z-score statistics are those of the observed values, always computed on the device (a
+    prepared file's would be NaN or polluted by the sentinel).  Needs a missing value and
+    stream_windows (the materialised path has no imputation): ValueError otherwise."""
     config = configparser.ConfigParser()
     config.read(config_path)
     dc, tc = config['Data'], config['Training']
@@ -639,8 +660,22 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
     seed_torch(1)
     if stream_windows is None:
         stream_windows = tc.getboolean('stream_windows', fallback=False)
+    cfg_loss, cfg_missing, beta, delta = loss_options(tc)
+    missing_value = cfg_missing if missing_value is None else missing_value
+    cfg_fill, cfg_gap = input_options(tc)
+    input_fill = cfg_fill if input_fill is None else (None if str(input_fill).lower() == 'none' else input_fill)
+    input_max_gap = cfg_gap if input_max_gap is None else input_max_gap
+    if input_fill is not None:
+        if missing_value is None:
+            raise ValueError("input_fill needs a missing value ([Training] missing_value or missing_value=)")
+        if not stream_windows:
+            raise ValueError("input_fill needs stream_windows: the materialised path has no imputation")
     if stream_windows:
-        ws = _windowed_series(dc, tc, device)
+        ws = _windowed_series(dc, tc, device, missing_value if input_fill is not None else None, input_fill,
+                              input_max_gap)
+        if input_fill is not None and rank == 0:
+            log(f'Input gaps (fill {input_fill}, max_gap {input_max_gap}): missing per feature '
+                f'{ws.missing_count.tolist()}, filled per feature {ws.filled_count.tolist()}')
         (train_x, train_y), (val_x, val_y), (test_x, test_y) = ((ws.split(k).x, ws.split(k).y)
                                                                 for k in ('train', 'val', 'test'))
         # the reference's one-batch probe (:59-61): its draws from the global RNG do not depend on the data
@@ -666,9 +701,7 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
     bs = int(tc['batch_size'])
     n_epochs = int(tc['epochs']) if epochs is None else int(epochs)
     cfg_norm, cfg_wd, decoupled = training_options(tc)
-    cfg_loss, cfg_missing, beta, delta = loss_options(tc)
-    criterion = make_criterion(cfg_loss if loss is None else loss,
-                               cfg_missing if missing_value is None else missing_value, beta, delta)
+    criterion = make_criterion(cfg_loss if loss is None else loss, missing_value, beta, delta)
     best_epoch, best_val, history = fit(net, train_x, train_y, val_x, val_y, epochs=n_epochs,
                                         start_epoch=int(tc['start_epoch']), batch_size=bs,
                                         lr=float(tc['learning_rate']), params_path=params_path,
@@ -685,13 +718,18 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
             "params_path": params_path, "net": net}
 
 
-def _windowed_series(dc, tc, device):
+def _windowed_series(dc, tc, device, missing_value=None, fill=None, max_gap=None):
     """The configuration's raw series as a windows.WindowedSeries; the prepared file's mean / std
-    where that file exists (np.load reads an .npz per key: the materialised arrays stay on disk)."""
+    where that file exists (np.load reads an .npz per key: the materialised arrays stay on disk).
+    With a fill (input_options()) that file is not read: its statistics include the gaps."""
     from .windows import WindowedSeries
     raw = dc['graph_signal_matrix_filename']
     nh, nd, nw = int(tc['num_of_hours']), int(tc['num_of_days']), int(tc['num_of_weeks'])
     prepared, stats = data_io.dataset_filename(raw, nh, nd, nw) + '.npz', None
+    if fill is not None:
+        return WindowedSeries.from_file(raw, nw, nd, nh, int(dc['num_for_predict']),
+                                        points_per_hour=int(dc['points_per_hour']), device=device,
+                                        missing_value=missing_value, fill=fill, max_gap=max_gap)
     if os.path.exists(prepared):
         with np.load(prepared) as f:
             stats = (f['mean'], f['std'])
@@ -722,6 +760,12 @@ def main(argv=None):
     ap.add_argument("--stream-windows", action="store_true", default=None,
                     help="cut every batch's windows from the raw series on the device instead of loading the "
                          "prepared *_dstagnn.npz (overrides [Training] stream_windows)")
+    ap.add_argument("--input-fill", default=None, choices=("none", "mean", "ffill"),
+                    help="with --stream-windows and a missing value: impute the missing inputs inside the gather "
+                         "launch, by the training mean or the last observed value (overrides [Training] input_fill)")
+    ap.add_argument("--input-max-gap", type=int, default=None,
+                    help="the furthest, in time steps, --input-fill ffill carries a value (overrides [Training] "
+                         "input_max_gap; default: any distance)")
     a = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
@@ -733,7 +777,7 @@ def main(argv=None):
         run(a.config, epochs=a.epochs, double_step=not a.no_double_step, dropout=a.dropout,
             max_batches=a.max_batches, root=a.out_root, max_grad_norm=a.max_grad_norm,
             weight_decay=a.weight_decay, loss=a.loss, missing_value=a.missing_value,
-            stream_windows=a.stream_windows)
+            stream_windows=a.stream_windows, input_fill=a.input_fill, input_max_gap=a.input_max_gap)
     finally:
         if world > 1:
             dist.destroy_process_group()

@@ -10,6 +10,15 @@ the z-score.  Label positions, window offsets and the 60/20/20 split are
 its statistics (``stats=``), and to fp64 rounding when the statistics are computed here
 (``window_stats``: numpy's own fp32 statistics of an fp32 series are ~1e-6 off the fp64 value).
 
+Series with gaps (``missing_value=``): a missing input would otherwise reach the model as NaN (or as
+a z-scored sentinel) and one NaN in the training windows would make every statistic NaN.  With a
+missing value set the statistics are taken over the observed values only
+(``window_stats_masked``), a missing input is imputed inside the gather launch
+(``window_gather_masked``: the training mean, i.e. exactly 0 after the z-score, or, with
+``fill='ffill'``, the last observed value of that node and feature, forward-filled once at
+construction by ``window_fill_forward``), and the targets stay raw so that a masked criterion
+(loss.HipLoss) leaves them out.
+
 The host side (tables, weights, checks) needs no device; the gather and the statistics run only
 on the HIP path: there is no CPU fallback.
 """
@@ -78,6 +87,32 @@ def window_weights(L, labels, rel):
     return w.astype(np.int32)
 
 
+FILLS = ("mean", "ffill")
+
+
+def check_missing_options(missing_value, fill='mean', max_gap=None):
+    """The gap options of WindowedSeries, checked on the host: (missing value as a float, fill,
+    max_gap or None); (None, None, None) without a missing value (fill and max_gap are then
+    ignored).  ValueError for an unknown fill, a max_gap that is not an int >= 1 or that comes with
+    fill='mean', and a numeric missing value float32 does not hold exactly (the fp32 targets must
+    still equal it for the loss to mask them)."""
+    if missing_value is None:
+        return None, None, None
+    mv = float(missing_value)
+    if mv == mv and float(np.float32(mv)) != mv:
+        raise ValueError(f"WindowedSeries: missing_value {mv!r} is not exactly representable in float32; the "
+                         "float32 targets would no longer equal it")
+    if fill not in FILLS:
+        raise ValueError(f"WindowedSeries: fill must be one of {', '.join(map(repr, FILLS))}, got {fill!r}")
+    if max_gap is not None:
+        if isinstance(max_gap, bool) or not isinstance(max_gap, (int, np.integer)) or int(max_gap) < 1:
+            raise ValueError(f"WindowedSeries: max_gap must be None or an int >= 1, got {max_gap!r}")
+        if fill != "ffill":
+            raise ValueError("WindowedSeries: max_gap limits the forward fill; it needs fill='ffill'")
+        max_gap = int(max_gap)
+    return mv, fill, max_gap
+
+
 class _SplitArray:
     """``x`` or ``y`` of a split as the training loop uses a tensor: ``shape``, ``device``,
     ``dtype``, ``len``, ``index_select(0, idx)`` and first-axis slicing, each a gather launch
@@ -131,10 +166,24 @@ class WindowedSeries:
     training windows' mean and std (ddof 0), computed on the device in fp64 from the raw series
     (``dstagnn::window_stats``) and cast to the series' dtype.
     ``mean`` / ``std``: (1, 1, F, 1) numpy arrays, the prepared file's layout (device values
-    copied back on first use)."""
+    copied back on first use).
+
+    missing_value=None: no gap handling (fill and max_gap are ignored).  A number or NaN: the
+    elements equal to it (NaN: the NaN elements) are missing.  The statistics (stats=None) are then
+    those of the observed values in the training windows (``dstagnn::window_stats_masked``; a
+    feature with none is a ValueError), a missing input is imputed in the gather launch
+    (``dstagnn::window_gather_masked``) and the targets keep the marker for a masked criterion.
+    fill='mean': a missing input becomes exactly 0.0, the training mean.  fill='ffill': it takes
+    the latest observed value of its node and feature at an earlier step of the whole series, at
+    most max_gap steps back (None: any distance), from one ``dstagnn::window_fill_forward`` at
+    construction; what that cannot fill becomes 0.0.  Nothing is ever taken from a later step.
+    ``valid_weight`` (F,) int64: the statistics' divisor per feature (None without a missing value
+    or with stats=); ``missing_count`` / ``filled_count`` (F,) int64: the series' missing elements
+    per feature and how many of them the forward fill replaced (zeros under fill='mean');
+    ``filled``: the forward-filled series on the device (fill='ffill'), else None."""
 
     def __init__(self, series, num_of_weeks, num_of_days, num_of_hours, num_for_predict, points_per_hour=1,
-                 device=None, stats=None):
+                 device=None, stats=None, missing_value=None, fill='mean', max_gap=None):
         series = np.asarray(series)
         if series.ndim == 4:
             series = series.squeeze(axis=2)
@@ -153,6 +202,8 @@ class WindowedSeries:
             if mean.size != self.F or std.size != self.F:
                 raise ValueError(f"WindowedSeries: stats must hold F = {self.F} values each, got {mean.size} "
                                  f"and {std.size}")
+        self.missing_value, self.fill, self.max_gap = check_missing_options(missing_value, fill, max_gap)
+        self.valid_weight = self.missing_count = self.filled_count = self.filled = None
         if device is None:
             if not torch.cuda.is_available():
                 raise RuntimeError(HIP_ONLY)
@@ -169,20 +220,40 @@ class WindowedSeries:
         self.stats64 = None  # (2, F) fp64 on the device when computed here
         if stats is None:
             w = window_weights(self.L, self.labels["train"], self.rel)
-            self.stats64 = self._ops.window_stats(self.series, torch.from_numpy(w).to(dev),
-                                                  float(self.N) * float(w.astype(np.int64).sum()))
+            if self.missing_value is None:
+                self.stats64 = self._ops.window_stats(self.series, torch.from_numpy(w).to(dev),
+                                                      float(self.N) * float(w.astype(np.int64).sum()))
+            else:  # the observed values only, never the filled ones
+                self.stats64, wvalid = self._ops.window_stats_masked(self.series, torch.from_numpy(w).to(dev),
+                                                                     self.missing_value)
+                self.valid_weight = wvalid.cpu().numpy()
+                empty = np.flatnonzero(self.valid_weight == 0)
+                if empty.size:
+                    raise ValueError(f"WindowedSeries: feature {', '.join(map(str, empty))} has no observed value "
+                                     "in the training windows: no statistics to normalise it with")
             self._mean, self._std = (self.stats64[i].to(self.series.dtype).contiguous() for i in (0, 1))
         else:
             self._mean, self._std = (torch.from_numpy(np.ascontiguousarray(s.astype(series.dtype))).to(dev)
                                      for s in (mean, std))
+        self._xsrc = self.series  # where the gather reads the inputs
+        if self.fill == "ffill":
+            self.filled, counts = self._ops.window_fill_forward(self.series, self.missing_value, self.max_gap or 0)
+            self._xsrc = self.filled
+            self.missing_count, self.filled_count = counts.cpu().numpy()
+        elif self.fill == "mean":  # nothing to launch: counted on the host copy
+            miss = np.isnan(series) if self.missing_value != self.missing_value \
+                else series == series.dtype.type(self.missing_value)
+            self.missing_count = miss.sum(axis=(0, 1), dtype=np.int64)
+            self.filled_count = np.zeros(self.F, dtype=np.int64)
         self._splits = {k: WindowSplit(self, k) for k in SPLITS}
 
     @classmethod
     def from_file(cls, graph_signal_matrix_filename, num_of_weeks, num_of_days, num_of_hours, num_for_predict,
-                  points_per_hour=1, device=None, stats=None):
+                  points_per_hour=1, device=None, stats=None, missing_value=None, fill='mean', max_gap=None):
         """From the raw ``.npz`` (key ``data``) read_and_generate_dataset reads."""
         return cls(np.load(graph_signal_matrix_filename)["data"], num_of_weeks, num_of_days, num_of_hours,
-                   num_for_predict, points_per_hour, device=device, stats=stats)
+                   num_for_predict, points_per_hour, device=device, stats=stats, missing_value=missing_value,
+                   fill=fill, max_gap=max_gap)
 
     @property
     def mean(self):
@@ -207,7 +278,8 @@ class WindowedSeries:
     def batch(self, name, idx):
         """(x (B, N, F, Tin), y (B, N, P)) fp32 of the samples ``idx`` (positions in the split:
         an int64 tensor, taken as it is when it lives on the device; a slice; or a sequence) from
-        one launch.  A position outside the split gives NaN, never a read outside the series."""
+        one launch.  A position outside the split gives NaN, never a read outside the series.
+        With a missing value: the masked gather (a missing input is 0.0, ``y`` keeps the marker)."""
         labels = self._labels[name] if name in self._labels else self.split(name)
         if isinstance(idx, slice):
             idx = self._iota(labels.numel())[idx]
@@ -216,4 +288,7 @@ class WindowedSeries:
         if idx.dtype != torch.int64 or idx.dim() != 1:
             raise ValueError("WindowedSeries.batch: idx must be a 1-D int64 tensor")
         idx = idx.to(self.device).contiguous()
-        return self._ops.window_gather(self.series, self._rel, labels, idx, self._mean, self._std, self.P)
+        if self.missing_value is None:
+            return self._ops.window_gather(self.series, self._rel, labels, idx, self._mean, self._std, self.P)
+        return self._ops.window_gather_masked(self._xsrc, self.series, self._rel, labels, idx, self._mean, self._std,
+                                              self.P, self.missing_value)

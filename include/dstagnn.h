@@ -433,6 +433,32 @@ int dstagnn_metrics_accumulate(int64_t rows, int P, const float* pred, const flo
  * one's mean), sums in a fixed order: the same bits on every call.  1 <= F <= 256, else
  * DSTAGNN_E_SHAPE; wtotal > 0, else DSTAGNN_E_ARG.  scratch:
  * dstagnn_window_stats_scratch_bytes(L, F) bytes.
+ *
+ * Series with gaps.  An element v of the series (type S) is MISSING when null_val is NaN
+ * (std::isnan, as dstagnn_metrics_accumulate reads its null_val) and v != v, otherwise when
+ * v == S(null_val) (IEEE ==: -0.0 == 0.0, and a NaN element is then valid).
+ *
+ * dstagnn_window_stats_masked: dstagnn_window_stats over the valid elements only:
+ * wvalid[f] = sum_s w[s] * #valid(s, ., f) (int64, exact), mean[f] = sum_valid w x / wvalid[f],
+ * std[f] = sqrt(sum_valid w (x - mean[f])^2 / wvalid[f]).  Same launches, threads and fp64 fold
+ * order: on a series with no missing element stats equals dstagnn_window_stats' bits.  A feature
+ * with wvalid[f] == 0 gives NaN.  scratch: dstagnn_window_stats_masked_scratch_bytes(L, F).
+ *
+ * dstagnn_window_fill_forward: the one-time forward fill along time.  filled (L, N, F) of type S:
+ * a valid element is copied; a missing one takes the value of the latest valid step p < s of its
+ * (n, f) over the whole series, if one exists and s - p <= max_gap (max_gap = 0: unlimited;
+ * < 0: DSTAGNN_E_ARG); otherwise it keeps its marker, bits unchanged.  Never reads a later step.
+ * counts (2, F) int64 = {missing elements per feature, how many of them were filled}.  Two
+ * launches over chunks of dstagnn_window_fill_chunk() time steps and workgroups of
+ * dstagnn_window_fill_cols() columns e = n F + f: the first writes every (chunk, column)'s last
+ * valid step into scratch (int32; dstagnn_window_fill_scratch_bytes(L, N, F) bytes), the second
+ * finds its carry there and walks its chunk.  L < 2^31, 1 <= F <= 256, filled != series.
+ *
+ * dstagnn_window_gather_masked: dstagnn_window_gather with the inputs read from xsrc and the
+ * targets from ysrc (both (L, N, F) of type S; they may be the same array):
+ *   x[b,n,f,t] = valid(v) ? float((v - mean[f]) / std[f]) : +0.0f,  v = xsrc[label_b + rel[t], n, f]
+ *   y[b,n,p]   = float(ysrc[label_b + p, n, F-1])   (raw: the marker stays for the masked loss)
+ * Same tile, LDS and checks as dstagnn_window_gather.
  * ------------------------------------------------------------------------------------- */
 int dstagnn_window_tile_nodes(int F, int Tin);
 int64_t dstagnn_window_gather_lds_bytes(int F, int Tin, int P);
@@ -442,6 +468,20 @@ int dstagnn_window_gather(int series_f64, const void* series, int64_t L, int N, 
 int64_t dstagnn_window_stats_scratch_bytes(int64_t L, int F);
 int dstagnn_window_stats(int series_f64, const void* series, int64_t L, int N, int F, const int32_t* w, double wtotal,
                          double* stats, void* scratch, size_t scratch_bytes, dstagnn_stream_t stream);
+int64_t dstagnn_window_stats_masked_scratch_bytes(int64_t L, int F);
+int dstagnn_window_stats_masked(int series_f64, const void* series, int64_t L, int N, int F, const int32_t* w,
+                                double null_val, double* stats, int64_t* wvalid, void* scratch, size_t scratch_bytes,
+                                dstagnn_stream_t stream);
+int dstagnn_window_fill_chunk(void);
+int dstagnn_window_fill_cols(void);
+int64_t dstagnn_window_fill_scratch_bytes(int64_t L, int N, int F);
+int dstagnn_window_fill_forward(int series_f64, const void* series, int64_t L, int N, int F, double null_val,
+                                int64_t max_gap, void* filled, int64_t* counts, void* scratch, size_t scratch_bytes,
+                                dstagnn_stream_t stream);
+int dstagnn_window_gather_masked(int series_f64, const void* xsrc, const void* ysrc, int64_t L, int N, int F,
+                                 const int32_t* rel, int Tin, int P, const int64_t* labels, int64_t S,
+                                 const int64_t* idx, int B, const void* mean, const void* std, double null_val, float* x,
+                                 float* y, dstagnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Graph builders (stag.hip).  fp64 throughout, like the reference's numpy/scipy code.

@@ -19,6 +19,17 @@ the acceptance figure is (gather - index_select) / step <= 1 %.
 
     python tools/bench_windows.py --out profiles/windows_ab.json
 
+With --missing-rate R (off by default) the tool measures the gap-aware path instead: a seeded
+fraction R of the series is set to NaN and the masked gather (``fill='mean'`` and
+``fill='ffill'``: dstagnn::window_gather_masked) is timed beside the plain gather of the intact
+series in the same alternating-window protocol at both geometries (and the masked gather of the
+intact series: the select alone); the one-time
+dstagnn::window_fill_forward and dstagnn::window_stats_masked (beside dstagnn::window_stats) are
+timed once each, after one warm call.  The three move the same bytes; the figure to read is the
+masked medians against the spread the plain variant's own windows show.
+
+    python tools/bench_windows.py --missing-rate 0.2      (writes profiles/windows_gaps_ab.json)
+
 The JSON carries the library stamp (dstagnn_drought_amd._lib.build_stamp).  There is no fallback:
 without a HIP device the tool fails."""
 import argparse
@@ -98,21 +109,119 @@ def time_config(torch, name, iters, rounds, warmup):
     return out
 
 
+def time_gaps(torch, name, rate, iters, rounds, warmup):
+    """The masked gather (both fills) beside the plain one, and the one-time fill / statistics."""
+    import numpy as np
+    from dstagnn_drought_amd import WindowedSeries
+    from dstagnn_drought_amd import windows as W
+    L, N, F, nh, P, pph, B, S = GEOMETRIES[name]
+    rng = np.random.default_rng(1)
+    series = (rng.standard_normal((L, N, F), dtype=np.float32) + 2.0)
+    gapped = series.copy()
+    gapped[rng.random(series.shape) < rate] = np.nan
+    nan = float("nan")
+    plain = WindowedSeries(series, 0, 0, nh, P, points_per_hour=pph)
+    owners = {"gather": plain,
+              "gather_masked_mean": WindowedSeries(gapped, 0, 0, nh, P, points_per_hour=pph, missing_value=nan),
+              "gather_masked_ffill": WindowedSeries(gapped, 0, 0, nh, P, points_per_hour=pph, missing_value=nan,
+                                                    fill="ffill"),
+              # the masked kernel where nothing is missing: the cost of the select alone
+              "gather_masked_intact": WindowedSeries(series, 0, 0, nh, P, points_per_hour=pph, missing_value=nan)}
+    ops, dev, Tin = plain._ops, plain.device, plain.Tin
+    gen = torch.Generator().manual_seed(2)
+    sidx = torch.randperm(len(plain.labels["train"]), generator=gen)[:S].to(dev)
+    nb = S // B
+    variants = {k: (lambda i, ws=ws: ws.batch("train", sidx[i * B:(i + 1) * B])) for k, ws in owners.items()}
+    for k, f in variants.items():
+        x, y = f(0)
+        assert bool(torch.isfinite(x).all()), k  # (the plain one reads the intact series)
+        for i in range(warmup):
+            f(i % nb)
+    torch.cuda.synchronize()
+    runs = {k: [] for k in variants}
+    for _ in range(rounds):
+        for k, f in variants.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(iters):
+                f(i % nb)
+            e1.record()
+            e1.synchronize()
+            runs[k].append(round(e0.elapsed_time(e1) / iters * 1e3, 3))
+    med = {k: statistics.median(r) for k, r in runs.items()}
+
+    def once(f):  # one warm call, then one timed call
+        f()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        f()
+        e1.record()
+        e1.synchronize()
+        return round(e0.elapsed_time(e1) * 1e3, 1)
+
+    gws = owners["gather_masked_ffill"]
+    w = W.window_weights(L, plain.labels["train"], plain.rel)
+    wd, wtotal = torch.from_numpy(w).to(dev), float(N) * float(w.astype(np.int64).sum())
+    one_time = {"window_fill_forward_us": once(lambda: ops.window_fill_forward(gws.series, nan, 0)),
+                "window_stats_masked_us": once(lambda: ops.window_stats_masked(gws.series, wd, nan)),
+                "window_stats_us": once(lambda: ops.window_stats(plain.series, wd, wtotal))}
+    item = series.dtype.itemsize
+    moved = B * N * (Tin * F * item + P * item + F * Tin * 4 + P * 4)
+    spread = {k: round((max(r) - min(r)) / med[k], 4) for k, r in runs.items()}
+    out = {"series": [L, N, F], "dtype": str(series.dtype), "Tin": Tin, "B": B, "missing_rate": rate,
+           "missing_per_feature": gws.missing_count.tolist(), "filled_per_feature": gws.filled_count.tolist(),
+           "us_per_batch_runs": runs, "median_us": med, "spread": spread,
+           "masked_over_plain": {k: round(med[k] / med["gather"] - 1.0, 4) for k in med if k != "gather"},
+           "inside_plain_spread": {k: bool(abs(med[k] - med["gather"]) <= max(runs["gather"]) - min(runs["gather"]))
+                                   for k in med if k != "gather"},
+           "bytes_moved_per_batch": moved, "one_time_us": one_time, "series_bytes": int(series.nbytes)}
+    del owners, plain, gws
+    torch.cuda.empty_cache()
+    return out
+
+
+def main_gaps(a, torch, _lib):
+    rec = {"what": f"the masked gather (missing inputs imputed in the launch; fill = mean / ffill) beside the plain "
+                   f"gather of the intact series, us per batch between device events, {a.rounds} alternating windows x "
+                   f"{a.iters} batches; NaN at a seeded fraction {a.missing_rate} of the series; the one-time "
+                   "window_fill_forward / window_stats_masked / window_stats: one timed call after a warm one "
+                   "(tools/bench_windows.py --missing-rate)",
+           "stamp": _lib.build_stamp(), "configs": {}}
+    for name in GEOMETRIES:
+        rec["configs"][name] = time_gaps(torch, name, a.missing_rate, a.iters, a.rounds, a.warmup)
+        print(f"[windows gaps] {name}: {rec['configs'][name]}", file=sys.stderr, flush=True)
+    print(json.dumps(rec))
+    out = a.out or os.path.join(ROOT, "profiles", "windows_gaps_ab.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(rec, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=1000, help="batches per window (>= 100)")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--step-steps", type=int, default=50, help="steps of the block timing per configuration")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "windows_ab.json"))
+    ap.add_argument("--missing-rate", type=float, default=None,
+                    help="measure the gap-aware path instead: this fraction of the series is NaN "
+                         "(writes profiles/windows_gaps_ab.json unless --out is given)")
+    ap.add_argument("--out", default=None,
+                    help="default: profiles/windows_ab.json (profiles/windows_gaps_ab.json with --missing-rate)")
     a = ap.parse_args()
     if a.iters < 100:
         ap.error("--iters must be at least 100")
+    if a.missing_rate is not None and not 0.0 < a.missing_rate < 1.0:
+        ap.error("--missing-rate must lie in (0, 1)")
     import torch
     from dstagnn_drought_amd import _lib
     if not torch.cuda.is_available():
         raise SystemExit("bench_windows.py measures on the GPU only: no HIP device")
     torch.cuda.set_device(0)
+    if a.missing_rate is not None:
+        return main_gaps(a, torch, _lib)
+    a.out = a.out or os.path.join(ROOT, "profiles", "windows_ab.json")
     import bench_configs
     rec = {"what": f"one batch cut from the raw series (gather) vs from materialised tensors (index_select), us per "
                    f"batch between device events, {a.rounds} alternating windows x {a.iters} batches; the step is one "
