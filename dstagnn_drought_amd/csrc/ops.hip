@@ -1,7 +1,6 @@
-// ops.hip — the non-GEMM kernels of the DSTAGNN block (gfx950, wave64).
+// ops.hip — the non-GEMM kernels of the DSTAGNN block (gfx950, wave64), apart from the temporal
+// attention core (tat.hip, tat_fused.hip).
 //
-//   tat_fwd / tat_bwd     temporal attention core per (b,f,head): T x T scores,
-//                         softmax over the QUERY axis (model/DSTAGNN_my.py:37-41)
 //   ln_fwd / ln_bwd       row LayerNorm over strided multi-source sums (TAt LN_N :100,
 //                         EmbedT LN_N :176-181, EmbedS LN_D :180-181) + fused dropout
 //   cheb_softmax_fwd/bwd  column softmax over source node i of S'+A_pa*M_k, times T_k
@@ -9,7 +8,6 @@
 //   gate_fwd / gate_bwd   GTU gates tanh(p)*sigmoid(q) + concat (:192-197, :242)
 //   tail_fwd / tail_bwd   fcmy dropout + residual + ReLU + LN_C (:243-252)
 //   reductions            deterministic two-stage column sums (bias / gamma / beta grads)
-#include <initializer_list>
 #include <map>
 #include <mutex>
 
@@ -55,477 +53,6 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
       if (beta != 0.f) v += beta * old[u];
       op[o] = v;
     }
-  }
-}
-
-// =====================================================================================
-// temporal attention core (one workgroup per (b, f, head))
-// =====================================================================================
-struct TatArgs {
-  int B, F, T, h, dk, dv;
-  const float* qkv;      // (B*F*T, 2*h*dk + h*dv): [Q | K | V]
-  const float* res;      // res_att or null
-  int res_mode;
-  float scale;
-  float* re_at;          // (B,F,h,T,T) scores
-  float* att;            // (B,F,h,T,T) softmax (saved)
-  float* ctx;            // (B*F*T, h*dv)
-  // bwd
-  const float* dctx;     // (B*F*T, h*dv)
-  const float* dre;      // (B,F,h,T,T) or null
-  float* dqkv;           // (B*F*T, 3 cols blocks)
-  float* dscore;         // (B,F,h,T,T) dS (== d res_att before f-reduction); scratch when !keep_ds
-  // matrix-core backward only: dres_sum = sum_f dS ((B,1,h,T,T), the broadcast res_att's
-  // gradient) folded in-kernel by tickets cnt[b*h + hd] over partials in dscore
-  float* dres_sum;
-  int* cnt;
-  int keep_ds;           // write the full dS to dscore
-};
-
-// -------------------------------------------------------------------------------------
-// Wave-per-problem variants for short series (T <= 16): one 64-lane wave owns one
-// (b, f, head) problem, four per workgroup, so no lane idles through the T-wide softmax
-// phases: the column softmax over the query axis runs on lanes (j = lane % 16, part =
-// lane / 16) with the part sums combined by xor-shuffles over lane bits 4 and 5.  All
-// global accesses are row-contiguous (coalesced).
-// -------------------------------------------------------------------------------------
-constexpr int kTatW = 4;  // problems (waves) per workgroup
-
-__device__ __forceinline__ float xor_max_1632(float v) {
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float xor_sum_1632(float v) {
-  v += __shfl_xor(v, 16, 64);
-  return v + __shfl_xor(v, 32, 64);
-}
-
-__host__ __device__ inline int tat_wave_fwd_floats(int T, int dk, int dv) {
-  return 2 * T * (dk + 1) + T * (dv + 1) + T * T;
-}
-__host__ __device__ inline int tat_wave_bwd_floats(int T, int dk, int dv) {
-  return 2 * T * (dk + 1) + 2 * T * (dv + 1) + 2 * T * T;
-}
-
-__global__ __launch_bounds__(256) void tat_fwd_wave_kernel(TatArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int T = a.T, dk = a.dk, dv = a.dv, dkp = dk + 1, dvp = dv + 1;
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int id = blockIdx.x * kTatW + w;  // ((b*F + f)*h + hd)
-  const bool live = id < a.B * a.F * a.h;
-  float* Qs = sm + w * tat_wave_fwd_floats(T, dk, dv);
-  float* Ks = Qs + T * dkp;
-  float* Vs = Ks + T * dkp;
-  float* Ss = Vs + T * dvp;
-  const int hd = id % a.h, bf = id / a.h, b = bf / a.F;
-  const int ld = 2 * a.h * dk + a.h * dv;
-  const float* base = a.qkv + (int64_t)bf * T * ld;
-  if (live) {
-    for (int e = lane; e < T * dk; e += 64) {
-      const int i = e / dk, d = e - i * dk;
-      Qs[i * dkp + d] = base[(int64_t)i * ld + hd * dk + d];
-      Ks[i * dkp + d] = base[(int64_t)i * ld + a.h * dk + hd * dk + d];
-    }
-    for (int e = lane; e < T * dv; e += 64) {
-      const int i = e / dv, d = e - i * dv;
-      Vs[i * dvp + d] = base[(int64_t)i * ld + 2 * a.h * dk + hd * dv + d];
-    }
-  }
-  __syncthreads();
-  const int64_t sbase = (int64_t)id * T * T;
-  if (live) {
-    const float* rp = nullptr;
-    if (a.res_mode == DSTAGNN_RES_BCAST) rp = a.res + ((int64_t)b * a.h + hd) * T * T;
-    else if (a.res_mode == DSTAGNN_RES_FULL) rp = a.res + sbase;
-    for (int e = lane; e < T * T; e += 64) {
-      const int i = e / T, j = e - i * T;
-      float sc = 0.f;
-      for (int d = 0; d < dk; ++d) sc = fmaf(Qs[i * dkp + d], Ks[j * dkp + d], sc);
-      sc *= a.scale;
-      if (rp) sc += rp[e];
-      Ss[e] = sc;
-      a.re_at[sbase + e] = sc;
-    }
-  }
-  __syncthreads();
-  if (live) {  // softmax over i for column j
-    const int j = lane & 15, part = lane >> 4;
-    float m = -INFINITY;
-    if (j < T)
-      for (int i = part; i < T; i += 4) m = fmaxf(m, Ss[i * T + j]);
-    m = xor_max_1632(m);
-    float l = 0.f;
-    if (j < T)
-      for (int i = part; i < T; i += 4) l += __expf(Ss[i * T + j] - m);
-    l = xor_sum_1632(l);
-    const float inv = 1.f / l;
-    if (j < T)
-      for (int i = part; i < T; i += 4) Ss[i * T + j] = __expf(Ss[i * T + j] - m) * inv;
-  }
-  __syncthreads();
-  if (live) {
-    for (int e = lane; e < T * T; e += 64) a.att[sbase + e] = Ss[e];
-    const int ldc = a.h * dv;
-    float* cbase = a.ctx + (int64_t)bf * T * ldc;
-    for (int e = lane; e < T * dv; e += 64) {
-      const int i = e / dv, d = e - i * dv;
-      float acc = 0.f;
-      for (int j = 0; j < T; ++j) acc = fmaf(Ss[i * T + j], Vs[j * dvp + d], acc);
-      cbase[(int64_t)i * ldc + hd * dv + d] = acc;
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void tat_bwd_wave_kernel(TatArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int T = a.T, dk = a.dk, dv = a.dv, dkp = dk + 1, dvp = dv + 1;
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int id = blockIdx.x * kTatW + w;
-  const bool live = id < a.B * a.F * a.h;
-  float* Qs = sm + w * tat_wave_bwd_floats(T, dk, dv);
-  float* Ks = Qs + T * dkp;
-  float* Vs = Ks + T * dkp;
-  float* dCs = Vs + T * dvp;
-  float* As = dCs + T * dvp;
-  float* dAs = As + T * T;
-  const int hd = id % a.h, bf = id / a.h;
-  const int ld = 2 * a.h * dk + a.h * dv, ldc = a.h * dv;
-  const float* base = a.qkv + (int64_t)bf * T * ld;
-  const float* cb = a.dctx + (int64_t)bf * T * ldc;
-  const int64_t sbase = (int64_t)id * T * T;
-  if (live) {
-    for (int e = lane; e < T * dk; e += 64) {
-      const int i = e / dk, d = e - i * dk;
-      Qs[i * dkp + d] = base[(int64_t)i * ld + hd * dk + d];
-      Ks[i * dkp + d] = base[(int64_t)i * ld + a.h * dk + hd * dk + d];
-    }
-    for (int e = lane; e < T * dv; e += 64) {
-      const int i = e / dv, d = e - i * dv;
-      Vs[i * dvp + d] = base[(int64_t)i * ld + 2 * a.h * dk + hd * dv + d];
-      dCs[i * dvp + d] = cb[(int64_t)i * ldc + hd * dv + d];
-    }
-    for (int e = lane; e < T * T; e += 64) As[e] = a.att[sbase + e];
-  }
-  __syncthreads();
-  float* dbase = a.dqkv + (int64_t)bf * T * ld;
-  if (live) {
-    for (int e = lane; e < T * T; e += 64) {  // dA[i][j] = sum_d dctx[i][d] V[j][d]
-      const int i = e / T, j = e - i * T;
-      float acc = 0.f;
-      for (int d = 0; d < dv; ++d) acc = fmaf(dCs[i * dvp + d], Vs[j * dvp + d], acc);
-      dAs[e] = acc;
-    }
-    for (int e = lane; e < T * dv; e += 64) {  // dV[j][d] = sum_i A[i][j] dctx[i][d]
-      const int j = e / dv, d = e - j * dv;
-      float acc = 0.f;
-      for (int i = 0; i < T; ++i) acc = fmaf(As[i * T + j], dCs[i * dvp + d], acc);
-      dbase[(int64_t)j * ld + 2 * a.h * dk + hd * dv + d] = acc;
-    }
-  }
-  __syncthreads();
-  if (live) {  // column softmax backward: dS = A (dA - sum_i A dA) + d re_At
-    const int j = lane & 15, part = lane >> 4;
-    float c = 0.f;
-    if (j < T)
-      for (int i = part; i < T; i += 4) c = fmaf(As[i * T + j], dAs[i * T + j], c);
-    c = xor_sum_1632(c);
-    if (j < T)
-      for (int i = part; i < T; i += 4) {
-        float v = As[i * T + j] * (dAs[i * T + j] - c);
-        if (a.dre) v += a.dre[sbase + i * T + j];
-        dAs[i * T + j] = v;
-      }
-  }
-  __syncthreads();
-  if (live) {
-    for (int e = lane; e < T * T; e += 64) a.dscore[sbase + e] = dAs[e];
-    for (int e = lane; e < T * dk; e += 64) {
-      const int i = e / dk, d = e - i * dk;
-      float sq = 0.f, sk = 0.f;
-      for (int j = 0; j < T; ++j) {
-        sq = fmaf(dAs[i * T + j], Ks[j * dkp + d], sq);
-        sk = fmaf(dAs[j * T + i], Qs[j * dkp + d], sk);
-      }
-      dbase[(int64_t)i * ld + hd * dk + d] = sq * a.scale;
-      dbase[(int64_t)i * ld + a.h * dk + hd * dk + d] = sk * a.scale;
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void tat_fwd_kernel(TatArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int T = a.T, dk = a.dk, dv = a.dv;
-  const int dkp = dk + 1, dvp = dv + 1;
-  float* Qs = sm;
-  float* Ks = Qs + T * dkp;
-  float* Vs = Ks + T * dkp;
-  float* Ss = Vs + T * dvp;  // T*T
-  const int id = blockIdx.x;  // ((b*F + f)*h + hd)
-  const int hd = id % a.h;
-  const int bf = id / a.h;
-  const int b = bf / a.F;
-  const int ld = 2 * a.h * dk + a.h * dv;
-  const float* base = a.qkv + (int64_t)bf * T * ld;
-  for (int e = threadIdx.x; e < T * dk; e += blockDim.x) {
-    int i = e / dk, d = e % dk;
-    Qs[i * dkp + d] = base[(int64_t)i * ld + hd * dk + d];
-    Ks[i * dkp + d] = base[(int64_t)i * ld + a.h * dk + hd * dk + d];
-  }
-  for (int e = threadIdx.x; e < T * dv; e += blockDim.x) {
-    int i = e / dv, d = e % dv;
-    Vs[i * dvp + d] = base[(int64_t)i * ld + 2 * a.h * dk + hd * dv + d];
-  }
-  __syncthreads();
-  const int64_t sbase = (int64_t)id * T * T;
-  const float* rp = nullptr;
-  if (a.res_mode == DSTAGNN_RES_BCAST) rp = a.res + ((int64_t)b * a.h + hd) * T * T;
-  else if (a.res_mode == DSTAGNN_RES_FULL) rp = a.res + sbase;
-  for (int e = threadIdx.x; e < T * T; e += blockDim.x) {
-    int i = e / T, j = e % T;
-    float s = 0.f;
-    for (int d = 0; d < dk; ++d) s = fmaf(Qs[i * dkp + d], Ks[j * dkp + d], s);
-    s = s * a.scale;
-    if (rp) s += rp[e];
-    Ss[e] = s;
-    a.re_at[sbase + e] = s;
-  }
-  __syncthreads();
-  // softmax over i (query axis) for each column j
-  for (int j = threadIdx.x; j < T; j += blockDim.x) {
-    float m = -INFINITY;
-    for (int i = 0; i < T; ++i) m = fmaxf(m, Ss[i * T + j]);
-    float l = 0.f;
-    for (int i = 0; i < T; ++i) l += expf(Ss[i * T + j] - m);
-    float inv = 1.f / l;
-    for (int i = 0; i < T; ++i) Ss[i * T + j] = expf(Ss[i * T + j] - m) * inv;
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < T * T; e += blockDim.x) a.att[sbase + e] = Ss[e];
-  const int ldc = a.h * dv;
-  float* cbase = a.ctx + (int64_t)bf * T * ldc;
-  for (int e = threadIdx.x; e < T * dv; e += blockDim.x) {
-    int i = e / dv, d = e % dv;
-    float s = 0.f;
-    for (int j = 0; j < T; ++j) s = fmaf(Ss[i * T + j], Vs[j * dvp + d], s);
-    cbase[(int64_t)i * ldc + hd * dv + d] = s;
-  }
-}
-
-__global__ __launch_bounds__(256) void tat_bwd_kernel(TatArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int T = a.T, dk = a.dk, dv = a.dv;
-  const int dkp = dk + 1, dvp = dv + 1;
-  float* Qs = sm;
-  float* Ks = Qs + T * dkp;
-  float* Vs = Ks + T * dkp;
-  float* dCs = Vs + T * dvp;    // T*dvp
-  float* As = dCs + T * dvp;    // T*T
-  float* dAs = As + T * T;      // T*T  (becomes dS)
-  const int id = blockIdx.x;
-  const int hd = id % a.h;
-  const int bf = id / a.h;
-  const int ld = 2 * a.h * dk + a.h * dv;
-  const int ldc = a.h * dv;
-  const float* base = a.qkv + (int64_t)bf * T * ld;
-  const float* cb = a.dctx + (int64_t)bf * T * ldc;
-  const int64_t sbase = (int64_t)id * T * T;
-  for (int e = threadIdx.x; e < T * dk; e += blockDim.x) {
-    int i = e / dk, d = e % dk;
-    Qs[i * dkp + d] = base[(int64_t)i * ld + hd * dk + d];
-    Ks[i * dkp + d] = base[(int64_t)i * ld + a.h * dk + hd * dk + d];
-  }
-  for (int e = threadIdx.x; e < T * dv; e += blockDim.x) {
-    int i = e / dv, d = e % dv;
-    Vs[i * dvp + d] = base[(int64_t)i * ld + 2 * a.h * dk + hd * dv + d];
-    dCs[i * dvp + d] = cb[(int64_t)i * ldc + hd * dv + d];
-  }
-  for (int e = threadIdx.x; e < T * T; e += blockDim.x) As[e] = a.att[sbase + e];
-  __syncthreads();
-  // dA[i][j] = sum_d dctx[i][d] V[j][d]
-  for (int e = threadIdx.x; e < T * T; e += blockDim.x) {
-    int i = e / T, j = e % T;
-    float s = 0.f;
-    for (int d = 0; d < dv; ++d) s = fmaf(dCs[i * dvp + d], Vs[j * dvp + d], s);
-    dAs[e] = s;
-  }
-  // dV[j][d] = sum_i A[i][j] dctx[i][d]
-  float* dbase = a.dqkv + (int64_t)bf * T * ld;
-  for (int e = threadIdx.x; e < T * dv; e += blockDim.x) {
-    int j = e / dv, d = e % dv;
-    float s = 0.f;
-    for (int i = 0; i < T; ++i) s = fmaf(As[i * T + j], dCs[i * dvp + d], s);
-    dbase[(int64_t)j * ld + 2 * a.h * dk + hd * dv + d] = s;
-  }
-  __syncthreads();
-  // column softmax backward: dS = A * (dA - sum_i A dA) + d re_At
-  for (int j = threadIdx.x; j < T; j += blockDim.x) {
-    float c = 0.f;
-    for (int i = 0; i < T; ++i) c = fmaf(As[i * T + j], dAs[i * T + j], c);
-    for (int i = 0; i < T; ++i) {
-      float v = As[i * T + j] * (dAs[i * T + j] - c);
-      if (a.dre) v += a.dre[sbase + i * T + j];
-      dAs[i * T + j] = v;
-    }
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < T * T; e += blockDim.x) a.dscore[sbase + e] = dAs[e];
-  // dQ[i][d] = scale * sum_j dS[i][j] K[j][d];  dK[j][d] = scale * sum_i dS[i][j] Q[i][d]
-  for (int e = threadIdx.x; e < T * dk; e += blockDim.x) {
-    int i = e / dk, d = e % dk;
-    float sq = 0.f, sk = 0.f;
-    for (int j = 0; j < T; ++j) {
-      sq = fmaf(dAs[i * T + j], Ks[j * dkp + d], sq);
-      sk = fmaf(dAs[j * T + i], Qs[j * dkp + d], sk);
-    }
-    dbase[(int64_t)i * ld + hd * dk + d] = sq * a.scale;
-    dbase[(int64_t)i * ld + a.h * dk + hd * dk + d] = sk * a.scale;
-  }
-}
-
-// Long-series variants (GAMBIA T = 144: one workgroup per (b,f,head) problem would hold
-// 140-160 KB of LDS and leave most of its threads idle in the column phases).  The query-axis
-// softmax normalises each COLUMN j over the rows i, so a problem splits into column chunks of
-// kTatCW columns, one workgroup each (B*F*h*ceil(T/kTatCW) workgroups):
-//   fwd  S[:, chunk] -> re_At, softmax -> att; then ctx = att . V as one batched GEMM
-//   bwd  dA[:, chunk] = dctx . V_chunk^T, dV_chunk = A_chunk^T dctx, dS[:, chunk] (-> d score),
-//        dK_chunk = s dS_chunk^T Q; then dQ = s dS . K as one batched GEMM
-constexpr int kTatCW = 16;
-
-__host__ __device__ inline int tat_cols_fwd_floats(int T, int dk) {
-  return T * (dk + 1) + kTatCW * (dk + 1) + T * kTatCW + 2 * 16 * 16;
-}
-__host__ __device__ inline int tat_cols_bwd_floats(int T, int dk, int dv) {
-  return T * (dk + 1) + T * (dv + 1) + kTatCW * (dv + 1) + 2 * T * kTatCW + 16 * 16;
-}
-
-// column reduction helper: 256 threads = 16 columns x 16 row groups (tid = g * 16 + jj)
-__device__ __forceinline__ float col_reduce16(float v, float* red, bool is_max) {
-  const int jj = threadIdx.x & 15, g = threadIdx.x >> 4;
-  red[g * 16 + jj] = v;
-  __syncthreads();
-  float r = red[jj];
-#pragma unroll
-  for (int q = 1; q < 16; ++q) r = is_max ? fmaxf(r, red[q * 16 + jj]) : r + red[q * 16 + jj];
-  __syncthreads();
-  return r;
-}
-
-__global__ __launch_bounds__(256) void tat_fwd_cols_kernel(TatArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int T = a.T, dk = a.dk, dkp = dk + 1;
-  const int nch = (T + kTatCW - 1) / kTatCW;
-  const int id = blockIdx.x / nch, j0 = (blockIdx.x % nch) * kTatCW, cw = min(kTatCW, T - j0);
-  float* Qs = sm;
-  float* Ks = Qs + T * dkp;
-  float* Ss = Ks + kTatCW * dkp;   // [i][jj]
-  float* red = Ss + T * kTatCW;
-  const int hd = id % a.h, bf = id / a.h, b = bf / a.F;
-  const int ld = 2 * a.h * dk + a.h * a.dv;
-  const float* base = a.qkv + (int64_t)bf * T * ld;
-  for (int e = threadIdx.x; e < T * dk; e += 256) {
-    const int i = e / dk, d = e - i * dk;
-    Qs[i * dkp + d] = base[(int64_t)i * ld + hd * dk + d];
-  }
-  for (int e = threadIdx.x; e < cw * dk; e += 256) {
-    const int jj = e / dk, d = e - jj * dk;
-    Ks[jj * dkp + d] = base[(int64_t)(j0 + jj) * ld + a.h * dk + hd * dk + d];
-  }
-  __syncthreads();
-  const int64_t sbase = (int64_t)id * T * T;
-  const float* rp = nullptr;
-  if (a.res_mode == DSTAGNN_RES_BCAST) rp = a.res + ((int64_t)b * a.h + hd) * T * T;
-  else if (a.res_mode == DSTAGNN_RES_FULL) rp = a.res + sbase;
-  for (int e = threadIdx.x; e < T * kTatCW; e += 256) {
-    const int i = e / kTatCW, jj = e - i * kTatCW;
-    float sc = 0.f;
-    if (jj < cw) {
-      for (int d = 0; d < dk; ++d) sc = fmaf(Qs[i * dkp + d], Ks[jj * dkp + d], sc);
-      sc *= a.scale;
-      if (rp) sc += rp[(int64_t)i * T + j0 + jj];
-      a.re_at[sbase + (int64_t)i * T + j0 + jj] = sc;
-    }
-    Ss[e] = sc;
-  }
-  __syncthreads();
-  const int jj = threadIdx.x & 15, g = threadIdx.x >> 4;
-  float m = -INFINITY;
-  for (int i = g; i < T; i += 16) m = fmaxf(m, Ss[i * kTatCW + jj]);
-  m = col_reduce16(m, red, true);
-  float l = 0.f;
-  for (int i = g; i < T; i += 16) l += __expf(Ss[i * kTatCW + jj] - m);
-  l = col_reduce16(l, red, false);
-  const float inv = 1.f / l;
-  if (jj < cw)
-    for (int i = g; i < T; i += 16) a.att[sbase + (int64_t)i * T + j0 + jj] = __expf(Ss[i * kTatCW + jj] - m) * inv;
-}
-
-__global__ __launch_bounds__(256) void tat_bwd_cols_kernel(TatArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int T = a.T, dk = a.dk, dv = a.dv, dkp = dk + 1, dvp = dv + 1;
-  const int nch = (T + kTatCW - 1) / kTatCW;
-  const int id = blockIdx.x / nch, j0 = (blockIdx.x % nch) * kTatCW, cw = min(kTatCW, T - j0);
-  float* Qs = sm;                       // T x dkp
-  float* dCs = Qs + T * dkp;            // T x dvp
-  float* Vs = dCs + T * dvp;            // kTatCW x dvp
-  float* As = Vs + kTatCW * dvp;        // [i][jj]
-  float* dAs = As + T * kTatCW;         // [i][jj] -> dS
-  float* red = dAs + T * kTatCW;
-  const int hd = id % a.h, bf = id / a.h;
-  const int ld = 2 * a.h * dk + a.h * dv, ldc = a.h * dv;
-  const float* base = a.qkv + (int64_t)bf * T * ld;
-  const float* cb = a.dctx + (int64_t)bf * T * ldc;
-  const int64_t sbase = (int64_t)id * T * T;
-  for (int e = threadIdx.x; e < T * dk; e += 256) {
-    const int i = e / dk, d = e - i * dk;
-    Qs[i * dkp + d] = base[(int64_t)i * ld + hd * dk + d];
-  }
-  for (int e = threadIdx.x; e < T * dv; e += 256) {
-    const int i = e / dv, d = e - i * dv;
-    dCs[i * dvp + d] = cb[(int64_t)i * ldc + hd * dv + d];
-  }
-  for (int e = threadIdx.x; e < cw * dv; e += 256) {
-    const int jj = e / dv, d = e - jj * dv;
-    Vs[jj * dvp + d] = base[(int64_t)(j0 + jj) * ld + 2 * a.h * dk + hd * dv + d];
-  }
-  for (int e = threadIdx.x; e < T * kTatCW; e += 256) {
-    const int i = e / kTatCW, jj = e - i * kTatCW;
-    As[e] = jj < cw ? a.att[sbase + (int64_t)i * T + j0 + jj] : 0.f;
-  }
-  __syncthreads();
-  float* dbase = a.dqkv + (int64_t)bf * T * ld;
-  for (int e = threadIdx.x; e < T * kTatCW; e += 256) {  // dA[i][j] = sum_d dctx[i][d] V[j][d]
-    const int i = e / kTatCW, jj = e - i * kTatCW;
-    float acc = 0.f;
-    if (jj < cw)
-      for (int d = 0; d < dv; ++d) acc = fmaf(dCs[i * dvp + d], Vs[jj * dvp + d], acc);
-    dAs[e] = acc;
-  }
-  for (int e = threadIdx.x; e < cw * dv; e += 256) {  // dV[j][d] = sum_i A[i][j] dctx[i][d]
-    const int jj = e / dv, d = e - jj * dv;
-    float acc = 0.f;
-    for (int i = 0; i < T; ++i) acc = fmaf(As[i * kTatCW + jj], dCs[i * dvp + d], acc);
-    dbase[(int64_t)(j0 + jj) * ld + 2 * a.h * dk + hd * dv + d] = acc;
-  }
-  __syncthreads();
-  // column softmax backward: dS = A (dA - sum_i A dA) + d re_At
-  const int jj = threadIdx.x & 15, g = threadIdx.x >> 4;
-  float c = 0.f;
-  for (int i = g; i < T; i += 16) c = fmaf(As[i * kTatCW + jj], dAs[i * kTatCW + jj], c);
-  c = col_reduce16(c, red, false);
-  for (int i = g; i < T; i += 16) {
-    float v = As[i * kTatCW + jj] * (dAs[i * kTatCW + jj] - c);
-    if (jj < cw) {
-      if (a.dre) v += a.dre[sbase + (int64_t)i * T + j0 + jj];
-      a.dscore[sbase + (int64_t)i * T + j0 + jj] = v;
-    }
-    dAs[i * kTatCW + jj] = v;
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < cw * dk; e += 256) {  // dK[j][d] = s sum_i dS[i][j] Q[i][d]
-    const int jj2 = e / dk, d = e - jj2 * dk;
-    float acc = 0.f;
-    for (int i = 0; i < T; ++i) acc = fmaf(dAs[i * kTatCW + jj2], Qs[i * dkp + d], acc);
-    dbase[(int64_t)(j0 + jj2) * ld + a.h * dk + hd * dk + d] = acc * a.scale;
   }
 }
 
@@ -1181,222 +708,6 @@ __global__ __launch_bounds__(256) void colsum2d_kernel(Colsum2dArgs a) {
   }
 }
 
-// =====================================================================================
-// Temporal attention on the matrix cores: T <= 16 with T % 4 == 0, d_k = d_v = 32 — the
-// production TAt (model/DSTAGNN_my.py:27-67 at T = 12, d_k = d_v = 32).  One wave per
-// (b, f, head) problem (four per workgroup); the T x T tile is padded to 16 x 16 and every
-// product is a v_mfma_f32_16x16x4_f32 chain (fragments: A[l&15][k = l>>4], B[k = l>>4][l&15],
-// D[4(l>>4) + r][l&15]) whose operands come from global memory straight into registers.
-// Each product's contraction index is assigned to (k slot q = l>>4, step s) as 4q + s, so an
-// accumulator tile whose ROW index is that contraction index is, register s for register s,
-// the next product's A operand: scores -> P -> ctx in the forward, dA -> dS -> dK / dV in the
-// backward, with one 16 x 16 LDS transpose of dS for dQ.  (The VALU wave kernels above spend
-// ~2 400 VALU and ~700 LDS instructions per problem on index arithmetic and LDS operands.)
-// =====================================================================================
-constexpr int kTmD = 32;  // d_k = d_v of the matrix-core variant
-
-template <int T>
-__global__ __launch_bounds__(256) void tat_fwd_mfma_kernel(TatArgs a) {
-  static_assert(T % 4 == 0 && T <= 16, "one 16 x 16 tile, float4 rows");
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, c = l & 15, q = l >> 4;
-  const int id = blockIdx.x * kTatW + w;
-  if (id >= a.B * a.F * a.h) return;  // no barrier in this kernel
-  const int h = a.h, hd = id % h, bf = id / h, b = bf / a.F;
-  const int ld = 3 * h * kTmD;
-  const float* Qp = a.qkv + (int64_t)bf * T * ld + hd * kTmD;
-  const float* Kp = Qp + h * kTmD;
-  const float* Vp = Qp + 2 * h * kTmD;
-  const bool vi = c < T, vj = q < T / 4;
-  // ctx's B operand V[j = 4q + s][d = c + 16t] first: it does not depend on the scores
-  float vv[2][4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s)
-#pragma unroll
-    for (int t = 0; t < 2; ++t) vv[t][s] = (4 * q + s < T) ? Vp[(int64_t)(4 * q + s) * ld + c + 16 * t] : 0.f;
-  // S^T = K Q^T: A[m = j][k = d] = K[j = c][8q + s], B[k = d][n = i] = Q[i = c][8q + s]
-  float4 k0 = {0.f, 0.f, 0.f, 0.f}, k1 = k0, q0 = k0, q1 = k0;
-  if (vi) {
-    k0 = *reinterpret_cast<const float4*>(Kp + (int64_t)c * ld + 8 * q);
-    k1 = *reinterpret_cast<const float4*>(Kp + (int64_t)c * ld + 8 * q + 4);
-    q0 = *reinterpret_cast<const float4*>(Qp + (int64_t)c * ld + 8 * q);
-    q1 = *reinterpret_cast<const float4*>(Qp + (int64_t)c * ld + 8 * q + 4);
-  }
-  const int64_t sbase = (int64_t)id * T * T;
-  const float* rp = nullptr;
-  if (a.res_mode == DSTAGNN_RES_BCAST) rp = a.res + ((int64_t)b * h + hd) * T * T;
-  else if (a.res_mode == DSTAGNN_RES_FULL) rp = a.res + sbase;
-  float4 rr = {0.f, 0.f, 0.f, 0.f};
-  if (rp && vi && vj) rr = *reinterpret_cast<const float4*>(rp + c * T + 4 * q);
-  floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-  acc = mfma16(k0.x, q0.x, acc);
-  acc = mfma16(k0.y, q0.y, acc);
-  acc = mfma16(k0.z, q0.z, acc);
-  acc = mfma16(k0.w, q0.w, acc);
-  acc = mfma16(k1.x, q1.x, acc);
-  acc = mfma16(k1.y, q1.y, acc);
-  acc = mfma16(k1.z, q1.z, acc);
-  acc = mfma16(k1.w, q1.w, acc);
-  // lane (c, q) holds S[i = c][j = 4q + r]
-  const float rv[4] = {rr.x, rr.y, rr.z, rr.w};
-  float sc[4], p[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    sc[r] = acc[r] * a.scale;
-    sc[r] += rv[r];
-  }
-  if (vi && vj) *reinterpret_cast<float4*>(a.re_at + sbase + c * T + 4 * q) = make_float4(sc[0], sc[1], sc[2], sc[3]);
-  // softmax over the query axis i = the 16 lanes c of this quarter (column j = 4q + r)
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float m = xor_max_16(vi ? sc[r] : -INFINITY);
-    const float e = vi ? __expf(sc[r] - m) : 0.f;
-    const float inv = 1.f / xor_sum_16(e);
-    p[r] = vj ? e * inv : 0.f;
-  }
-  if (vi && vj) *reinterpret_cast<float4*>(a.att + sbase + c * T + 4 * q) = make_float4(p[0], p[1], p[2], p[3]);
-  // ctx = P V: A[m = i][k = j] = P[i = c][j = 4q + s] = p[s], B = vv
-  floatx4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    c0 = mfma16(p[s], vv[0][s], c0);
-    c1 = mfma16(p[s], vv[1][s], c1);
-  }
-  const int ldc = h * kTmD;
-  float* cb = a.ctx + (int64_t)bf * T * ldc + hd * kTmD + c;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int i = 4 * q + r;
-    if (i < T) {
-      cb[(int64_t)i * ldc] = c0[r];
-      cb[(int64_t)i * ldc + 16] = c1[r];
-    }
-  }
-}
-
-template <int T>
-__global__ __launch_bounds__(256) void tat_bwd_mfma_kernel(TatArgs a) {
-  static_assert(T % 4 == 0 && T <= 16, "one 16 x 16 tile");
-  __shared__ float tr[kTatW][16][17];  // per-wave dS transpose (dQ's A operand)
-  __shared__ float red[kTatW][T * T];  // F-sum: the workgroup's four dS tiles
-  __shared__ int last;
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, c = l & 15, q = l >> 4;
-  const int h = a.h, P = a.B * a.F * h;
-  const int nch = a.F / kTatW;
-  int id;
-  if (a.dres_sum) {  // workgroup = (b, head, four consecutive f): wave w takes f = 4 ch + w
-    const int bh = blockIdx.x / nch, ch = blockIdx.x - bh * nch;
-    id = ((bh / h) * a.F + ch * kTatW + w) * h + bh % h;
-  } else {
-    id = blockIdx.x * kTatW + w;
-  }
-  const bool live = id < P;
-  const int hd = id % h, bf = id / h;
-  const int ld = 3 * h * kTmD, ldc = h * kTmD;
-  const float* Qp = a.qkv + (int64_t)bf * T * ld + hd * kTmD;
-  const float* Kp = Qp + h * kTmD;
-  const float* Vp = Qp + 2 * h * kTmD;
-  const float* Cp = a.dctx + (int64_t)bf * T * ldc + hd * kTmD;
-  const int64_t sbase = (int64_t)id * T * T;
-  const bool vj = c < T;  // lane column j = c; rows i = 4q + r
-  // every load up front: dA's operands dC[i = c][8q + s] / V[j = c][8q + s]; the B operands
-  // [4q + s][c + 16t] of dV (dC), dK (Q) and dQ (K); A[i = 4q + r][j = c] and d re_At
-  float4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0, v0 = d0, v1 = d0;
-  float cb[2][4], qb[2][4], kb[2][4], at[4], dr[4];
-  if (live && vj) {
-    d0 = *reinterpret_cast<const float4*>(Cp + (int64_t)c * ldc + 8 * q);
-    d1 = *reinterpret_cast<const float4*>(Cp + (int64_t)c * ldc + 8 * q + 4);
-    v0 = *reinterpret_cast<const float4*>(Vp + (int64_t)c * ld + 8 * q);
-    v1 = *reinterpret_cast<const float4*>(Vp + (int64_t)c * ld + 8 * q + 4);
-  }
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const int i = 4 * q + s;
-    const bool ok = live && i < T;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      cb[t][s] = ok ? Cp[(int64_t)i * ldc + c + 16 * t] : 0.f;
-      qb[t][s] = ok ? Qp[(int64_t)i * ld + c + 16 * t] : 0.f;
-      kb[t][s] = ok ? Kp[(int64_t)i * ld + c + 16 * t] : 0.f;
-    }
-    at[s] = ok && vj ? a.att[sbase + i * T + c] : 0.f;
-    dr[s] = ok && vj && a.dre ? a.dre[sbase + i * T + c] : 0.f;
-  }
-  // dA = dC V^T: D[m = i][n = j], A[m = i][k = d] = dC[i = c][8q + s], B[k = d][n = j] = V[j = c][8q + s]
-  floatx4 dA = {0.f, 0.f, 0.f, 0.f};
-  dA = mfma16(d0.x, v0.x, dA);
-  dA = mfma16(d0.y, v0.y, dA);
-  dA = mfma16(d0.z, v0.z, dA);
-  dA = mfma16(d0.w, v0.w, dA);
-  dA = mfma16(d1.x, v1.x, dA);
-  dA = mfma16(d1.y, v1.y, dA);
-  dA = mfma16(d1.z, v1.z, dA);
-  dA = mfma16(d1.w, v1.w, dA);
-  // column softmax backward over i (this lane's four rows, then the quarters): dS = A (dA - sum_i A dA) + d re_At
-  float cs = 0.f;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) cs = fmaf(at[r], dA[r], cs);
-  cs = xor_sum_1632(cs);
-  float ds[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) ds[r] = at[r] * (dA[r] - cs) + dr[r];
-  if (a.keep_ds && live && vj) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (4 * q + r < T) a.dscore[sbase + (4 * q + r) * T + c] = ds[r];
-  }
-  // dV = A^T dC and dK = dS^T Q: A operand [m = j = c][k = i = 4q + s] = at[s] / ds[s]
-  floatx4 z = {0.f, 0.f, 0.f, 0.f};
-  floatx4 gv0 = z, gv1 = z, gk0 = z, gk1 = z, gq0 = z, gq1 = z;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    gv0 = mfma16(at[s], cb[0][s], gv0);
-    gv1 = mfma16(at[s], cb[1][s], gv1);
-    gk0 = mfma16(ds[s], qb[0][s], gk0);
-    gk1 = mfma16(ds[s], qb[1][s], gk1);
-  }
-  // dQ = dS K: A operand [m = i = c][k = j = 4q + s] = dS[c][4q + s], through LDS
-#pragma unroll
-  for (int r = 0; r < 4; ++r) tr[w][4 * q + r][c] = ds[r];
-  if (a.dres_sum && vj) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (4 * q + r < T) red[w][(4 * q + r) * T + c] = ds[r];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const float x = tr[w][c][4 * q + s];
-    gq0 = mfma16(x, kb[0][s], gq0);
-    gq1 = mfma16(x, kb[1][s], gq1);
-  }
-  if (live) {
-    float* db = a.dqkv + (int64_t)bf * T * ld + hd * kTmD + c;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = 4 * q + r;
-      if (i >= T) continue;
-      float* row = db + (int64_t)i * ld;
-      row[0] = gq0[r] * a.scale;
-      row[16] = gq1[r] * a.scale;
-      row[h * kTmD] = gk0[r] * a.scale;
-      row[h * kTmD + 16] = gk1[r] * a.scale;
-      row[2 * h * kTmD] = gv0[r];
-      row[2 * h * kTmD + 16] = gv1[r];
-    }
-  }
-  if (!a.dres_sum) return;
-  // res_att gradient sum_f dS (deterministic): the four tiles in wave order, one partial per
-  // workgroup, a ticket per (b, head); the last of its nch workgroups adds the partials in chunk
-  // order (handoff.hpp)
-  const int t = threadIdx.x, bh = blockIdx.x / nch, ch = blockIdx.x - bh * nch;
-  float* part = a.dscore + (int64_t)bh * nch * T * T;
-  if (t < T * T) st_agent(part + (int64_t)ch * T * T + t, ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t]);
-  if (!last_arrival(a.cnt + bh, nch, &last) || t >= T * T) return;
-  float v = 0.f;
-  for (int k = 0; k < nch; ++k) v += ld_agent(part + (int64_t)k * T * T + t);
-  a.dres_sum[(int64_t)bh * T * T + t] = v;
-}
-
 // out[a][i] = beta*out + sum_m in[a][m][i]; grid (i blocks, a)
 // out[a][i] = beta*out[a][i] + sum_m in[a][m][i]: a workgroup owns 32 consecutive i of one a;
 // its 8 wave-quarters sum interleaved m (8-way parallel chains per output instead of one
@@ -1767,142 +1078,6 @@ int op_transpose(const float* in, float* out, int R, int Cc, int batch, int64_t 
                  hipStream_t st) {
   dim3 grid((unsigned)cdiv64(Cc, 32), (unsigned)cdiv64(R, 32), (unsigned)batch);
   hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, st, in, out, R, Cc, in_bs, out_bs, beta);
-  DS_CHECK_LAUNCH();
-  return 0;
-}
-
-// dynamic LDS above 64 KB must be opted into per kernel (gfx950 has 160 KB per workgroup)
-static int allow_lds(const void* kernel, size_t bytes) {
-  hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) { set_last_error(std::string("LDS attribute: ") + hipGetErrorString(e)); return (int)e; }
-  return 0;
-}
-
-// the matrix-core TAt kernels: T in {4, 8, 12, 16}, d_k = d_v = 32, 16-B aligned operands
-// (float4 rows); DSTAGNN_TAT_MFMA=0 keeps the VALU wave kernels (A/B switch)
-static bool tat_mfma_ok(int T, int dk, int dv, std::initializer_list<const float*> ptrs) {
-  static const bool off = !env_flag("DSTAGNN_TAT_MFMA", true);
-  if (off || dk != kTmD || dv != kTmD || T % 4 != 0 || T < 4 || T > 16) return false;
-  for (const float* p : ptrs)
-    if (reinterpret_cast<uintptr_t>(p) % 16 != 0) return false;
-  return true;
-}
-static void launch_tat_bwd_mfma(const TatArgs& a, dim3 grid, hipStream_t st) {
-  const dim3 blk(64 * kTatW);
-  switch (a.T) {
-    case 4: hipLaunchKernelGGL(tat_bwd_mfma_kernel<4>, grid, blk, 0, st, a); break;
-    case 8: hipLaunchKernelGGL(tat_bwd_mfma_kernel<8>, grid, blk, 0, st, a); break;
-    case 12: hipLaunchKernelGGL(tat_bwd_mfma_kernel<12>, grid, blk, 0, st, a); break;
-    default: hipLaunchKernelGGL(tat_bwd_mfma_kernel<16>, grid, blk, 0, st, a); break;
-  }
-}
-
-static size_t tat_fwd_lds(int T, int dk, int dv) {
-  return sizeof(float) * (size_t)(2 * T * (dk + 1) + T * (dv + 1) + T * T);
-}
-static size_t tat_bwd_lds(int T, int dk, int dv) {
-  return sizeof(float) * (size_t)(2 * T * (dk + 1) + 2 * T * (dv + 1) + 2 * T * T);
-}
-
-int op_tat_fwd(int B, int F, int T, int h, int dk, int dv, const float* qkv, const float* res, int res_mode,
-               float* re_at, float* att, float* ctx, hipStream_t st) {
-  TatArgs a{};
-  a.B = B; a.F = F; a.T = T; a.h = h; a.dk = dk; a.dv = dv;
-  a.qkv = qkv; a.res = res; a.res_mode = res ? res_mode : 0; a.scale = 1.f / sqrtf((float)dk);
-  a.re_at = re_at; a.att = att; a.ctx = ctx;
-  const int P = B * F * h;
-  if (tat_mfma_ok(T, dk, dv, {qkv, res, re_at, att})) {
-    const dim3 grid((unsigned)cdiv64(P, kTatW)), blk(64 * kTatW);
-    switch (T) {
-      case 4: hipLaunchKernelGGL(tat_fwd_mfma_kernel<4>, grid, blk, 0, st, a); break;
-      case 8: hipLaunchKernelGGL(tat_fwd_mfma_kernel<8>, grid, blk, 0, st, a); break;
-      case 12: hipLaunchKernelGGL(tat_fwd_mfma_kernel<12>, grid, blk, 0, st, a); break;
-      default: hipLaunchKernelGGL(tat_fwd_mfma_kernel<16>, grid, blk, 0, st, a); break;
-    }
-    DS_CHECK_LAUNCH();
-    return 0;
-  }
-  if (T <= 16 && (size_t)kTatW * tat_wave_fwd_floats(T, dk, dv) * sizeof(float) <= 64 * 1024) {
-    hipLaunchKernelGGL(tat_fwd_wave_kernel, dim3((unsigned)cdiv64(P, kTatW)), dim3(64 * kTatW),
-                       (size_t)kTatW * tat_wave_fwd_floats(T, dk, dv) * sizeof(float), st, a);
-    DS_CHECK_LAUNCH();
-    return 0;
-  }
-  size_t lds = tat_fwd_lds(T, dk, dv);
-  if (lds > 64 * 1024) {  // long series: column chunks, then ctx = att . V as one batched GEMM
-    const size_t lc = sizeof(float) * (size_t)tat_cols_fwd_floats(T, dk);
-    if (lc > 160 * 1024) { set_last_error("tat_fwd: T too large for LDS"); return DSTAGNN_E_SHAPE; }
-    if (lc > 64 * 1024) DS_TRY(allow_lds((const void*)tat_fwd_cols_kernel, lc));
-    const int nch = (T + kTatCW - 1) / kTatCW;
-    hipLaunchKernelGGL(tat_fwd_cols_kernel, dim3((unsigned)(P * nch)), dim3(256), lc, st, a);
-    DS_CHECK_LAUNCH();
-    const int64_t ld = 2 * (int64_t)h * dk + (int64_t)h * dv, ldc = (int64_t)h * dv;
-    Gemm g;  // ctx[bf,i,hd,:] = sum_j att[bf,hd,i,j] V[bf,j,hd,:]
-    g.M = T; g.N = dv; g.K = T; g.batch = P;
-    g.A = att; g.am = idx1(T); g.ak = idx1(1); g.az = idx1((int64_t)T * T);
-    g.B = qkv; g.b_off = 2 * (int64_t)h * dk; g.bk = idx1(ld); g.bn = idx1(1); g.bz = idx2(h, dv, (int64_t)T * ld);
-    g.C = ctx; g.cm = idx1(ldc); g.cn = idx1(1); g.cz = idx2(h, dv, (int64_t)T * ldc);
-    return run_gemm(g, nullptr, 0, st);
-  }
-  hipLaunchKernelGGL(tat_fwd_kernel, dim3((unsigned)(B * F * h)), dim3(256), lds, st, a);
-  DS_CHECK_LAUNCH();
-  return 0;
-}
-
-int op_tat_bwd(int B, int F, int T, int h, int dk, int dv, const float* qkv, const float* att, const float* dctx,
-               const float* dre, float* dqkv, float* dscore, float* dres_sum, hipStream_t st) {
-  if (dres_sum) {  // the full dS is scratch; the output is its sum over f
-    if (tat_mfma_ok(T, dk, dv, {qkv, att, dctx, dre}) && F % kTatW == 0) {
-      int* cnt = stream_counters(st, B * h);
-      if (cnt) {
-        TatArgs a{};
-        a.B = B; a.F = F; a.T = T; a.h = h; a.dk = dk; a.dv = dv;
-        a.qkv = qkv; a.att = const_cast<float*>(att); a.scale = 1.f / sqrtf((float)dk);
-        a.dctx = dctx; a.dre = dre; a.dqkv = dqkv; a.dscore = dscore;
-        a.dres_sum = dres_sum; a.cnt = cnt; a.keep_ds = 0;
-        launch_tat_bwd_mfma(a, dim3((unsigned)(B * h * (F / kTatW))), st);
-        DS_CHECK_LAUNCH();
-        return 0;
-      }
-    }
-    DS_TRY(op_tat_bwd(B, F, T, h, dk, dv, qkv, att, dctx, dre, dqkv, dscore, nullptr, st));
-    return op_sum_middle(dscore, B, F, (int64_t)h * T * T, dres_sum, 0.f, st);
-  }
-  TatArgs a{};
-  a.B = B; a.F = F; a.T = T; a.h = h; a.dk = dk; a.dv = dv;
-  a.qkv = qkv; a.att = const_cast<float*>(att); a.scale = 1.f / sqrtf((float)dk);
-  a.dctx = dctx; a.dre = dre; a.dqkv = dqkv; a.dscore = dscore;
-  a.keep_ds = 1;
-  const int P = B * F * h;
-  if (tat_mfma_ok(T, dk, dv, {qkv, att, dctx, dre})) {
-    launch_tat_bwd_mfma(a, dim3((unsigned)cdiv64(P, kTatW)), st);
-    DS_CHECK_LAUNCH();
-    return 0;
-  }
-  if (T <= 16 && (size_t)kTatW * tat_wave_bwd_floats(T, dk, dv) * sizeof(float) <= 64 * 1024) {
-    hipLaunchKernelGGL(tat_bwd_wave_kernel, dim3((unsigned)cdiv64(P, kTatW)), dim3(64 * kTatW),
-                       (size_t)kTatW * tat_wave_bwd_floats(T, dk, dv) * sizeof(float), st, a);
-    DS_CHECK_LAUNCH();
-    return 0;
-  }
-  size_t lds = tat_bwd_lds(T, dk, dv);
-  if (lds > 64 * 1024) {  // long series: column chunks, then dQ = s dS . K as one batched GEMM
-    const size_t lc = sizeof(float) * (size_t)tat_cols_bwd_floats(T, dk, dv);
-    if (lc > 160 * 1024) { set_last_error("tat_bwd: T too large for LDS"); return DSTAGNN_E_SHAPE; }
-    if (lc > 64 * 1024) DS_TRY(allow_lds((const void*)tat_bwd_cols_kernel, lc));
-    const int nch = (T + kTatCW - 1) / kTatCW;
-    hipLaunchKernelGGL(tat_bwd_cols_kernel, dim3((unsigned)(P * nch)), dim3(256), lc, st, a);
-    DS_CHECK_LAUNCH();
-    const int64_t ld = 2 * (int64_t)h * dk + (int64_t)h * dv;
-    Gemm g;  // dQ[bf,i,hd,:] = s sum_j dS[bf,hd,i,j] K[bf,j,hd,:]
-    g.M = T; g.N = dk; g.K = T; g.batch = P;
-    g.A = dscore; g.am = idx1(T); g.ak = idx1(1); g.az = idx1((int64_t)T * T);
-    g.B = qkv; g.b_off = (int64_t)h * dk; g.bk = idx1(ld); g.bn = idx1(1); g.bz = idx2(h, dk, (int64_t)T * ld);
-    g.C = dqkv; g.cm = idx1(ld); g.cn = idx1(1); g.cz = idx2(h, dk, (int64_t)T * ld);
-    g.alpha = a.scale;
-    return run_gemm(g, nullptr, 0, st);
-  }
-  hipLaunchKernelGGL(tat_bwd_kernel, dim3((unsigned)(B * F * h)), dim3(256), lds, st, a);
   DS_CHECK_LAUNCH();
   return 0;
 }

@@ -1,4 +1,5 @@
-// ops.hpp — argument structs and launchers of the non-GEMM kernels (ops.hip).
+// ops.hpp — argument structs and launchers of the non-GEMM kernels (ops.hip; op_tat_fwd / op_tat_bwd:
+// tat.hip).
 #pragma once
 #include "common.hpp"
 

@@ -13,7 +13,7 @@
 //   2. Q | K | V = E Wqkv^T on the f32 matrix cores (v_mfma_f32_16x16x4_f32, 3 row tiles x the
 //      wave's 16-column tiles, contraction index 16 c + 4 q + s: one float4 per lane per operand
 //      and chunk; Wqkv re-laid (QW, NP) zero-padded by param_prep, streamed from L2);
-//   3. per (problem, head): tat_fwd_mfma's register-resident attention on the LDS tile;
+//   3. per (problem, head): the register-resident attention core (tat_core.hpp) on the LDS tile;
 //   4. u = ctx W_fc^T + E accumulated in the E tile in place;
 //   5. LayerNorm over N per row, writing u / mu / rs (saved for the backward) and O in its
 //      [(f,t)][(b,n)] order.
@@ -26,6 +26,7 @@
 #include "common.hpp"
 #include "handoff.hpp"
 #include "ops.hpp"
+#include "tat_core.hpp"
 
 namespace {
 
@@ -286,7 +287,7 @@ __global__ __launch_bounds__(64 * W, 1) void tat_fused_fwd_kernel(TatFusedArgs a
   __syncthreads();
   TF_MARK(2);
 
-  // ---- 3. attention per (problem, head) (tat_fwd_mfma_kernel's math, operands from LDS) ----
+  // ---- 3. attention per (problem, head) (tat_core.hpp, operands from LDS) -------------------
 #pragma unroll
   for (int k = 0; k < TPW; ++k) {
     const int task = w + W * k;
@@ -300,50 +301,16 @@ __global__ __launch_bounds__(64 * W, 1) void tat_fused_fwd_kernel(TatFusedArgs a
     const float* Vp = Qp + 2 * kTfHV;
     const int c = i;
     const bool vi = c < T, vj = q < T / 4;
-    float vv[2][4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) vv[t][s] = (4 * q + s < T) ? Vp[(4 * q + s) * kTfLQ + c + 16 * t] : 0.f;
-    float4 k0 = {0.f, 0.f, 0.f, 0.f}, k1 = k0, q0 = k0, q1 = k0;
-    if (vi) {
-      k0 = *reinterpret_cast<const float4*>(Kp + c * kTfLQ + 8 * q);
-      k1 = *reinterpret_cast<const float4*>(Kp + c * kTfLQ + 8 * q + 4);
-      q0 = *reinterpret_cast<const float4*>(Qp + c * kTfLQ + 8 * q);
-      q1 = *reinterpret_cast<const float4*>(Qp + c * kTfLQ + 8 * q + 4);
-    }
-    floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = mfma16(k0.x, q0.x, acc);
-    acc = mfma16(k0.y, q0.y, acc);
-    acc = mfma16(k0.z, q0.z, acc);
-    acc = mfma16(k0.w, q0.w, acc);
-    acc = mfma16(k1.x, q1.x, acc);
-    acc = mfma16(k1.y, q1.y, acc);
-    acc = mfma16(k1.z, q1.z, acc);
-    acc = mfma16(k1.w, q1.w, acc);
-    const float rv[4] = {rr[k].x, rr[k].y, rr[k].z, rr[k].w};
+    TatFwdOps o;
+    tat_fwd_load<T>(o, Qp, Kp, Vp, kTfLQ, c, q);
     float sc[4], pr[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      sc[r] = acc[r] * a.scale;
-      sc[r] += rv[r];
-    }
+    tat_fwd_scores(sc, o, rr[k], a.scale);
     const int tb = task * T * T;  // this task's tile in RA / AT ([p][hd] order = the global order)
     if (vi && vj) *reinterpret_cast<float4*>(RA + tb + c * T + 4 * q) = make_float4(sc[0], sc[1], sc[2], sc[3]);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float m = xor_max_16(vi ? sc[r] : -INFINITY);
-      const float e = vi ? __expf(sc[r] - m) : 0.f;
-      const float inv = 1.f / xor_sum_16(e);
-      pr[r] = vj ? e * inv : 0.f;
-    }
+    tat_fwd_softmax<T>(pr, sc, c, q);
     if (vi && vj) *reinterpret_cast<float4*>(AT + tb + c * T + 4 * q) = make_float4(pr[0], pr[1], pr[2], pr[3]);
-    floatx4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      c0 = mfma16(pr[s], vv[0][s], c0);
-      c1 = mfma16(pr[s], vv[1][s], c1);
-    }
+    floatx4 c0, c1;
+    tat_fwd_ctx(c0, c1, pr, o);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int ii = 4 * q + r;
@@ -726,7 +693,7 @@ __global__ __launch_bounds__(64 * W, 1) void tat_fused_bwd_kernel(TatFusedBwdArg
     }
   }
 
-  // ---- C. attention backward per (problem, head) (tat_bwd_mfma_kernel's math) ---------------
+  // ---- C. attention backward per (problem, head) (tat_core.hpp, operands from LDS) ----------
 #pragma unroll
   for (int k = 0; k < TPW; ++k) {
     const int task = w + W * k;
@@ -741,66 +708,19 @@ __global__ __launch_bounds__(64 * W, 1) void tat_fused_bwd_kernel(TatFusedBwdArg
     const float* Cp = Cs + rb * kTfLC + hd * kTfD;
     const int c = i;
     const bool vj = c < T;
-    float4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0, v0 = d0, v1 = d0;
-    float cb[2][4], qb[2][4], kb[2][4];
-    if (vj) {
-      d0 = *reinterpret_cast<const float4*>(Cp + c * kTfLC + 8 * q);
-      d1 = *reinterpret_cast<const float4*>(Cp + c * kTfLC + 8 * q + 4);
-      v0 = *reinterpret_cast<const float4*>(Vp + c * kTfLQ + 8 * q);
-      v1 = *reinterpret_cast<const float4*>(Vp + c * kTfLQ + 8 * q + 4);
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const int ii = 4 * q + s;
-      const bool ok = ii < T;
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        cb[t][s] = ok ? Cp[ii * kTfLC + c + 16 * t] : 0.f;
-        qb[t][s] = ok ? Qp[ii * kTfLQ + c + 16 * t] : 0.f;
-        kb[t][s] = ok ? Kp[ii * kTfLQ + c + 16 * t] : 0.f;
-      }
-    }
-    floatx4 dA = {0.f, 0.f, 0.f, 0.f};
-    dA = mfma16(d0.x, v0.x, dA);
-    dA = mfma16(d0.y, v0.y, dA);
-    dA = mfma16(d0.z, v0.z, dA);
-    dA = mfma16(d0.w, v0.w, dA);
-    dA = mfma16(d1.x, v1.x, dA);
-    dA = mfma16(d1.y, v1.y, dA);
-    dA = mfma16(d1.z, v1.z, dA);
-    dA = mfma16(d1.w, v1.w, dA);
-    float cs = 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) cs = fmaf(at[k][r], dA[r], cs);
-    cs += __shfl_xor(cs, 16, 64);
-    cs += __shfl_xor(cs, 32, 64);
+    TatBwdOps o;
+    tat_bwd_load<T>(o, Qp, Kp, Vp, kTfLQ, Cp, kTfLC, c, q, true);
     float ds[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ds[r] = at[k][r] * (dA[r] - cs) + dr[k][r];
+    TatBwdGrads g;
+    float* tr = TRs + w * 16 * 17;
+    tat_bwd_part1(ds, g, tr, o, at[k], dr[k], c, q);
     if (vj) {
 #pragma unroll
       for (int r = 0; r < 4; ++r)
         if (4 * q + r < T) DSs[task * T * T + (4 * q + r) * T + c] = ds[r];
     }
-    floatx4 z = {0.f, 0.f, 0.f, 0.f};
-    floatx4 gv0 = z, gv1 = z, gk0 = z, gk1 = z, gq0 = z, gq1 = z;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      gv0 = mfma16(at[k][s], cb[0][s], gv0);
-      gv1 = mfma16(at[k][s], cb[1][s], gv1);
-      gk0 = mfma16(ds[s], qb[0][s], gk0);
-      gk1 = mfma16(ds[s], qb[1][s], gk1);
-    }
-    float* tr = TRs + w * 16 * 17;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) tr[(4 * q + r) * 17 + c] = ds[r];
     wave_lds_sync();
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const float xv = tr[c * 17 + 4 * q + s];
-      gq0 = mfma16(xv, kb[0][s], gq0);
-      gq1 = mfma16(xv, kb[1][s], gq1);
-    }
+    tat_bwd_part2(g, tr, o, c, q);
     wave_lds_sync();  // (every lane's Q/K/V reads of this task precede the in-place writes below)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -814,12 +734,12 @@ __global__ __launch_bounds__(64 * W, 1) void tat_fused_bwd_kernel(TatFusedBwdArg
       int off = ii * kTfLQ + c;
       asm volatile("" : "+v"(off));
       float* row = Qp + off;
-      row[0] = gq0[r] * a.scale;
-      row[16] = gq1[r] * a.scale;
-      row[kTfHV] = gk0[r] * a.scale;
-      row[kTfHV + 16] = gk1[r] * a.scale;
-      row[2 * kTfHV] = gv0[r];
-      row[2 * kTfHV + 16] = gv1[r];
+      row[0] = g.gq0[r] * a.scale;
+      row[16] = g.gq1[r] * a.scale;
+      row[kTfHV] = g.gk0[r] * a.scale;
+      row[kTfHV + 16] = g.gk1[r] * a.scale;
+      row[2 * kTfHV] = g.gv0[r];
+      row[2 * kTfHV + 16] = g.gv1[r];
     }
   }
   __syncthreads();

@@ -1,8 +1,8 @@
 """GPU: the opt-in / A-B paths that the default run does not take, each held to the fp64 oracle in
 a subprocess (the library reads its switches once per process):
 
-  DSTAGNN_TAT_MFMA=0   the VALU wave kernels of the temporal attention instead of the
-                       matrix-core ones (ops.hip tat_*_mfma_kernel)
+  DSTAGNN_TAT_MFMA=0   the wave-per-problem VALU kernels of the temporal attention (tat.hip
+                       tat_*_valu_kernel<64>) instead of the matrix-core ones (tat_*_mfma_kernel)
   DSTAGNN_SIDE_CUMASK  the side stream confined to a CU subset (scheduling only: same results)
   DSTAGNN_SDDMM_NOPF=1 the aggregate-first SDDMM without its batch prefetch (4 waves per SIMD)
   DSTAGNN_SDDMM_PAIR=0 the aggregate-first SDDMM one sample per wave instead of sample pairs

@@ -372,6 +372,12 @@ CONFIGS = {
     "gambia": (2139, 144, 2, 2, 64, 32, 32),   # long series: sparse Chebyshev rows in 1024-element chunks
     "syn": (4096, 24, 5, 8, 512, 32, 32),
     "t24": (64, 24, 3, 2, 64, 32, 32),         # small graph, T >= 20: the split GTU tail
+    # the TAt hand-over band (tat.hip): at d_k = d_v = 32 a workgroup-per-problem VALU kernel holds
+    # 4 (99 T + T^2) bytes of LDS in the forward and 4 (132 T + 2 T^2) in the backward, and each
+    # direction leaves it for the column-chunk kernels past 65 536: the forward at T >= 88
+    # (T = 87: 64 728; T = 88: 65 824), the backward at T >= 64 (T = 63: 65 016; T = 64: 66 560).
+    # So for T in 64..87 the workgroup forward's att / re_At feed the column-chunk backward.
+    "t64": (48, 64, 3, 2, 64, 32, 32),
     # K = 3 at a long series: the aggregate-first backward's LDS image (16 K F T bytes = 221 KB)
     # does not fit, so cheb_agg_ok sends the block down the Theta-first sparse path
     "t144k3": (48, 144, 3, 2, 64, 32, 32),
@@ -593,7 +599,8 @@ def _run_config_vs_oracle(name, first, B, seed=3, flash=None, tol=TOL, relu_eps=
 
 CONFIG_CASES = [  # (name, first, B, flash)
     ("pems04", False, 1, None), ("pems07", False, 1, None), ("gambia", True, 1, None), ("gambia", False, 1, None),
-    ("syn", False, 1, None), ("t24", True, 1, None), ("t24", False, 1, None), ("pems08", False, 32, None),
+    ("syn", False, 1, None), ("t24", True, 1, None), ("t24", False, 1, None), ("t64", True, 1, None),
+    ("t64", False, 2, None), ("pems08", False, 32, None),
     # the fused (flash) Chebyshev attention is automatic on the sparse path: N <= 512 the
     # LDS-staged small-graph kernels (pems08, pems04, t24 above), larger N the streamed kernels
     # (pems07, gambia, syn); forced off at small, middle and large N, so the dense softmax path
