@@ -44,6 +44,9 @@ struct Arena {
   }
 };
 
+constexpr size_t kGemmWs = size_t(8) << 20;   // floats (32 MB) for split-K partial slabs
+constexpr size_t kPart = size_t(2) << 20;      // floats (8 MB) for column-sum partials
+
 struct Dims {
   int B, N, F, T, h, dk, dv, D, K, C;
   int64_t FT, BFT, BN, NN, HQ, HV, QW, KD, KC, CT, KCT, S;
@@ -51,6 +54,7 @@ struct Dims {
   bool first, sparse, flash;
   bool fsmall;      // flash on a small graph (flash_small): the LDS-staged kernels
   bool agg;         // sparse path in aggregate-first order (cheb_agg.hip): no x Theta GEMM
+  bool dth;         // ... with dTheta from the transposed SpMM itself: agg_k is not stored
   bool tfused;      // the temporal-attention stage as one kernel per direction (tat_fused.hip)
   int NP;           // tfused: node count padded to 16 (the re-laid Q|K|V weights' row length)
   bool tfused_bwd;  // ... and its backward (tat_fused.hip)
@@ -76,6 +80,7 @@ Dims mkdims(const dstagnn_block_dims& d) {
   m.fsmall = m.flash && flash_small(m.N);
   static const bool agg_env = env_flag("DSTAGNN_CHEB_AGG", true);
   m.agg = agg_env && m.sparse && cheb_agg_ok(m.F, m.C, m.K, m.T);
+  m.dth = m.agg && cheb_agg_dtheta_fused(m.B, m.N, m.F, m.C, m.K, m.T, (int64_t)kGemmWs);
   m.apa_nnz = m.fsmall ? std::max(d.cheb_apa_nnz, 0) : 0;
   m.tfused = tat_fused_fwd_ok(m.N, m.T, m.h, m.dk, m.dv);
   m.NP = m.tfused ? tat_fused_np(m.N) : 0;
@@ -134,6 +139,8 @@ SaveBufs plan_save(const Dims& m, Arena& a) {
   s.am = m.fsmall ? a.take((int64_t)m.K * m.NN) : nullptr;
   s.amt = m.fsmall ? a.take((int64_t)m.K * m.NN) : nullptr;
   s.papa = m.fsmall ? a.take(std::max<int64_t>(1, (int64_t)m.B * m.K * m.apa_nnz)) : nullptr;
+  // (m.dth leaves the xth slot, and m.gfused && m.gbfused the G slot, unwritten: the slots stay so
+  // that dstagnn_block_sizes reports the save size the forward-only workspace bound is stated in)
   s.xth = a.take(m.BN * m.KCT);
   s.X = a.take(m.BN * m.CT);
   for (int g = 0; g < 3; ++g) s.conv[g] = a.take(m.BN * 2 * m.C * std::max(m.Tg[g], 0));
@@ -151,9 +158,6 @@ SaveBufs plan_save(const Dims& m, Arena& a) {
   }
   return s;
 }
-
-constexpr size_t kGemmWs = size_t(8) << 20;   // floats (32 MB) for split-K partial slabs
-constexpr size_t kPart = size_t(2) << 20;      // floats (8 MB) for column-sum partials
 
 struct Scratch {
   float *gemm_ws, *part;
@@ -739,7 +743,7 @@ struct Fwd {
     ChebIO c;
     c.B = m.B; c.N = m.N; c.F = m.F; c.T = m.T; c.K = m.K; c.C = m.C;
     c.x = x; c.S = s.P; c.mask = p.mask; c.g = &gr; c.sparse = m.sparse; c.thcat = s.thcat;
-    c.P = s.P; c.W = s.W; c.xth = s.xth; c.X = s.X;
+    c.P = s.P; c.W = s.W; c.xth = m.dth ? nullptr : s.xth; c.X = s.X;  // m.dth: agg_k stays in LDS (SAVE = false)
     c.agg = m.agg;
     if (m.flash) {
       fl = make_fl(m, p, gr, s);
@@ -771,7 +775,9 @@ struct Fwd {
       g.fcmy_w = p.fcmy_w; g.fcmy_b = p.fcmy_b; g.res_w = p.res_w; g.res_b = p.res_b;
       g.ln_g = p.ln_g; g.ln_b = p.ln_b;
       if (d.train && d.drop_p > 0.f) { g.drop_p = d.drop_p; g.seed = d.seed; g.drop_off = drop_off(d, 1); }
-      g.G = s.G; g.tco = s.tco; g.r = s.r; g.mu = s.mu_c; g.rs = s.rs_c; g.out = out;
+      // G only for the unfused backward's fcmy weight gradient (the fused one recomputes the gates)
+      g.G = m.gbfused ? nullptr : s.G;
+      g.tco = s.tco; g.r = s.r; g.mu = s.mu_c; g.rs = s.rs_c; g.out = out;
       return op_gtu_fused_fwd(g, st);
     }
     // the three independent convolutions (kernel widths 3, 5, 7) as ONE grouped launch
@@ -943,6 +949,9 @@ struct Bwd {
     g.part = w.gcon_t;  // (sized max(BN CT, gtu_fused_bwd_part_floats(BN)) by plan_scratch)
     // (a flag written by the kernel's last workgroup instead of this fork measured 20 us/step
     // SLOWER: the side's GTU weight-gradient GEMM then starts under the SDDMM and both stretch)
+    // (no fork here, the weight gradients issued behind the SDDMM's kernel-carried flag in
+    // stage_cheb instead: 0.544 ms/step with {GTU dW, SpMM^T}, 0.526 with {SpMM^T, GTU dW},
+    // against 0.520 with this fork — same box, three interleaved rounds)
     DS_TRY(op_gtu_fused_bwd(g, st));
     DS_TRY(fork());
     return stage_tail_wgrads(true);
@@ -1065,21 +1074,30 @@ struct Bwd {
       // (One fork after the SDDMM for the side's SpMM, dTheta and mask gradient together
       // measured 0.705 vs 0.703 ms/step, same box: the SpMM then starts later.)
       ChebAg a = make_ag(B, N, K, F, C, m.T, &gr);
-      a.x = x; a.thcat = s.thcat; a.P = s.P; a.agg = s.xth; a.g = w.gpre; a.dW = w.dW; a.dx = dx; a.dx_beta = 1.f;
+      a.x = x; a.thcat = s.thcat; a.P = s.P; a.agg = m.dth ? nullptr : s.xth; a.g = w.gpre; a.dW = w.dW; a.dx = dx; a.dx_beta = 1.f;
+      bool adjacent = gd.theta[0] != nullptr;
+      for (int k = 1; k < K && adjacent; ++k) adjacent = gd.theta[k] == gd.theta[0] + (int64_t)k * F * C;
       if (m.flash) {
         a.nnz = (int)m.nnz; a.wsupp = s.wsupp; a.psupp = s.psupp; a.tsupp = gr.tsupp; a.dzs = w.dzs; a.cc = w.cc;
         if (m.fsmall) { a.csc2csr = gr.csc2csr; a.dzs_r = w.dzs_r; }
       }
       DS_TRY(ks.fork_on([&](ForkSig* sig) { return op_cheb_agg_sddmm(a, st, sig); }));
+      if (m.dth) {
+        // dTheta_k = sum_{b,i} x[b,i] h_k[b,i] inside the transposed SpMM (no agg_k, no GEMM): its
+        // fold rows in the side stream's GEMM workspace, idle between the side's GEMMs
+        a.dth_ws = ks.split() ? w.gemm_ws_side : w.gemm_ws;
+        if (adjacent) { a.dth = gd.theta[0]; a.dth_sk = (int64_t)F * C; a.dth_sf = C; }  // [k][f][c]
+        else { a.dth = w.dthcat; a.dth_sk = C; a.dth_sf = KC; }                          // (F, K*C), unpacked below
+      }
       DS_TRY(op_cheb_agg_spmm_t(a, ks.side()));
       DS_TRY(mark_side(&dx_ready));
-      {
+      if (m.dth) {
+        if (!adjacent) DS_TRY(unpack_theta(w.dthcat, K, F, C, gd.theta, ks.side()));
+      } else {
         Gemm g;  // dTheta[(k,f), c] = sum_{b,j,t} agg[b,j,k,f,t] g[b,j,t,c]
         g.M = K * F; g.N = C; g.K = B * N * m.T;
         g.A = s.xth; g.am = idx1(T); g.ak = idx2(T, 1, (int64_t)K * FT);
         g.B = w.gpre; g.bk = idx1(C); g.bn = idx1(1);
-        bool adjacent = gd.theta[0] != nullptr;
-        for (int k = 1; k < K && adjacent; ++k) adjacent = gd.theta[k] == gd.theta[0] + (int64_t)k * F * C;
         if (adjacent) {  // [k][f][c]: the parameters' own layout in the flat gradient buffer
           g.C = gd.theta[0]; g.cm = idx1(C); g.cn = idx1(1);
         } else {         // (F, K*C), unpacked below

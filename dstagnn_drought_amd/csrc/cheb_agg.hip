@@ -13,7 +13,8 @@
 //   sddmm    dagg_k[j] = Theta_k g_j^T                             (F x T per k, wave-local LDS)
 //            dW_k[i,j] = < x_i, dagg_k[j] >  on the support      (the softmax backward's input)
 //   spmm_t   dx_i    += sum_k Theta_k ( sum_{j in supp_row(i)} W_k[i,j] g_j )^T
-//   dTheta_k = sum_{b,j,t} agg_k[b,j,:,t] g[b,j,t,:]  — one GEMM (block.hip)
+//   dTheta_k = sum_{b,j,t} agg_k[b,j,:,t] g[b,j,t,:]  — one GEMM (block.hip), or, on the pair
+//            path, = sum_{b,i} x_i h_k[i] inside spmm_t (DTH): agg_k is then not saved
 //
 // so the Theta GEMM of the forward and the dx GEMM of the backward disappear together with
 // the (B,N,K,C,T) tensor and its gradient.  g = d(pre-ReLU X), layout (B,N,T,C); x (B,N,F,T).
@@ -680,15 +681,41 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(gather_wpe<
 // transposed SpMM for T <= 16 (T C <= 512): one wave per (sample PAIR, i), as the pair forward:
 // h_k of sample bsel accumulated over virtual entries v = 2 e + bsel of the row's support, the
 // two samples' h_k stacked into one MFMA A operand (m = bsel T + t) for the Theta_k chain.
+//
+// DTH: the kernel also produces dTheta, so the forward need not keep agg_k:
+//   dTheta_k = sum_{b,j} agg_k[b,j] g[b,j] = sum_{b,i} x[b,i] (F x T) h_k[b,i] (T x C)
+// The stacked h_k rows are in LDS once per order anyway; the wave adds E_k[f][c] += sum_m
+// x[b0 + s, i, f, t] h_k[m][c] (m = s T + t) on the matrix cores, A from the lane's own x row
+// (f = l32), B from LDS.  The four waves' E_k fold in LDS in wave order into the workgroup's row
+// of K F C floats (every workgroup of the grid writes one: padding ones zeros; a padding wave
+// repeats the last wave's work and contributes nothing), and cheb_agg_dtheta_fold_kernel sums
+// the rows.  Fixed orders throughout: the same bits every run.
+// (The rows folded inside this kernel by tickets instead, two levels of 16 as skinny_dw_kernel's,
+// ran 49.8 us at PEMS08 B = 32 against 20.8 us without DTH: 680 rows of 12 KB end in ONE
+// 256-thread workgroup reading 43 group rows behind two ticket round trips.  The fold launch
+// reads the 8.4 MB with 48 workgroups; DESIGN has the numbers.)
 // ---------------------------------------------------------------------------------------
-template <int kNQ, int KM>  // kNQ >= T * C / 64 (<= 8)
+// the variant whose registers do not hold the x operand beside the K accumulators at its
+// occupancy (it would spill 5 VGPRs) keeps that operand in LDS instead (+4 KB per wave)
+template <int kNQ, int KM>
+constexpr bool dth_x_lds() { return kNQ == 4 && KM == 3; }
+// the (NQ, KM) forms that take the K accumulators without scratch and at the occupancy of the
+// form without them (-Rpass-analysis=kernel-resource-usage, DESIGN): not <1, .> and <2, 2>
+// (8 / 6 / 5 waves per SIMD without, 4 with), not <1, 5> and <2, 5> (spill), not KM = 8
+constexpr bool dth_form_ok(int nq, int km) { return km <= 5 && nq >= 2 && nq <= 8 && !(nq == 2 && km != 3); }
+
+template <int kNQ, int KM, bool DTH = false>  // kNQ >= T * C / 64 (<= 8)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(gather_wpe<kNQ, 2 * KM>(), 8))) void cheb_agg_spmm_t2_kernel(ChebAg a) {
   static_assert(kNQ <= 8, "T C <= 512");
+  constexpr bool XL = DTH && dth_x_lds<kNQ, KM>();
   __shared__ float Hs[4][32 * kAs];
+  __shared__ float Xs[XL ? 4 : 1][XL ? 32 * kAs : 1];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5, l32 = lane & 31;
-  const int64_t wv = xcd_block(a.xcd_order) * 4 + w;
+  const int64_t wv0 = xcd_block(a.xcd_order) * 4 + w;
   const int npair = (a.B + 1) >> 1;
-  if (wv >= (int64_t)npair * a.N) return;
+  const bool active = wv0 < (int64_t)npair * a.N;
+  if (!DTH && !active) return;
+  const int64_t wv = DTH ? min(wv0, (int64_t)npair * a.N - 1) : wv0;
   const int bp = (int)(wv / a.N), i = (int)(wv % a.N), b0 = 2 * bp, nb = min(2, a.B - b0);
   const int T = a.T, TC = T * a.C;
   const int64_t NN = (int64_t)a.N * a.N;
@@ -758,6 +785,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(gather_wpe<
         for (int q = 0; q < kNQ; ++q) v[e][q] = vn[e][q];
     }
   }
+  // (DTH operands only from here on: the support walk above keeps its registers)
+  float xa[DTH ? 16 : 1];  // A[f = l32][kk = m] = x[b0 + ms, i, f, mt], m = 2 s + h (zero past F / the pair's rows)
+  floatx16 E[DTH ? KM : 1];
+  float* xs = Xs[XL ? w : 0];  // XL: the same operand as [m][f] in LDS (read behind the loop's first wave_lds_sync)
+  if constexpr (DTH) {
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      const int m = 2 * s + h, ms = m >= T ? 1 : 0, mt = m - ms * T;
+      xa[s] = (l32 < a.F && m < nb * T) ? a.x[((int64_t)(b0 + ms) * a.N + i) * a.F * T + (int64_t)l32 * T + mt] : 0.f;
+      if constexpr (XL) xs[m * kAs + l32] = xa[s];
+    }
+#pragma unroll
+    for (int k = 0; k < KM; ++k) E[k] = zero16();
+  }
   floatx16 acc = zero16();
 #pragma unroll
   for (int k = 0; k < KM; ++k) {
@@ -778,17 +819,78 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(gather_wpe<
       const float av = (c < a.C && l32 < nb * T) ? hs[l32 * kAs + c] : 0.f;
       acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bt[s], acc, 0, 0, 0);
     }
+    if constexpr (DTH) {
+#pragma unroll
+      for (int s = 0; s < 16; ++s) {  // E_k[f][n = c] += sum_m x[f][m] h_k[m][c]
+        if (2 * s >= nb * T) break;
+        const int m = 2 * s + h;
+        const float bv = (m < nb * T && l32 < a.C) ? hs[m * kAs + l32] : 0.f;
+        const float xv = XL ? xs[m * kAs + l32] : xa[s];
+        E[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(xv, bv, E[k], 0, 0, 0);
+      }
+    }
     wave_lds_sync();
   }
-  if (l32 >= a.F) return;
+  if constexpr (!DTH) {
+    if (l32 >= a.F) return;
+  }
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int m = frow(r, h), ms = m >= T ? 1 : 0, mt = m - ms * T;
-    if (m < nb * T) {
+    if (m < nb * T && (!DTH || (active && l32 < a.F))) {
       float* d = a.dx + ((int64_t)(b0 + ms) * a.N + i) * a.F * T + (int64_t)l32 * T + mt;
       *d = a.dx_beta * *d + acc[r];
     }
   }
+  if constexpr (DTH) {
+    const int FC = a.F * a.C, P = a.K * FC;
+    float* part = a.dth_ws + (int64_t)blockIdx.x * P;
+    __syncthreads();  // every wave is done with its h_k tile
+#pragma unroll
+    for (int k = 0; k < KM; ++k) {
+      if (k >= a.K) break;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) hs[frow(r, h) * kAs + l32] = active ? E[k][r] : 0.f;
+      __syncthreads();
+      for (int e = threadIdx.x; e < FC; e += 256) {
+        const int f = e / a.C, o = f * kAs + (e - f * a.C);
+        part[k * FC + e] = ((Hs[0][o] + Hs[1][o]) + Hs[2][o]) + Hs[3][o];
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// dTheta[k sk + f sf + c] = the sum of the nrows workgroup rows of part (P = K F C floats each),
+// rows in a fixed order: a workgroup owns 16 column quads; thread (sub = t / 16, quad t % 16)
+// sums rows sub, sub + 16, ... (8 loads in flight), the 16 subsets then in order through LDS.
+__global__ __launch_bounds__(256) void cheb_agg_dtheta_fold_kernel(const float* part, int nrows, int P, int F, int C,
+                                                                    float* out, int64_t sk, int64_t sf) {
+  __shared__ float4 red[256];
+  const int t = threadIdx.x, sub = t >> 4, q = blockIdx.x * 16 + (t & 15), P4 = P >> 2;
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (q < P4) {
+    const float4* p = reinterpret_cast<const float4*>(part) + q;
+    for (int r0 = sub; r0 < nrows; r0 += 16 * 8) {
+      float4 u[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        u[j] = r0 + 16 * j < nrows ? p[(int64_t)(r0 + 16 * j) * P4] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { v.x += u[j].x; v.y += u[j].y; v.z += u[j].z; v.w += u[j].w; }
+    }
+  }
+  red[t] = v;
+  __syncthreads();
+  if (sub != 0 || q >= P4) return;
+  float4 tot = red[t];
+  for (int s = 1; s < 16; ++s) {
+    const float4 x = red[16 * s + t];
+    tot.x += x.x; tot.y += x.y; tot.z += x.z; tot.w += x.w;
+  }
+  const int e = 4 * q, FC = F * C, k = e / FC, r = e - k * FC, f = r / C, c = r - f * C;  // (C % 4 == 0: one (k, f) per quad)
+  float* o = out + k * sk + f * sf + c;
+  o[0] = tot.x; o[1] = tot.y; o[2] = tot.z; o[3] = tot.w;
 }
 
 int nq_of(int n) { return n <= 64 ? 1 : n <= 128 ? 2 : n <= 256 ? 4 : n <= 384 ? 6 : n <= 512 ? 8 : n <= 768 ? 12 : 16; }
@@ -908,6 +1010,13 @@ struct SpmmT2L {
     if constexpr (NQ <= 8) hipLaunchKernelGGL((cheb_agg_spmm_t2_kernel<NQ, KM>), l.grid, dim3(256), 0, l.st, l.a);
   }
 };
+// ... producing dTheta too (a.dth set; the forms of dth_form_ok)
+template <int NQ, int KM>
+struct SpmmT2DL {
+  static void run(const Launch& l) {
+    if constexpr (dth_form_ok(NQ, KM)) hipLaunchKernelGGL((cheb_agg_spmm_t2_kernel<NQ, KM, true>), l.grid, dim3(256), 0, l.st, l.a);
+  }
+};
 template <int NQ, int KM>
 struct SpmmTL {
   static void run(const Launch& l) {
@@ -926,6 +1035,22 @@ int check(const ChebAg& a) {
 size_t sddmm_lds_bytes(int K, int F, int T) { return (size_t)4 * K * F * T * sizeof(float); }
 
 }  // namespace
+
+// fold scratch of the in-kernel dTheta: one row of K F C floats per workgroup
+int64_t cheb_agg_dtheta_ws_floats(int B, int N, int F, int C, int K) {
+  return (int64_t)grid_rows((int64_t)((B + 1) / 2) * N) * K * F * C;
+}
+
+// The pair kernels (T <= 16, DSTAGNN_AGG_PAIR), a kernel form that holds the K accumulators
+// (dth_form_ok: K <= 5 — cheb_agg_spmm_t2_kernel<., 8> spills even without them; K <= 5 also
+// keeps the forward's SAVE = false forms at the training forms' occupancy, gather_wpe_fwd),
+// and the fold rows within the scratch.
+bool cheb_agg_dtheta_fused(int B, int N, int F, int C, int K, int T, int64_t ws_floats) {
+  static const bool pair_env = env_flag("DSTAGNN_AGG_PAIR", true);
+  if (!pair_env || B < 1 || N < 1 || !cheb_agg_ok(F, C, K, T) || T > 16) return false;
+  if (!dth_form_ok(nq_of(T * C), km_of(K))) return false;
+  return cheb_agg_dtheta_ws_floats(B, N, F, C, K) <= ws_floats;
+}
 
 // F <= 32 (one MFMA contraction / tile side), C = 16 or 32 (16-float operand rows), K <= 8
 // (the kernels' order templates), and the backward SDDMM's per-workgroup LDS image of the K
@@ -980,8 +1105,22 @@ int op_cheb_agg_sddmm(const ChebAg& a0, hipStream_t st, ForkSig* sig) {
 
 int op_cheb_agg_spmm_t(const ChebAg& a0, hipStream_t st) {
   DS_TRY(check(a0));
-  const ChebAg a = with_order(a0);
+  ChebAg a = with_order(a0);
   static const bool pair_env = env_flag("DSTAGNN_AGG_PAIR", true);
+  if (a.dth) {  // dTheta from the kernel itself: the caller asked cheb_agg_dtheta_fused first
+    if (!a.dth_ws || !cheb_agg_dtheta_fused(a.B, a.N, a.F, a.C, a.K, a.T, cheb_agg_dtheta_ws_floats(a.B, a.N, a.F, a.C, a.K))) {
+      set_last_error("cheb_agg_spmm_t: dTheta in the kernel needs the pair path, K <= 5 and its fold scratch");
+      return DSTAGNN_E_ARG;
+    }
+    const unsigned nwg = grid_rows((int64_t)((a.B + 1) / 2) * a.N);
+    dispatch<SpmmT2DL>(nq_of(a.T * a.C), km_of(a.K), Launch{a, dim3(nwg), 0, st});
+    DS_CHECK_LAUNCH();
+    const int P = a.K * a.F * a.C;
+    hipLaunchKernelGGL(cheb_agg_dtheta_fold_kernel, dim3((unsigned)cdiv64(P / 4, 16)), dim3(256), 0, st, a.dth_ws, (int)nwg,
+                       P, a.F, a.C, a.dth, a.dth_sk, a.dth_sf);
+    DS_CHECK_LAUNCH();
+    return 0;
+  }
   if (pair_env && a.T <= 16 && a.T * a.C <= 512) {  // sample pairs per wave (cheb_agg_spmm_t2_kernel)
     dispatch<SpmmT2L>(nq_of(a.T * a.C), km_of(a.K), Launch{a, dim3(grid_rows((int64_t)((a.B + 1) / 2) * a.N)), 0, st});
     DS_CHECK_LAUNCH();

@@ -286,7 +286,8 @@ __global__ __launch_bounds__(kGW * 64, 1) void gtu_fwd_fused_kernel(GtuFusedArgs
   }
   TF_MARK(6);
   // G out (the fcmy weight gradient's operand): the nodes' [c][s] rows are one contiguous block
-  if (SAVE) {
+  // (a.G null: the fused backward follows, which recomputes the gates from conv_k)
+  if (SAVE && a.G) {
     float4* gout = reinterpret_cast<float4*>(a.G + bn0 * kGC * kGS);
     for (int e4 = tid; e4 < nn * kGC * (kGS / 4); e4 += NT) {
       const int nc = e4 / (kGS / 4), s = 4 * (e4 - nc * (kGS / 4));
@@ -766,14 +767,15 @@ int op_gtu_fused_fwd(const GtuFusedArgs& a, hipStream_t st) {
     set_last_error("gtu_fused_fwd: unsupported shape");
     return DSTAGNN_E_SHAPE;
   }
-  // forward-only: every saved-for-backward output null (the SAVE = false kernel); a mix is an error
-  const int nsave = (a.G != nullptr) + (a.tco != nullptr) + (a.r != nullptr) + (a.mu != nullptr) + (a.rs != nullptr) +
+  // forward-only: every saved-for-backward output null (the SAVE = false kernel).  Training: all
+  // set, or all but G (only the unfused backward reads G); any other mix is an error
+  const int nsave = (a.tco != nullptr) + (a.r != nullptr) + (a.mu != nullptr) + (a.rs != nullptr) +
                     (a.conv[0] != nullptr) + (a.conv[1] != nullptr) + (a.conv[2] != nullptr);
-  if (nsave != 0 && nsave != 8) {
-    set_last_error("gtu_fused_fwd: saved outputs must be all set or all null");
+  if ((nsave != 0 && nsave != 7) || (nsave == 0 && a.G)) {
+    set_last_error("gtu_fused_fwd: saved outputs must be all set (G optional) or all null");
     return DSTAGNN_E_ARG;
   }
-  const bool save = nsave == 8;
+  const bool save = nsave == 7;
   bool al = gf_al16(a.X) && gf_al16(a.x) && gf_al16(a.G) && gf_al16(a.tco) && gf_al16(a.r) && gf_al16(a.mu) &&
             gf_al16(a.rs) && gf_al16(a.out) && gf_al16(a.fcmy_b);
   for (int q = 0; q < 3; ++q) al = al && gf_al16(a.conv[q]) && gf_al16(a.wt[q]) && gf_al16(a.bias[q]);

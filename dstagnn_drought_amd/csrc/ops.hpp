@@ -198,8 +198,18 @@ struct ChebAg {
   float* dx = nullptr; float dx_beta = 1.f;  // spmm_t: dx = dx_beta dx + (the Chebyshev path's gradient)
   int xcd_order = 0;
   uint32_t* sig = nullptr; uint32_t sig_v = 0;  // kernel-written stream signal (SDDMM; common.hpp)
+  // spmm_t, pair path: dTheta_k = sum_{b,i} x[b,i] h_k[b,i] from the kernel itself (no agg_k).
+  // dth null: dTheta is the caller's GEMM over agg.  dth[k dth_sk + f dth_sf + c]; dth_ws holds
+  // cheb_agg_dtheta_ws_floats(...) floats of the launching stream's scratch.
+  float* dth = nullptr; int64_t dth_sk = 0, dth_sf = 0;
+  float* dth_ws = nullptr;
 };
 bool cheb_agg_ok(int F, int C, int K, int T);
+// dTheta inside the pair transposed SpMM (cheb_agg.hip): the one predicate the forward (agg_k
+// not stored), the backward (no dTheta GEMM) and the planners share; ws_floats: the fold's
+// scratch the caller has on the SpMM's stream
+bool cheb_agg_dtheta_fused(int B, int N, int F, int C, int K, int T, int64_t ws_floats);
+int64_t cheb_agg_dtheta_ws_floats(int B, int N, int F, int C, int K);
 int op_cheb_agg_fwd(const ChebAg& a, hipStream_t st);
 int op_cheb_agg_sddmm(const ChebAg& a, hipStream_t st, ForkSig* sig = nullptr);
 int op_cheb_agg_spmm_t(const ChebAg& a, hipStream_t st);
