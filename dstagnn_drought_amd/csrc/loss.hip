@@ -19,6 +19,14 @@
 //                        (coalesced; its p never changes), keeps four fp64 sums, LDS folds them
 //                        over rl in order, workgroups hand off as above and the last one adds the
 //                        folded sums into the table.  No floating-point atomics anywhere.
+//   metrics_masked_kernel (B, N, P) predictions / targets -> a running (P, 8) horizon table and an
+//                        optional running (N, 8) node table of fp64 sums over the VALID entries
+//                        (the criterion's is_valid): count, sum e, sum |e|, sum e^2, sum |e / t|
+//                        over t != mape_null, its count, sum t, sum t^2.  A workgroup owns a strip
+//                        of 256 / P nodes: thread nl P + p walks the samples of element (n0 + nl,
+//                        p), LDS folds the strip over nl (per horizon: a partial handed off as
+//                        above) and over p (per node: added straight into the node table, whose
+//                        rows have one owning workgroup each).
 //
 // A masked entry is selected out (never multiplied by zero): a NaN target under the NaN mask
 // leaves the loss finite and its gradient entry exactly 0.  A NaN prediction at a valid entry makes
@@ -230,6 +238,94 @@ __global__ __launch_bounds__(kMetThreads) void metrics_accum_kernel(int64_t n, i
   }
 }
 
+constexpr int kMmThreads = 256, kMmCols = 8, kMmUnroll = 4, kMmFold = 8;
+
+// one entry into a thread's eight sums: e, e * e and e / t in fp32, every add in fp64; t and t * t
+// as doubles (the product of two floats is exact there)
+__device__ __forceinline__ void masked_entry(double (&s)[kMmCols], int mask, float null_val, float mape_null,
+                                             float pv, float tv) {
+  if (!is_valid(mask, null_val, tv)) return;  // selected out: a NaN target never reaches a sum
+  const float e = pv - tv;
+  s[0] += 1.0;
+  s[1] += (double)e;
+  s[2] += (double)fabsf(e);
+  s[3] += (double)(e * e);
+  if (tv != mape_null) {
+    s[4] += (double)fabsf(e / tv);
+    s[5] += 1.0;
+  }
+  s[6] += (double)tv;
+  s[7] += (double)tv * (double)tv;
+}
+
+__global__ __launch_bounds__(kMmThreads) void metrics_masked_kernel(int B, int N, int P,
+                                                                   const float* __restrict__ pred,
+                                                                   const float* __restrict__ tg, int mask,
+                                                                   float null_val, float mape_null,
+                                                                   double* __restrict__ part, int* ticket,
+                                                                   double* __restrict__ htable,
+                                                                   double* __restrict__ ntable) {
+  __shared__ double red[kMmCols][kMmThreads];
+  __shared__ int last;
+  const int t = threadIdx.x;
+  const int TN = kMmThreads / P;                   // nodes of a whole strip
+  const int n0 = (int)blockIdx.x * TN;             // (the grid is ceil(N / TN): n0 < N)
+  const int tn = N - n0 < TN ? N - n0 : TN;        // nodes of this strip (the last one is partial)
+  double s[kMmCols] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (t < tn * P) {
+    // element (b, n0 + nl, p) with t = nl P + p sits at b N P + n0 P + t: for a fixed b the strip
+    // reads tn P contiguous floats
+    const int64_t step = (int64_t)N * P;
+    const float* __restrict__ pp = pred + (int64_t)n0 * P + t;
+    const float* __restrict__ tp = tg + (int64_t)n0 * P + t;
+    int b = 0;
+    for (; b + kMmUnroll <= B; b += kMmUnroll) {  // the loads of kMmUnroll samples in flight together
+      float pv[kMmUnroll], tv[kMmUnroll];
+#pragma unroll
+      for (int u = 0; u < kMmUnroll; ++u) pv[u] = pp[(b + u) * step], tv[u] = tp[(b + u) * step];
+#pragma unroll
+      for (int u = 0; u < kMmUnroll; ++u) masked_entry(s, mask, null_val, mape_null, pv[u], tv[u]);
+    }
+    for (; b < B; ++b) masked_entry(s, mask, null_val, mape_null, pp[b * step], tp[b * step]);
+  }
+#pragma unroll
+  for (int c = 0; c < kMmCols; ++c) red[c][t] = s[c];
+  __syncthreads();
+  // per node, over p in order: item = nl 8 + c lands on ntable[(n0 + nl) 8 + c].  This workgroup is
+  // the only one that ever touches these rows and launches on a stream are ordered: plain adds.
+  if (ntable != nullptr) {
+    for (int item = t; item < kMmCols * tn; item += kMmThreads) {
+      const int nl = item / kMmCols, c = item - nl * kMmCols;
+      double a = 0.0;
+      for (int p = 0; p < P; ++p) a += red[c][nl * P + p];
+      ntable[(int64_t)n0 * kMmCols + item] += a;
+    }
+  }
+  // per horizon, over nl in order (the idle rows of a partial strip hold zeros); item = c P + p
+  const int items = kMmCols * P;
+  for (int item = t; item < items; item += kMmThreads) {
+    const int c = item / P, p = item - c * P;
+    double a = 0.0;
+    for (int nl = 0; nl < TN; ++nl) a += red[c][nl * P + p];
+    st_agent(part + (int64_t)blockIdx.x * items + item, a);
+  }
+  if (!last_arrival(ticket, (int)gridDim.x, &last)) return;
+  // the last arrival: the partials in workgroup order, kMmFold sc1 loads issued before their adds
+  const int G = (int)gridDim.x;
+  for (int item = t; item < items; item += kMmThreads) {
+    const int c = item / P, p = item - c * P;
+    double a = 0.0;
+    for (int k0 = 0; k0 < G; k0 += kMmFold) {
+      double u[kMmFold];
+#pragma unroll
+      for (int k = 0; k < kMmFold; ++k) u[k] = k0 + k < G ? ld_agent(part + (int64_t)(k0 + k) * items + item) : 0.0;
+#pragma unroll
+      for (int k = 0; k < kMmFold; ++k) a += u[k];
+    }
+    htable[p * kMmCols + c] += a;
+  }
+}
+
 int64_t loss_grid(int64_t n) {
   const int64_t tiles = (n + kLossTile - 1) / kLossTile;
   return tiles < 1 ? 1 : tiles > kLossMaxWg ? kLossMaxWg : tiles;
@@ -272,6 +368,15 @@ int loss_args(const char* who, const dstagnn_loss_cfg* cfg, int64_t n, const voi
   if (out->kind == DSTAGNN_LOSS_SMOOTH_L1 && out->param == 0.f) out->kind = DSTAGNN_LOSS_MAE;
   if (out->mask_mode == DSTAGNN_MASK_NEQ && std::isnan(out->null_val)) out->mask_mode = DSTAGNN_MASK_NAN;
   return 0;
+}
+
+// ceil(N / (256 / P)) workgroups, or 0 for a shape the masked metrics reject
+int64_t masked_grid(int64_t B, int64_t N, int P) {
+  if (P < 1 || P > kMetMaxP || B <= 0 || N <= 0) return 0;
+  const int64_t lim = (1ll << 31) - 1;
+  if (N > lim / P || B > lim / (N * P)) return 0;  // B N P >= 2^31
+  const int64_t TN = kMmThreads / P;
+  return (N + TN - 1) / TN;
 }
 
 }  // namespace
@@ -355,6 +460,47 @@ int dstagnn_metrics_accumulate(int64_t rows, int P, const float* pred, const flo
   hipLaunchKernelGGL(metrics_accum_kernel, dim3((unsigned)metrics_grid(rows, P)), dim3(kMetThreads), 0, st,
                      rows * (int64_t)P, P, pred, target, null_val, std::isnan(null_val) ? 1 : 0,
                      static_cast<double*>(scratch), ticket, table);
+  DS_CHECK_LAUNCH();
+  return 0;
+}
+
+int64_t dstagnn_metrics_masked_scratch_bytes(int64_t B, int64_t N, int P) {
+  return masked_grid(B, N, P) * kMmCols * (int64_t)P * (int64_t)sizeof(double);
+}
+
+int dstagnn_metrics_accumulate_masked(int64_t B, int64_t N, int P, const float* pred, const float* target,
+                                      int mask_mode, float null_val, float mape_null, double* htable,
+                                      double* ntable, void* scratch, size_t scratch_bytes, dstagnn_stream_t stream) {
+  if (P < 1 || P > kMetMaxP) {
+    set_last_error("metrics_accumulate_masked: P (the last axis) must be in [1, 256], got " + std::to_string(P));
+    return DSTAGNN_E_SHAPE;
+  }
+  const int64_t grid = masked_grid(B, N, P);
+  if (grid == 0) {
+    set_last_error("metrics_accumulate_masked: B and N must be >= 1 and B * N * P in [1, 2^31)");
+    return DSTAGNN_E_SHAPE;
+  }
+  if (!pred || !target || !htable || !scratch) {
+    set_last_error("metrics_accumulate_masked: null pred / target / htable / scratch");
+    return DSTAGNN_E_ARG;
+  }
+  if (mask_mode < DSTAGNN_MASK_NONE || mask_mode > DSTAGNN_MASK_NAN) {
+    set_last_error("metrics_accumulate_masked: unknown mask mode " + std::to_string(mask_mode));
+    return DSTAGNN_E_ARG;
+  }
+  if (scratch_bytes < (size_t)dstagnn_metrics_masked_scratch_bytes(B, N, P)) {
+    set_last_error("metrics_accumulate_masked: scratch smaller than dstagnn_metrics_masked_scratch_bytes(B, N, P)");
+    return DSTAGNN_E_SPACE;
+  }
+  if (mask_mode == DSTAGNN_MASK_NEQ && std::isnan(null_val)) mask_mode = DSTAGNN_MASK_NAN;  // as loss_args
+  hipStream_t st = (hipStream_t)stream;
+  int* ticket = stream_counters(st, 1);
+  if (!ticket) {
+    set_last_error("metrics_accumulate_masked: no ticket counter for this stream");
+    return DSTAGNN_E_ARG;
+  }
+  hipLaunchKernelGGL(metrics_masked_kernel, dim3((unsigned)grid), dim3(kMmThreads), 0, st, (int)B, (int)N, P, pred,
+                     target, mask_mode, null_val, mape_null, static_cast<double*>(scratch), ticket, htable, ntable);
   DS_CHECK_LAUNCH();
   return 0;
 }

@@ -15,6 +15,7 @@
 //   dstagnn::head_fwd/bwd   DSTAGNN_submodule's cat + final_conv + final_fc (:272-280)
 //   dstagnn::loss_fwd/bwd   the criterion (train_DSTAGNN_my.py:132, :156-157) and its masked variants
 //   dstagnn::metrics_update per-horizon MAE / RMSE / MAPE sums on the device (lib/utils1.py:418-431)
+//   dstagnn::metrics_update_masked the same over the valid entries only, per horizon and per node
 //   dstagnn::window_gather  a batch's input windows and targets cut from the raw series, transposed
 //                           and z-scored (prepareData.py:63-161 per batch instead of once per label)
 //   dstagnn::window_stats   the training windows' mean / std from the raw series (prepareData.py:149-161)
@@ -981,6 +982,36 @@ void metrics_update(const Tensor& pred, const Tensor& target, double null_val, T
            "dstagnn_metrics_accumulate");
 }
 
+// pred, target (..., N, P) taken as (B, N, P): the eight masked sums added into the running (P, 8)
+// horizon table and, where given, the running (N, 8) node table; one launch, no host sync
+void metrics_update_masked(const Tensor& pred, const Tensor& target, int64_t mask_mode, double null_val,
+                           double mape_null, Tensor htable, const c10::optional<Tensor>& ntable) {
+  check_loss_pair(pred, target, "metrics_update_masked");
+  check_dev(htable, at::kDouble, "htable");
+  TORCH_CHECK(pred.dim() >= 2, "metrics_update_masked: pred must have a node and a horizon axis");
+  const int64_t P = pred.size(-1), N = pred.size(-2), B = P > 0 && N > 0 ? pred.numel() / (N * P) : 0;
+  // (a P outside [1, 256] is the library's DSTAGNN_E_SHAPE below)
+  TORCH_CHECK(P < 1 || P > 256 || (htable.dim() == 2 && htable.size(0) == P && htable.size(1) == 8),
+              "metrics_update_masked: htable must be (", P, ", 8), got ", htable.sizes());
+  TORCH_CHECK(htable.device() == pred.device(), "metrics_update_masked: htable on another device");
+  const bool nodes = ntable.has_value() && ntable->defined();
+  if (nodes) {
+    check_dev(*ntable, at::kDouble, "ntable");
+    TORCH_CHECK(ntable->dim() == 2 && ntable->size(0) == N && ntable->size(1) == 8,
+                "metrics_update_masked: ntable must be (", N, ", 8), got ", ntable->sizes());
+    TORCH_CHECK(ntable->device() == pred.device(), "metrics_update_masked: ntable on another device");
+  }
+  c10::DeviceGuard guard(pred.device());
+  const int Pi = (int)std::min<int64_t>(P, INT32_MAX);
+  const int64_t sb = std::max<int64_t>(dstagnn_metrics_masked_scratch_bytes(B, N, Pi), 16);
+  Tensor scratch = at::empty({sb / 8}, pred.options().dtype(at::kDouble));
+  check_rc(dstagnn_metrics_accumulate_masked(B, N, Pi, pred.data_ptr<float>(), target.data_ptr<float>(),
+                                             (int)mask_mode, (float)null_val, (float)mape_null,
+                                             htable.data_ptr<double>(), nodes ? ntable->data_ptr<double>() : nullptr,
+                                             scratch.data_ptr<double>(), (size_t)sb, stream_of(pred)),
+           "dstagnn_metrics_accumulate_masked");
+}
+
 // -------------------------------------------------------------------------------------
 // training windows from the raw series (windows.hip)
 // -------------------------------------------------------------------------------------
@@ -1271,6 +1302,8 @@ TORCH_LIBRARY(dstagnn, m) {
   m.def("loss_bwd(Tensor y, Tensor target, Tensor stat, Tensor? gout, int kind, float param, int mask_mode, "
         "float null_val) -> Tensor");
   m.def("metrics_update(Tensor pred, Tensor target, float null_val, Tensor(a!) table) -> ()");
+  m.def("metrics_update_masked(Tensor pred, Tensor target, int mask_mode, float null_val, float mape_null, "
+        "Tensor(a!) htable, Tensor(b!)? ntable) -> ()");
   m.def("window_gather(Tensor series, Tensor rel, Tensor labels, Tensor idx, Tensor mean, Tensor std, int P) "
         "-> (Tensor, Tensor)");
   m.def("window_stats(Tensor series, Tensor w, float wtotal) -> Tensor");
@@ -1321,6 +1354,7 @@ TORCH_LIBRARY_IMPL(dstagnn, CUDA, m) {
   m.impl("loss_fwd", loss_fwd);
   m.impl("loss_bwd", loss_bwd);
   m.impl("metrics_update", metrics_update);
+  m.impl("metrics_update_masked", metrics_update_masked);
   m.impl("window_gather", window_gather);
   m.impl("window_stats", window_stats);
   m.impl("window_stats_masked", window_stats_masked);

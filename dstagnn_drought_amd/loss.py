@@ -8,11 +8,14 @@ taken over the entries that remain.  One launch forward, one backward, no host s
 ``ForecastMetrics``: the per-horizon MAE / RMSE / MAPE list of
 ``predict_and_save_results_mstgcn`` (lib/utils1.py:418-431, lib/metrics.py:6-17) accumulated in
 a (P, 4) fp64 table on the device: one launch per batch, one device-to-host copy at the end.
+With a missing value and / or a node count: the masked (P, 8) and (N, 8) tables of
+``metrics_masked_kernel``, which also give the bias, the Nash-Sutcliffe skill and per-node scores.
 
 HIP tensors only: there is no CPU fallback.
 """
 import math
 
+import numpy as np
 import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
@@ -111,9 +114,25 @@ class ForecastMetrics:
     list ``predict_and_save_results_mstgcn`` returns, ``[MAE_0, RMSE_0, MAPE_0, ..., MAE_all,
     RMSE_all, MAPE_all]`` as Python floats: MAE_p = sum |e| / (S N), RMSE_p = sqrt(sum e^2 /
     (S N)), MAPE_p = 100 sum |e / t| / count over the targets != ``null_val`` (0 where there is
-    none, as masked_mape_np gives); the overall three from the column sums.  ``reset()`` clears."""
+    none, as masked_mape_np gives); the overall three from the column sums.  ``reset()`` clears.
 
-    def __init__(self, num_for_predict, null_val=0.0, device=None):
+    Series with gaps, per-node scores.  ``missing_value`` (a number, or NaN for the NaN targets:
+    ``mask_of``) leaves the targets equal to it out of every sum, as ``HipLoss(null_val=)`` leaves
+    them out of the loss; ``num_nodes`` adds ``node_table``, the same sums per node over all
+    samples and horizons.  Either one switches the object to ``metrics_masked_kernel``: ``table``
+    is then (P, 8) (count, sum e, sum |e|, sum e^2, sum |e / t| over t != ``null_val``, its count,
+    sum t, sum t^2 over the valid entries), ``node_table`` (num_nodes, 8) or None, the divisors of
+    ``compute()`` are the valid counts, and MAE / RMSE are NaN where a horizon has no valid entry
+    (MAPE stays 0.0 where its own count is 0).  With neither keyword the object is the (P, 4) one
+    above, untouched.
+
+    ``scores()``: a dict of float64 arrays of shape (P + 1,), the overall value last: ``count``,
+    ``mae``, ``rmse``, ``mape`` and, from the eight-column table, ``bias`` (sum e / count) and
+    ``nse`` (1 - sum e^2 / (sum t^2 - (sum t)^2 / count)); NaN wherever a divisor is 0.
+    ``node_scores()``: the same keys in shape (num_nodes,).  ``merge(other)`` adds another
+    object's tables; ``all_reduce()`` sums them over the ranks of the process group."""
+
+    def __init__(self, num_for_predict, null_val=0.0, device=None, *, missing_value=None, num_nodes=None):
         self.P = int(num_for_predict)
         if not 1 <= self.P <= 256:
             raise ValueError(f"ForecastMetrics: num_for_predict must be in [1, 256], got {num_for_predict!r}")
@@ -121,14 +140,26 @@ class ForecastMetrics:
         device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if device.type != "cuda":
             raise RuntimeError(HIP_ONLY)
-        self.table = torch.zeros(self.P, 4, dtype=torch.float64, device=device)
+        self.missing_value = None if missing_value is None else float(missing_value)
+        self.num_nodes = None if num_nodes is None else int(num_nodes)
+        if self.num_nodes is not None and self.num_nodes < 1:
+            raise ValueError(f"ForecastMetrics: num_nodes must be >= 1, got {num_nodes!r}")
+        self.masked = missing_value is not None or num_nodes is not None
+        self._mask = mask_of(missing_value)
+        self.table = torch.zeros(self.P, 8 if self.masked else 4, dtype=torch.float64, device=device)
+        self.node_table = (None if self.num_nodes is None else
+                           torch.zeros(self.num_nodes, 8, dtype=torch.float64, device=device))
         self.rows = 0
 
     def reset(self):
         self.table.zero_()
+        if self.node_table is not None:
+            self.node_table.zero_()
         self.rows = 0
 
     def update(self, pred, target):
+        if self.masked:
+            return self._update_masked(pred, target)
         if pred.shape != target.shape or pred.dim() < 1 or pred.shape[-1] != self.P:
             raise ValueError(f"ForecastMetrics: pred {tuple(pred.shape)} / target {tuple(target.shape)} must be "
                              f"equal (..., {self.P}) shapes")
@@ -140,7 +171,24 @@ class ForecastMetrics:
                                    self.table)
         self.rows += pred.numel() // self.P
 
+    def _update_masked(self, pred, target):
+        if pred.shape != target.shape or pred.dim() < 2 or pred.shape[-1] != self.P:
+            raise ValueError(f"ForecastMetrics: pred {tuple(pred.shape)} / target {tuple(target.shape)} must be "
+                             f"equal (..., N, {self.P}) shapes")
+        if self.num_nodes is not None and pred.shape[-2] != self.num_nodes:
+            raise ValueError(f"ForecastMetrics: pred {tuple(pred.shape)} has {pred.shape[-2]} nodes, "
+                             f"num_nodes is {self.num_nodes}")
+        if not (pred.is_cuda and target.is_cuda):
+            raise RuntimeError(HIP_ONLY)
+        if pred.numel() == 0:
+            return
+        _lib.load().metrics_update_masked(pred.detach().contiguous(), target.detach().contiguous(), self._mask[0],
+                                          self._mask[1], self.null_val, self.table, self.node_table)
+        self.rows += pred.numel() // self.P
+
     def compute(self):
+        if self.masked:
+            return self.list_of_table(self.table.cpu().numpy())
         tab = self.table.cpu().numpy()  # the one copy (and the one sync)
         rows = max(self.rows, 1)
 
@@ -152,3 +200,84 @@ class ForecastMetrics:
             out.extend(three(*tab[p], rows))
         out.extend(three(*tab.sum(0), rows * self.P))
         return out
+
+    @staticmethod
+    def list_of_table(table):
+        """``compute()``'s list from a (K, 8) table of the masked sums (a numpy array): three
+        entries per row, then the three of the column sums.  MAE / RMSE NaN at a zero count, MAPE
+        0.0 at a zero count of its own."""
+        tab = np.asarray(table, dtype=np.float64).reshape(-1, 8)
+
+        def three(r):
+            n = r[0]
+            return [float(r[2] / n) if n > 0 else float("nan"),
+                    float(math.sqrt(r[3] / n)) if n > 0 else float("nan"),
+                    float(100.0 * r[4] / r[5]) if r[5] > 0 else 0.0]
+        out = []
+        for r in tab:
+            out.extend(three(r))
+        out.extend(three(tab.sum(0)))
+        return out
+
+    @staticmethod
+    def scores_of_table(table, rows=None, overall=True):
+        """The scores of a table of sums (a numpy array), one entry per row and, with ``overall``,
+        one more from the column sums.  (K, 8): the masked sums; count, mae, rmse, mape, bias,
+        nse.  (K, 4): the unmasked object's columns with ``rows`` entries behind each row; count,
+        mae, rmse, mape.  NaN wherever a divisor is 0."""
+        tab = np.asarray(table, dtype=np.float64)
+        if tab.ndim != 2 or tab.shape[1] not in (4, 8):
+            raise ValueError(f"ForecastMetrics: a table of sums is (K, 4) or (K, 8), got {tab.shape}")
+        if overall:
+            tab = np.concatenate([tab, tab.sum(0, keepdims=True)], 0)
+
+        def over(a, b):
+            out = np.full(a.shape, np.nan)
+            np.divide(a, b, out=out, where=b != 0)
+            return out
+        if tab.shape[1] == 4:
+            count = np.full(tab.shape[0], float(rows or 0))
+            if overall:
+                count[-1] *= tab.shape[0] - 1
+            return {"count": count, "mae": over(tab[:, 0], count), "rmse": np.sqrt(over(tab[:, 1], count)),
+                    "mape": 100.0 * over(tab[:, 2], tab[:, 3])}
+        count = tab[:, 0].copy()
+        var = tab[:, 7] - over(tab[:, 6] * tab[:, 6], count)  # NaN at a zero count
+        return {"count": count, "mae": over(tab[:, 2], count), "rmse": np.sqrt(over(tab[:, 3], count)),
+                "mape": 100.0 * over(tab[:, 4], tab[:, 5]), "bias": over(tab[:, 1], count),
+                "nse": 1.0 - over(tab[:, 3], np.where(np.isnan(var), 0.0, var))}
+
+    def scores(self):
+        return self.scores_of_table(self.table.cpu().numpy(), self.rows)
+
+    def node_scores(self):
+        if self.node_table is None:
+            raise ValueError("ForecastMetrics: node_scores() needs num_nodes")
+        return self.scores_of_table(self.node_table.cpu().numpy(), overall=False)
+
+    def _config(self):
+        return (self.P, repr(self.null_val), self.masked, self._mask[0], repr(self._mask[1]), self.num_nodes)
+
+    def merge(self, other):
+        """Adds ``other``'s tables and row count into this object's (the sums are additive)."""
+        if not isinstance(other, ForecastMetrics) or other._config() != self._config():
+            raise ValueError("ForecastMetrics.merge: the other object has a different configuration")
+        self.table += other.table.to(self.table.device)
+        if self.node_table is not None:
+            self.node_table += other.node_table.to(self.node_table.device)
+        self.rows += other.rows
+        return self
+
+    def all_reduce(self):
+        """One SUM all-reduce per table (and one of the row count) when a process group is up;
+        nothing otherwise."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return self
+        dist.all_reduce(self.table)
+        if self.node_table is not None:
+            dist.all_reduce(self.node_table)
+        rows = torch.tensor([self.rows], dtype=torch.int64, device=self.table.device)
+        dist.all_reduce(rows)
+        self.rows = int(rows.item())
+        return self

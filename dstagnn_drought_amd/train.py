@@ -177,7 +177,18 @@ def evaluate_on_test_mstgcn(net, test_loader, test_target_tensor, sw, epoch, _me
     against its slice of `test_target_tensor` in loader order (loss.ForecastMetrics: one launch
     per batch) and only the (P, 4) table of sums comes back.  Also returns the list
     predict_and_save_results_mstgcn returns (the overall three last); the reference returns
-    None.  `_mean` / `_std` are unused, as in the reference."""
+    None.  `_mean` / `_std` are unused, as in the reference.  Every target is scored: for a series
+    with gaps, or per-node scores, evaluate_on_test_masked."""
+    return evaluate_on_test_masked(net, test_loader, test_target_tensor, sw, epoch)
+
+
+def evaluate_on_test_masked(net, test_loader, test_target_tensor, sw, epoch, *, missing_value=None, per_node=False):
+    """evaluate_on_test_mstgcn's loop, printed lines and `sw` scalars with two options (that
+    function keeps the reference's parameter list).  missing_value (a number, or NaN for the NaN
+    targets) leaves those targets out of every score, as the masked criterion leaves them out of
+    the loss.  per_node: returns (list, ForecastMetrics.node_scores()), the per-node count / mae /
+    rmse / mape / bias / nse arrays from the (N, 8) device table; no prediction is copied to the
+    host.  With neither, the unmasked (P, 4) object of evaluate_on_test_mstgcn."""
     from .loss import ForecastMetrics
     net.train(False)
     with torch.no_grad():
@@ -186,7 +197,8 @@ def evaluate_on_test_mstgcn(net, test_loader, test_target_tensor, sw, epoch, _me
         for batch_index, (encoder_inputs, labels) in enumerate(test_loader):
             outputs = net(encoder_inputs)
             if metrics is None:
-                metrics = ForecastMetrics(outputs.shape[-1], 0.0, outputs.device)
+                metrics = ForecastMetrics(outputs.shape[-1], 0.0, outputs.device, missing_value=missing_value,
+                                          num_nodes=outputs.shape[-2] if per_node else None)
                 test_target_tensor = test_target_tensor.to(outputs.device, torch.float32)
             metrics.update(outputs, test_target_tensor[at:at + outputs.shape[0]])
             at += outputs.shape[0]
@@ -205,26 +217,60 @@ def evaluate_on_test_mstgcn(net, test_loader, test_target_tensor, sw, epoch, _me
                 sw.add_scalar('MAE_%s_points' % (i), mae, epoch)
                 sw.add_scalar('RMSE_%s_points' % (i), rmse, epoch)
                 sw.add_scalar('MAPE_%s_points' % (i), mape, epoch)
-    return excel_list
+    return (excel_list, metrics.node_scores()) if per_node else excel_list
+
+
+def score_batches(net, x, y, batch_size, missing_value=None, per_node=False):
+    """The test-set scores of `net` over (x, y), batched and sharded as eval_batches does it
+    (batches of `batch_size` cut with _cut, round-robin over the ranks), accumulated on the device
+    and summed over the ranks at the end.  Returns the loss.ForecastMetrics: masked by
+    missing_value when there is one, with the node table when per_node; with neither, the
+    unmasked (P, 4) object.  x, y: tensors, or the arrays of a windows.WindowedSeries split."""
+    from .loss import ForecastMetrics
+    rank, world = _world()
+    metrics = ForecastMetrics(y.shape[-1], 0.0, x.device, missing_value=missing_value,
+                              num_nodes=y.shape[-2] if per_node else None)
+    with torch.no_grad():
+        for b in list(range(0, x.shape[0], batch_size))[rank::world]:
+            xb, yb = _cut(x, y, b, b + batch_size)
+            metrics.update(net(xb), yb)
+    return metrics.all_reduce()
 
 
 def predict_and_save_results_mstgcn(net, data_loader, data_target_tensor, global_step, _mean, _std, params_path,
-                                    type):
+                                    type, missing_value=None):
     """lib/utils1.py:441-510: predictions over `data_loader`, saved with the de-normalised
     inputs as ``output_epoch_{step}_{type}.npz`` (keys input, prediction,
-    data_target_tensor); returns the per-horizon [MAE, RMSE, MAPE] list + the overall three."""
-    from sklearn.metrics import mean_absolute_error, mean_squared_error
+    data_target_tensor); returns the per-horizon [MAE, RMSE, MAPE] list + the overall three.
+    missing_value (a number, or NaN for the NaN targets): the targets equal to it are left out of
+    the list, which then comes from the masked loss.ForecastMetrics on the device, each batch
+    scored against its slice of the targets in loader order (sklearn raises on a NaN target and
+    scores a sentinel as data); the file is saved as before."""
     net.train(False)
     with torch.no_grad():
+        metrics, at = None, 0
+        if missing_value is not None:
+            from .loss import ForecastMetrics
+            metrics = ForecastMetrics(data_target_tensor.shape[-1], 0.0, next(net.parameters()).device,
+                                      missing_value=missing_value)
+            target_dev = data_target_tensor.to(metrics.table.device, torch.float32)
         data_target_tensor = data_target_tensor.cpu().numpy()
         prediction, inputs = [], []
         for encoder_inputs, labels in data_loader:
             inputs.append(encoder_inputs[:, :, 0:1].cpu().numpy())
-            prediction.append(net(encoder_inputs).detach().cpu().numpy())
+            outputs = net(encoder_inputs)
+            if metrics is not None:
+                metrics.update(outputs, target_dev[at:at + outputs.shape[0]])
+                at += outputs.shape[0]
+            prediction.append(outputs.detach().cpu().numpy())
         inputs = data_io.re_normalization(np.concatenate(inputs, 0), _mean, _std)
         prediction = np.concatenate(prediction, 0)
         np.savez(os.path.join(params_path, 'output_epoch_%s_%s' % (global_step, type)), input=inputs,
                  prediction=prediction, data_target_tensor=data_target_tensor)
+        if metrics is not None:
+            assert data_target_tensor.shape[0] == at
+            return metrics.compute()
+        from sklearn.metrics import mean_absolute_error, mean_squared_error
         excel_list = []
         for i in range(prediction.shape[2]):
             assert data_target_tensor.shape[0] == prediction.shape[0]
@@ -520,6 +566,12 @@ def input_options(tc):
     return fill, None if gap is None or gap.strip().lower() in ('', 'none') else int(gap)
 
 
+def scoring_options(tc):
+    """Optional [Training] keys of a configuration (a ConfigParser section): ``test_metrics`` and
+    ``node_scores`` -> (bool, bool).  Absent: (False, False), today's behaviour (a test loss only)."""
+    return tc.getboolean('test_metrics', fallback=False), tc.getboolean('node_scores', fallback=False)
+
+
 def make_criterion(name=None, missing_value=None, smooth_l1_beta=1.0, huber_delta=1.0):
     """The driver's criterion.  With no name and no missing value: ``nn.SmoothL1Loss()``
     (train_DSTAGNN_my.py:132), the object every run without the keys of loss_options() has
@@ -635,7 +687,7 @@ def load_best(net, path):
 
 def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches=None, root='myexperiments',
         log=print, max_grad_norm=None, weight_decay=None, loss=None, missing_value=None, stream_windows=None,
-        input_fill=None, input_max_gap=None):
+        input_fill=None, input_max_gap=None, test_metrics=None, node_scores=None):
     """Whole script: data, graphs, model, training, best-checkpoint test loss.  The optional
     [Training] keys of training_options() switch clipping / weight decay on; max_grad_norm /
     weight_decay given here override them.  loss / missing_value override the keys of
@@ -651,7 +703,14 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
     inputs equal to the missing value (the criterion's) are imputed inside the gather launch and
     the z-score statistics are those of the observed values, always computed on the device (a
     prepared file's would be NaN or polluted by the sentinel).  Needs a missing value and
-    stream_windows (the materialised path has no imputation): ValueError otherwise."""
+    stream_windows (the materialised path has no imputation): ValueError otherwise.
+    test_metrics / node_scores (None: the [Training] keys of scoring_options(), off when absent):
+    after the final test loss the test split is scored with the best checkpoint (score_batches:
+    MAE / RMSE / MAPE / bias / NSE per horizon and overall, masked by the run's missing value when
+    there is one; with node_scores also per node, which implies test_metrics).  Rank 0 logs one
+    line per horizon and one overall and writes ``test_metrics.json`` (and
+    ``test_node_scores.npz``) into the params path; the returned dict gains ``test_metrics`` (the
+    list of predict_and_save_results_mstgcn), ``test_scores`` and ``test_node_scores``."""
     config = configparser.ConfigParser()
     config.read(config_path)
     dc, tc = config['Data'], config['Training']
@@ -662,6 +721,9 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
         stream_windows = tc.getboolean('stream_windows', fallback=False)
     cfg_loss, cfg_missing, beta, delta = loss_options(tc)
     missing_value = cfg_missing if missing_value is None else missing_value
+    cfg_scores, cfg_nodes = scoring_options(tc)
+    node_scores = cfg_nodes if node_scores is None else bool(node_scores)
+    test_metrics = (cfg_scores if test_metrics is None else bool(test_metrics)) or node_scores
     cfg_fill, cfg_gap = input_options(tc)
     input_fill = cfg_fill if input_fill is None else (None if str(input_fill).lower() == 'none' else input_fill)
     input_max_gap = cfg_gap if input_max_gap is None else input_max_gap
@@ -714,8 +776,31 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
     test_loss = eval_batches(net, test_x, test_y, bs, criterion)
     if rank == 0:
         log(f'Final Test Loss: {test_loss:.4f}')
-    return {"best_epoch": best_epoch, "best_val": best_val, "test_loss": test_loss, "history": history,
-            "params_path": params_path, "net": net}
+    result = {"best_epoch": best_epoch, "best_val": best_val, "test_loss": test_loss, "history": history,
+              "params_path": params_path, "net": net}
+    if test_metrics:
+        result.update(_score_test_split(net, test_x, test_y, bs, missing_value, node_scores, params_path, log))
+    return result
+
+
+def _score_test_split(net, test_x, test_y, bs, missing_value, per_node, params_path, log):
+    """run()'s test-set scores: score_batches, rank 0's log lines and files, the result keys."""
+    import json
+    rank, _ = _world()
+    metrics = score_batches(net, test_x, test_y, bs, missing_value, per_node)
+    excel_list, scores = metrics.compute(), metrics.scores()
+    out = {"test_metrics": excel_list, "test_scores": scores}
+    if per_node:
+        out["test_node_scores"] = metrics.node_scores()
+    if rank == 0:
+        for i in range(metrics.P + 1):
+            log('Test %s: ' % ('overall' if i == metrics.P else 'horizon %d' % i)
+                + ' '.join('%s %.4f' % (k, v[i]) for k, v in scores.items()))
+        with open(os.path.join(params_path, 'test_metrics.json'), 'w') as f:
+            json.dump(dict({k: v.tolist() for k, v in scores.items()}, list=excel_list), f, indent=1)
+        if per_node:
+            np.savez(os.path.join(params_path, 'test_node_scores.npz'), **out["test_node_scores"])
+    return out
 
 
 def _windowed_series(dc, tc, device, missing_value=None, fill=None, max_gap=None):
@@ -766,6 +851,13 @@ def main(argv=None):
     ap.add_argument("--input-max-gap", type=int, default=None,
                     help="the furthest, in time steps, --input-fill ffill carries a value (overrides [Training] "
                          "input_max_gap; default: any distance)")
+    ap.add_argument("--test-metrics", action="store_true", default=None,
+                    help="after the final test loss, score the test split with the best checkpoint: MAE / RMSE / "
+                         "MAPE / bias / NSE per horizon and overall, masked by the missing value when there is one "
+                         "(overrides [Training] test_metrics)")
+    ap.add_argument("--node-scores", action="store_true", default=None,
+                    help="also score every node over all samples and horizons (test_node_scores.npz; implies "
+                         "--test-metrics; overrides [Training] node_scores)")
     a = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
@@ -777,7 +869,8 @@ def main(argv=None):
         run(a.config, epochs=a.epochs, double_step=not a.no_double_step, dropout=a.dropout,
             max_batches=a.max_batches, root=a.out_root, max_grad_norm=a.max_grad_norm,
             weight_decay=a.weight_decay, loss=a.loss, missing_value=a.missing_value,
-            stream_windows=a.stream_windows, input_fill=a.input_fill, input_max_gap=a.input_max_gap)
+            stream_windows=a.stream_windows, input_fill=a.input_fill, input_max_gap=a.input_max_gap,
+            test_metrics=a.test_metrics, node_scores=a.node_scores)
     finally:
         if world > 1:
             dist.destroy_process_group()

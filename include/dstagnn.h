@@ -384,6 +384,22 @@ int dstagnn_grad_scale(const dstagnn_adam_seg* segs, const int64_t* chunks, int 
  * RMSE_p = sqrt(table[p][1] / rows), MAPE_p = 100 table[p][2] / table[p][3] (0 where the count
  * is 0).  1 <= P <= 256 and rows * P < 2^31, else DSTAGNN_E_SHAPE.  scratch:
  * dstagnn_metrics_scratch_bytes(rows, P) bytes.
+ *
+ * dstagnn_metrics_accumulate_masked: pred, target (B, N, P) -> htable (P, 8) and, unless NULL,
+ * ntable (N, 8) doubles on the device, RUNNING tables the call adds to (zero them to start): per
+ * horizon p, and per node n over all samples and horizons, eight sums over the VALID entries (the
+ * criterion's rule above under mask_mode / null_val; selected out, never multiplied by zero):
+ *   0 count   1 sum e   2 sum |e|   3 sum e^2   4 sum |e / t| over t != mape_null   5 its count
+ *   6 sum t   7 sum t^2
+ * with e = pred - t, e * e and e / t in fp32 as dstagnn_metrics_accumulate forms them, t and t * t
+ * as doubles (exact), every add in fp64 in a fixed order (no atomics on floats: the same bits on
+ * every call).  A NaN target under DSTAGNN_MASK_NAN leaves every sum finite; a NaN prediction at a
+ * valid entry makes the sums NaN.  MAE = [2] / [0], RMSE = sqrt([3] / [0]), bias = [1] / [0],
+ * MAPE = 100 [4] / [5], NSE = 1 - [3] / ([7] - [6]^2 / [0]).  One launch of ceil(N / (256 / P))
+ * workgroups.  1 <= P <= 256, B, N >= 1 and B * N * P < 2^31, else DSTAGNN_E_SHAPE; a null pred /
+ * target / htable / scratch or an unknown mask mode -> DSTAGNN_E_ARG; scratch smaller than
+ * dstagnn_metrics_masked_scratch_bytes(B, N, P) bytes (0 for a shape it rejects) ->
+ * DSTAGNN_E_SPACE.  All of it is checked before anything touches the device.
  * ------------------------------------------------------------------------------------- */
 enum { DSTAGNN_LOSS_SMOOTH_L1 = 0, DSTAGNN_LOSS_HUBER = 1, DSTAGNN_LOSS_MAE = 2, DSTAGNN_LOSS_MSE = 3 };
 enum { DSTAGNN_MASK_NONE = 0, DSTAGNN_MASK_NEQ = 1, DSTAGNN_MASK_NAN = 2 };
@@ -402,6 +418,11 @@ int dstagnn_loss_backward(const dstagnn_loss_cfg* cfg, int64_t n, const float* y
 int64_t dstagnn_metrics_scratch_bytes(int64_t rows, int P);
 int dstagnn_metrics_accumulate(int64_t rows, int P, const float* pred, const float* target, float null_val,
                                double* table, void* scratch, size_t scratch_bytes, dstagnn_stream_t stream);
+int64_t dstagnn_metrics_masked_scratch_bytes(int64_t B, int64_t N, int P);
+int dstagnn_metrics_accumulate_masked(int64_t B, int64_t N, int P, const float* pred, const float* target,
+                                      int mask_mode, float null_val, float mape_null, double* htable,
+                                      double* ntable /* may be NULL */, void* scratch, size_t scratch_bytes,
+                                      dstagnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Training windows cut from the raw series on the device (windows.hip): what prepareData.py

@@ -14,6 +14,15 @@
 
     python tools/bench_loss.py --out profiles/loss_ab.json
 
+  (3) --mode metrics: a test-set scoring pass (reset, one ForecastMetrics.update per batch over
+      --batches (64) batches of head outputs already on the device, compute()) on the three shapes,
+      for the unmasked object (metrics_accum_kernel, the baseline), the masked one
+      (metrics_masked_kernel, NaN marker on 30 % of the targets) and the masked one with the node
+      table: windows of --passes (300) passes on the host clock (a pass ends in compute()'s
+      synchronising copy), --rounds windows of each variant, alternating; median and spread.
+
+    python tools/bench_loss.py --mode metrics --out profiles/metrics_masked_ab.json
+
 The JSON carries the library stamp (dstagnn_drought_amd._lib.build_stamp).  There is no fallback:
 without a HIP device the tool fails."""
 import argparse
@@ -112,14 +121,85 @@ def time_scoring(torch, dev, batches, rounds):
             "worst_relative_difference_of_the_lists": worst}
 
 
+def time_metrics(torch, dev, shape, batches, passes, rounds):
+    from dstagnn_drought_amd import ForecastMetrics
+    B, N, P = shape
+    gen = torch.Generator(device=dev).manual_seed(7)
+    data = []
+    for _ in range(batches):
+        t = 3.0 * torch.randn(shape, device=dev, generator=gen)
+        y = t + torch.randn(shape, device=dev, generator=gen)
+        t[torch.rand(shape, device=dev, generator=gen) < 0.3] = float("nan")
+        data.append((y, t))
+    objs = {"unmasked": ForecastMetrics(P, 0.0, dev),
+            "masked": ForecastMetrics(P, 0.0, dev, missing_value=float("nan")),
+            "masked_nodes": ForecastMetrics(P, 0.0, dev, missing_value=float("nan"), num_nodes=N)}
+
+    def one_pass(m):
+        m.reset()
+        for y, t in data:
+            m.update(y, t)
+        return m.compute()
+
+    for m in objs.values():
+        for _ in range(3):
+            one_pass(m)
+    torch.cuda.synchronize()
+    runs = {k: [] for k in objs}
+    for _ in range(rounds):
+        for k, m in objs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(passes):
+                one_pass(m)
+            runs[k].append(round((time.perf_counter() - t0) / passes * 1e3, 4))
+    med = {k: statistics.median(r) for k, r in runs.items()}
+    return {"shape": list(shape), "batches": batches, "passes_per_window": passes, "ms_per_pass_runs": runs,
+            "median_ms": med, "us_per_update": {k: round(v / batches * 1e3, 3) for k, v in med.items()},
+            "over_unmasked": {k: round(med[k] / med["unmasked"], 4) for k in ("masked", "masked_nodes")},
+            "spread": {k: round((max(r) - min(r)) / med[k], 4) for k, r in runs.items()}}
+
+
+def main_metrics(a):
+    import torch
+    from dstagnn_drought_amd import _lib
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_loss.py measures on the GPU only: no HIP device")
+    dev = torch.device("cuda:0")
+    rec = {"what": f"test-set scoring pass over {a.batches} batches of head outputs on the device (reset, one update "
+                   f"per batch, compute()), ms per pass on the host clock, {a.rounds} alternating windows x "
+                   f"{a.passes} passes (tools/bench_loss.py --mode metrics)",
+           "variants": {"unmasked": "ForecastMetrics(P) (metrics_accum_kernel)",
+                        "masked": "ForecastMetrics(P, missing_value=nan) (metrics_masked_kernel)",
+                        "masked_nodes": "ForecastMetrics(P, missing_value=nan, num_nodes=N)"},
+           "stamp": _lib.build_stamp(),
+           "metrics": {name: time_metrics(torch, dev, shape, a.batches, a.passes, a.rounds)
+                       for name, shape in SHAPES.items()}}
+    print(json.dumps(rec))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(rec, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=("loss", "metrics"), default="loss",
+                    help="loss: (1) and (2) above; metrics: (3), the masked scoring pass")
+    ap.add_argument("--passes", type=int, default=300, help="--mode metrics: passes per window")
     ap.add_argument("--iters", type=int, default=2000, help="iterations per window (>= 200)")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=500)
     ap.add_argument("--batches", type=int, default=64)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "loss_ab.json"))
+    ap.add_argument("--out", default=None,
+                    help="default: profiles/loss_ab.json (profiles/metrics_masked_ab.json with --mode metrics)")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "metrics_masked_ab.json" if a.mode == "metrics" else "loss_ab.json")
+    if a.mode == "metrics":
+        if a.passes < 1 or a.rounds < 3:
+            ap.error("--mode metrics needs --passes >= 1 and --rounds >= 3")
+        return main_metrics(a)
     if a.iters < 200:
         ap.error("--iters must be at least 200")
     import torch
