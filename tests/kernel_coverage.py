@@ -73,15 +73,319 @@ def flash_small_fwd_lds_bytes(N):
     return ((N + 31) >> 5) * 32 * 33 * 4
 
 
-def kernels(N, T, K, F, C, B, sparse=True, flash=True, d_k=32):
+def cdiv(a, b):
+    return -(-a // b)
+
+
+# ---------------------------------------------------------------------------------------
+# LayerNorm (ops.hip op_ln_fwd / op_ln_bwd) and the block's three call sites (block.hip)
+# ---------------------------------------------------------------------------------------
+LN_MAX_L = 4096  # ops.hip op_ln_fwd / op_ln_bwd: "ln_fwd: row too long" above
+LN_V4_L = (256, 512, 1024)  # ops.hip ln_fwd_v4_ok / ln_bwd_v4_ok
+
+
+def ln_bwd_part_blocks(R):
+    """ops.hpp ln_bwd_part_blocks (kLnRowsPerWave = 1: four rows a workgroup)."""
+    return cdiv(R, 4)
+
+
+def ln_bwd_partials_ok(L):
+    """ops.hpp ln_bwd_partials_ok."""
+    return L <= 1024
+
+
+def _ln_shape(L, v4):
+    """The template both directions pick for a row of L floats (ops.hip op_ln_fwd:1097-1123,
+    op_ln_bwd:1133-1158): ("v4", L / 256), ("vpt", VPT), ("wg", 8 | 16) or None (refused)."""
+    if v4 and L in LN_V4_L:
+        return ("v4", L // 256)
+    vpt = cdiv(L, 64)
+    for v in (1, 2, 4, 8, 16):
+        if vpt <= v:
+            return ("vpt", v)
+    if L <= LN_MAX_L:
+        return ("wg", 8 if L <= 2048 else 16)  # fwd: cdiv(L, 256) <= 8; bwd: L <= 2048 — the same split
+    return None
+
+
+def ln_kernels(L, v4_fwd=True, v4_bwd=True, part=True):
+    """(forward, backward) templates of one LayerNorm over rows of L floats, default DSTAGNN_LN_V4.
+
+    v4_fwd / v4_bwd: the float4 kernels' preconditions other than L in {256, 512, 1024} hold
+    (ln_fwd_v4_ok / ln_bwd_v4_ok: unit element strides, row maps whose strides are multiples of 4
+    floats, 16-B aligned pointers).  In the block they hold by construction wherever L is one of the
+    three lengths: every buffer is an Arena::take slot (256-B aligned) or a parameter tensor, a
+    partial slab's second half starts pb * L floats in (L % 4 == 0), and the row maps are idx1(L)
+    or idx2(FT, BN, N) with BN = B N a multiple of 4 when N is — except the first block's EmbedT
+    FORWARD, whose source 0 reads x (B,N,1,T) with element stride es = T (>= 7), so that launch
+    never takes v4 (its backward reads dE / writes du_et with unit stride and does).
+
+    part: the backward writes per-workgroup partial slabs (gpart / bpart) rather than the (R, L)
+    contribution tensors.  The slabs need ln_bwd_partials_ok(L); the v4 backward exists only in
+    the slab form.  Backward third field: "part" | "contrib".  Refused: ("refused", ())."""
+    f, b = _ln_shape(L, v4_fwd), None
+    if part and not ln_bwd_partials_ok(L):
+        raise ValueError("partial slabs need L <= 1024")  # op_ln_bwd:1131
+    if part:
+        b = _ln_shape(L, v4_bwd)  # L <= 1024: v4 or vpt, never wg
+    else:
+        b = _ln_shape(L, False)   # op_ln_bwd:1148-1158 has no float4 contribution kernel
+    fwd = ("refused", ()) if f is None else f
+    bwd = ("refused", ()) if b is None else b + ("part" if part else "contrib",)
+    return fwd, bwd
+
+
+def ln_sites(N, T, F, D, B, fused_fwd, fused_bwd, train=False):
+    """The block's LayerNorm launches as (family, args) with family "ln_fwd/<site>" /
+    "ln_bwd/<site>" (block.hip stage_tat:588-639, stage_sat:708-721, backward :1229-1245,
+    embedT_backward:1336-1354, stage_tat:1359-1371):
+      embedT  first block only (F == 1), rows B T of N floats; it runs whether or not the fused
+              TAt kernels do.  Slabs iff ln_bwd_partials_ok(N) and 2 pb <= B T.
+      tat     rows B F T of N floats, per direction only where the fused kernel is refused
+              (tat_fused_*_ok).  Slabs iff tat_part(): ln_bwd_partials_ok(N) and 2 pb <= B F T.
+      embedS  rows B N of D floats; slabs iff ln_bwd_partials_ok(D) (whatever the row count).
+              train: dropout in the forward's epilogue / on the backward's dy, recorded as
+              ("ln_drop", (kernel kind,)).  The pre_conv bias gradient rides on the slab launch
+              (preconv_bias_part: ln_bwd_partials_ok(D) and 2 pb <= B N) or takes its own column sum.
+    A forward over L > 4096 is refused before any backward is planned."""
+    out = set()
+    first = F == 1
+
+    def add(site, L, R, v4_fwd, part, fwd=True, bwd=True):
+        f, b = ln_kernels(L, v4_fwd=v4_fwd, part=part)
+        if fwd:
+            out.add(("ln_fwd/" + site, f))
+        if bwd and f[0] != "refused":
+            out.add(("ln_bwd/" + site, b))
+        return f
+
+    if first:
+        R = B * T
+        add("embedT", N, R, False, ln_bwd_partials_ok(N) and 2 * ln_bwd_part_blocks(R) <= R)
+    R = B * F * T
+    add("tat", N, R, True, ln_bwd_partials_ok(N) and 2 * ln_bwd_part_blocks(R) <= R,
+        fwd=not fused_fwd, bwd=not fused_bwd)
+    f = add("embedS", D, B * N, True, ln_bwd_partials_ok(D))
+    if f[0] != "refused":
+        if train:
+            out.add(("ln_drop", (f[0],)))
+        xpart = ln_bwd_partials_ok(D) and 2 * ln_bwd_part_blocks(B * N) <= B * N
+        out.add(("preconv_bias", ("xpart" if xpart else "colsum",)))
+    return out
+
+
+# ---------------------------------------------------------------------------------------
+# temporal attention (tat_fused.hip gates; tat.hip unfused paths)
+# ---------------------------------------------------------------------------------------
+TAT_LDS = 64 << 10  # tat.hip tat_path: a VALU problem's LDS bound
+TAT_CW = 16         # tat.hip kTatCW
+
+
+def tat_fused_fwd_ok(N, T, h, dk, dv):
+    """tat_fused.hip tat_fused_fwd_ok (kTfH = 3, kTfD = 32, kTfNmax = 320), default knobs."""
+    return h == 3 and dk == 32 and dv == 32 and 1 <= N <= 320 and T in (8, 12, 16)
+
+
+def tat_fused_bwd_ok(N, T, h, dk, dv, F, res_kind):
+    """tat_fused.hip tat_fused_bwd_ok: broadcast res_att (res_kind 1) needs whole 48-row
+    workgroups per sample."""
+    return tat_fused_fwd_ok(N, T, h, dk, dv) and (res_kind != 1 or (F * T) % 48 == 0)
+
+
+def tat_mfma_ok(T, dk, dv):
+    """tat.hip tat_mfma_ok (kTatD = 32), default knobs; its operands are Arena slots or whole
+    tensors, so the 16-B alignment holds."""
+    return dk == 32 and dv == 32 and T % 4 == 0 and 4 <= T <= 16
+
+
+def tat_valu_fwd_floats(T, dk, dv):
+    """tat.hip tat_valu_fwd_floats."""
+    return 2 * T * (dk + 1) + T * (dv + 1) + T * T
+
+
+def tat_valu_bwd_floats(T, dk, dv):
+    """tat.hip tat_valu_bwd_floats."""
+    return 2 * T * (dk + 1) + 2 * T * (dv + 1) + 2 * T * T
+
+
+def tat_path(mfma, T, valu_floats):
+    """tat.hip tat_path (kTatW = 4 problems per G = 64 workgroup)."""
+    if mfma:
+        return "mfma"
+    if T <= 16 and 4 * valu_floats * 4 <= TAT_LDS:
+        return "valu64"
+    return "cols" if valu_floats * 4 > TAT_LDS else "valu256"
+
+
+def tat_kernels(T, h, dk, dv, F, res_kind, fused_fwd=False, fused_bwd=False):
+    """The unfused temporal-attention launches (tat.hip op_tat_fwd / op_tat_bwd), per direction
+    only where the fused kernel is refused.  ("tat_fwd" | "tat_bwd", args) with args ("mfma", T),
+    ("valu64",), ("valu256",) or ("cols", "full" | "partial") — partial: T % 16 != 0, the last
+    column chunk has cw < 16 (and the batched GEMM behind it an M = T off its tile).  With a
+    broadcast res_att (res_kind 1) the backward's sum over f is ("tat_dres", ("fold",)) — in-kernel,
+    the matrix-core path with F % 4 == 0 (op_tat_bwd:610) — or ("tat_dres", ("sum_middle", path));
+    with a full one (res_kind 2) ("tat_dres", ("full", path)).  ("tat_res", (forward path, "none" |
+    "bcast" | "full")) is the residual tile the forward adds to the scores; ("tat_edge", (direction,
+    "last_valu256" | "first_cols")) marks a T on either side of that direction's hand-over from
+    the G = 256 kernel (largest LDS image) to the column chunks."""
+    out = set()
+
+    def args(path):
+        return ("mfma", T) if path == "mfma" else ("cols", "partial" if T % TAT_CW else "full") \
+            if path == "cols" else (path,)
+
+    def edge(d, floats):  # T sits on the G = 256 | column-chunk hand-over of direction d
+        at = lambda t: tat_path(tat_mfma_ok(t, dk, dv), t, floats(t, dk, dv))  # noqa: E731
+        if at(T) == "valu256" and at(T + 1) == "cols":
+            out.add(("tat_edge", (d, "last_valu256")))
+        if at(T) == "cols" and at(T - 1) == "valu256":
+            out.add(("tat_edge", (d, "first_cols")))
+
+    mf = tat_mfma_ok(T, dk, dv)
+    mode = ("none", "bcast", "full")[res_kind]
+    if not fused_fwd:
+        path = tat_path(mf, T, tat_valu_fwd_floats(T, dk, dv))
+        out.add(("tat_fwd", args(path)))
+        out.add(("tat_res", (path, mode)))  # tat_res_tile: no residual tile, one per (b, head), one per problem
+        edge("fwd", tat_valu_fwd_floats)
+    if not fused_bwd:
+        path = tat_path(mf, T, tat_valu_bwd_floats(T, dk, dv))
+        out.add(("tat_bwd", args(path)))
+        edge("bwd", tat_valu_bwd_floats)
+        if res_kind == 1:
+            out.add(("tat_dres", ("fold",) if path == "mfma" and F % 4 == 0 else ("sum_middle", path)))
+        elif res_kind == 2:  # block.hip stage_tat:1382: dS is written straight into d res_att
+            out.add(("tat_dres", ("full", path)))
+    return out
+
+
+# ---------------------------------------------------------------------------------------
+# GTU stage (gtu_fused.hip gates; gtu_tail.hip; block.hip stage_tail)
+# ---------------------------------------------------------------------------------------
+TAIL_NT = 64          # gtu_tail.hip kNT
+TAIL_SPLIT_T = 20     # gtu_tail.hip kTailSplitT
+TAIL_SPLIT_LDS = 32 << 10  # gtu_tail.hip tail_split_fwd / tail_split_bwd
+
+
+def tail_fwd_lds_bytes(C, T, stage_w=True, has_g=True, nt=TAIL_NT):
+    """gtu_tail.hip TailFwdLds(...).total floats, as bytes (fwd_lds)."""
+    S = 3 * T - 12
+    SP, CP, P = S + 1, C + 1, (nt // T if T < nt else 1)
+    total = (C * SP if has_g else 0) + C * T + T * CP + max(P * T, nt) + 2 * T + (T * SP if stage_w else 0)
+    return 4 * total
+
+
+def tail_bwd_lds_bytes(C, T, stage_w=True, has_g=True, nt=TAIL_NT):
+    """gtu_tail.hip TailBwdLds(...).total floats, as bytes (bwd_lds)."""
+    S = 3 * T - 12
+    SP, CP, P = S + 1, C + 1, (nt // T if T < nt else 1)
+    shared = max(C * SP if has_g else 0, T * CP, 2 * max(P * T, nt))
+    return 4 * (3 * C * T + shared + 2 * T + (T * S if stage_w else 0))
+
+
+def tail_ct24(C, T):
+    """gtu_tail.hip tail_ct24, default DSTAGNN_TAIL_CT24."""
+    return C == 32 and T == 24
+
+
+def tail_split_fwd(C, T):
+    """gtu_tail.hip tail_split_fwd."""
+    return not tail_ct24(C, T) and (tail_fwd_lds_bytes(C, T) > TAIL_SPLIT_LDS or T >= TAIL_SPLIT_T)
+
+
+def tail_split_bwd(C, T):
+    """gtu_tail.hip tail_split_bwd."""
+    return not tail_ct24(C, T) and (tail_bwd_lds_bytes(C, T) > TAIL_SPLIT_LDS or T >= TAIL_SPLIT_T)
+
+
+def gtu_fused_ok(C, T):
+    """gtu_fused.hip gtu_fused_fwd_ok / gtu_fused_bwd_ok (kGC = 32, kGT = 12), default knobs."""
+    return C == 32 and T == 12
+
+
+def gtu_kernels(C, T, first=False):
+    """The GTU stage's launches (block.hip stage_tail forward :769-816, backward :960-1019).
+    Fused (C = 32, T = 12): ("gtu_fused_fwd", ()), ("gtu_fused_bwd", ()).  Otherwise
+    ("gtu_tail_fwd" | "gtu_tail_bwd", (kind, cc)) with kind "split" (gates | GEMM | tail), "ct24"
+    (tail_ct: C = 32 at T = 24; its T = 12 twin runs only with the fused kernels switched off) or
+    "generic" (gtu_tail_*_kernel<true>), the two directions decided independently, and cc the
+    channel class "c32" | "c16" | "cx" (any other C: the runtime-C kernels off the two widths the
+    Chebyshev stage's aggregate-first kernels admit), then "first" | "inner" (a.first: the
+    residual_conv branch and its rpart / dpart sums); ("gtu_tail_pair", (fwd kind, bwd kind));
+    and the input gradient ("gtu_dx", ("tconv",)) (gtu_tconv_ok: C = 32) or ("gtu_dx", ("kcat",))."""
+    if gtu_fused_ok(C, T):
+        return {("gtu_fused_fwd", ()), ("gtu_fused_bwd", ())}
+
+    def kind(split):
+        return "split" if split else "ct24" if tail_ct24(C, T) else "generic"
+    f, b = kind(tail_split_fwd(C, T)), kind(tail_split_bwd(C, T))
+    cc = "c32" if C == 32 else "c16" if C == 16 else "cx"
+    fi = "first" if first else "inner"
+    return {("gtu_tail_fwd", (f, cc, fi)), ("gtu_tail_bwd", (b, cc, fi)), ("gtu_tail_pair", (f, b)),
+            ("gtu_dx", ("tconv" if C == 32 else "kcat",))}
+
+
+# ---------------------------------------------------------------------------------------
+# Theta-first sparse Chebyshev (cheb_sparse.hip), where cheb_agg_ok refuses
+# ---------------------------------------------------------------------------------------
+CHEB_CHUNK = 1024  # cheb_sparse.hip kChunk = 64 * kMaxNQ
+
+
+def theta_first_kernels(C, T):
+    """cheb_sparse.hip DS_NQ_DISPATCH over rows of C T floats, the same template for
+    cheb_spmm_fwd / cheb_sddmm_bwd / cheb_spmm_t_bwd: ("theta_first", (NQ,)), and
+    ("theta_first_chunked", ()) when a row is walked in more than one 1024-float chunk."""
+    nq = cdiv(min(C * T, CHEB_CHUNK), 64)
+    nq = next(v for v in (1, 2, 3, 4, 6, 8, 12, 16) if nq <= v)
+    out = {("theta_first", (nq,))}
+    if C * T > CHEB_CHUNK:
+        out.add(("theta_first_chunked", ()))
+    return out
+
+
+DISPATCH_FAMILIES = ("ln_", "preconv_bias", "tat_fwd", "tat_bwd", "tat_dres", "tat_res", "tat_edge", "tat_dkv", "gtu_tail", "gtu_dx", "theta_first")
+
+
+def dispatch_only(ks):
+    """The members of a kernels() set that belong to the LayerNorm, unfused temporal-attention,
+    GTU-tail and Theta-first dispatchers, as "family<args>" strings."""
+    return {f"{f}<{', '.join(map(str, a))}>" for f, a in ks if f.startswith(DISPATCH_FAMILIES)}
+
+
+def kernels(N, T, K, F, C, B, sparse=True, flash=True, d_k=32, h=None, D=None, d_v=None, first=None,
+            res_kind=None, train=False):
     """The set of (kernel family, template args) a block of this geometry runs.  sparse: the
     union support is <= 1/4 dense (block_fn.use_sparse); flash: not forced off
-    (block_fn.use_flash: on the sparse path, d_k == 32, B <= 128).  Mirrors block.hip mkdims."""
+    (block_fn.use_flash: on the sparse path, d_k == 32, B <= 128).  Mirrors block.hip mkdims.
+    With h and D given the LayerNorm, temporal-attention and GTU dispatchers are included too
+    (d_v defaults to d_k, first to F == 1, res_kind to 0 on the first block and 1 — broadcast
+    res_att — on an inner one, the parity suite's default)."""
     out = set()
+    if h is not None and D is not None:
+        d_v = d_k if d_v is None else d_v
+        first = (F == 1) if first is None else first
+        assert first == (F == 1)  # block.hip mkdims: m.first = (F == 1)
+        res_kind = (0 if first else 1) if res_kind is None else res_kind
+        ff = tat_fused_fwd_ok(N, T, h, d_k, d_v)
+        fb = ff and tat_fused_bwd_ok(N, T, h, d_k, d_v, F, res_kind)
+        if ff:
+            out.add(("tat_fused_fwd", ()))
+        if fb:
+            out.add(("tat_fused_bwd", ()))
+        out |= ln_sites(N, T, F, D, B, ff, fb, train=train)
+        out |= tat_kernels(T, h, d_k, d_v, F, res_kind, ff, fb)
+        if d_k != d_v:  # the same kernels with two different widths in the [Q | K | V] row: (path,)
+            out |= {(f + "_dkv", a[:1]) for f, a in out if f in ("tat_fwd", "tat_bwd")}
+            out.add(("tat_dkv_order", ("dk>dv" if d_k > d_v else "dk<dv",)))  # which of the row's blocks is the wider
+        out |= gtu_kernels(C, T, first)
+        if train and not gtu_fused_ok(C, T):  # the fcmy dropout rides in the tail kernels, both directions
+            out |= {("gtu_tail_drop", a) for f, a in gtu_kernels(C, T, first) if f == "gtu_tail_pair"}
     if not sparse:
         return out
     if cheb_agg_ok(F, C, K, T):
         out |= cheb_agg_kernels(T, K, F, C)
+    else:
+        out |= theta_first_kernels(C, T)
     if flash and d_k == 32 and B <= 128:
         out |= flash_small_kernels(N) if N <= FLASH_SMALL_N else {("flash_streamed", ())}
     return out

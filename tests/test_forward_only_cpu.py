@@ -43,9 +43,9 @@ def test_size_errors_match_block_sizes():
 
 
 def _dims(name, first, B):
-    N, T, K, h, D, dk, C = tp.CONFIGS[name]
-    d = ab.BlockDims(B, N, 1 if first else C, T, h, dk, dk, D, K, C, 0 if first else 1, 0, 0.05, 0)
-    d.cheb_sparse, d.cheb_flash, d.cheb_nnz, d.cheb_apa_nnz = 1, 1, 3 * N, 4 * N
+    N, T, K, h, D, dk, C, dv = tp.config(name)
+    d = ab.BlockDims(B, N, 1 if first else C, T, h, dk, dv, D, K, C, 0 if first else 1, 0, 0.05, 0)
+    d.cheb_sparse, d.cheb_flash, d.cheb_nnz, d.cheb_apa_nnz = 1, int(dk == 32), 3 * N, 4 * N  # block_fn.use_flash
     return d
 
 
@@ -59,14 +59,14 @@ def test_workspace_holds_no_backward_state(name, first):
     lib = ab.c_abi()
     B = BASELINE_B.get(name, 2)
     d = _dims(name, first, B)
-    N, T, K, h, D, dk, C = tp.CONFIGS[name]
+    N, T, K, h, D, dk, C, dv = tp.config(name)
     F = d.F
     bits, sv, sc, wb = ctypes.c_uint32(0), ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
     assert lib.dstagnn_block_paths(ctypes.byref(d), ctypes.byref(bits)) == 0, lib.dstagnn_last_error()
     assert lib.dstagnn_block_sizes(ctypes.byref(d), ctypes.byref(sv), ctypes.byref(sc)) == 0
     assert lib.dstagnn_block_forward_only_size(ctypes.byref(d), ctypes.byref(wb)) == 0
     BN, BFT, S = B * N, B * F * T, 3 * T - 12
-    QW, HV = 3 * h * dk, h * dk
+    QW, HV = 2 * h * dk + h * dv, h * dv
     floor = 3 * BN * C * T + BN * C * S
     if bits.value & PATH["GTU_FUSED_FWD"]:
         floor += BN * 2 * C * S

@@ -268,8 +268,8 @@ def _scaled_laplacian_fixed_start(W):
     return (2.0 * Lap) / lam - np.eye(W.shape[0])
 
 
-def _oracle_case(B, N, T, K, h, D, dk, C, first, res_kind, seed, train=False, hub=0):
-    """hub=H > 0: node 0 gets H in-edges and node 1 H out-edges in both graphs, i.e. one column
+def _oracle_case(B, N, T, K, h, D, dk, C, first, res_kind, seed, train=False, hub=0, d_v=None):
+    """d_v: the value width of the temporal attention (default d_k).  hub=H > 0: node 0 gets H in-edges and node 1 H out-edges in both graphs, i.e. one column
     and one row of the supports longer than the 64-entry chunk the kernels walk them in."""
     from oracle import dstagnn_ref as ref
     import dstagnn_drought_amd as D_
@@ -286,13 +286,14 @@ def _oracle_case(B, N, T, K, h, D, dk, C, first, res_kind, seed, train=False, hu
     Lt = _scaled_laplacian_fixed_start(tmd)
     cheb = [torch.from_numpy(c).float() for c in D_.cheb_polynomial(Lt, K)][:K]
     F = 1 if first else C
-    p = ref.random_block_params(gen, F, F, K, C, N, T, D, dk, dk, h)
+    dv = dk if d_v is None else d_v
+    p = ref.random_block_params(gen, F, F, K, C, N, T, D, dk, dv, h)
     x = torch.randn(B, N, F, T, generator=gen)
     if res_kind == 0:
         res = 0
     else:
         res = torch.randn(B, 1 if res_kind == 1 else F, h, T, T, generator=gen)
-    return ref, p, x, res, cheb, torch.from_numpy(pa).float(), dict(n_heads=h, d_k=dk, d_v=dk, K=K), gen
+    return ref, p, x, res, cheb, torch.from_numpy(pa).float(), dict(n_heads=h, d_k=dk, d_v=dv, K=K), gen
 
 
 @pytest.mark.parametrize("first,res_kind,sparse", [(False, 1, True), (True, 0, True), (False, 2, True),
@@ -437,7 +438,70 @@ CONFIGS = {
     "t7h2": (40, 7, 3, 2, 64, 32, 32),
     "t10": (40, 10, 3, 3, 64, 32, 32),
     "t13": (40, 13, 3, 3, 64, 32, 32),
+    # --- the geometries of DISPATCH_CASES below; an optional eighth entry is d_v (default d_k)
+    # both sides of the unfused TAt hand-overs (see "t64" above) and a series whose last
+    # 16-column chunk is partial: T = 63 | 64 (backward G = 256 -> column chunks; 63 = 3 * 16 + 15),
+    # 87 | 88 (forward; 87 = 5 * 16 + 7), 100 = 6 * 16 + 4
+    "t63": (40, 63, 2, 2, 64, 32, 32),
+    "t64k2": (40, 64, 2, 2, 64, 32, 32),
+    "t87": (40, 87, 2, 2, 64, 32, 32),
+    "t88": (40, 88, 2, 2, 64, 32, 32),
+    "t100": (40, 100, 2, 2, 64, 32, 32),
+    # d_k != d_v: the qkv row is [Q | K | V] of width 2 h d_k + h d_v; neither the matrix-core nor
+    # the fused TAt kernels admit it, so T = 12 takes the G = 64 VALU kernels, T = 24 G = 256, T = 100
+    # the column chunks (d_v = 16: forward 4 (83 T + T^2) = 73 200 B, backward 4 (100 T + 2 T^2))
+    "dv16": (40, 12, 3, 3, 64, 32, 32, 16),
+    "dk16dv32": (40, 12, 3, 3, 64, 16, 32, 32),
+    "dk12dv20": (40, 12, 3, 3, 64, 12, 32, 20),
+    "dv16t24": (40, 24, 3, 3, 64, 32, 32, 16),
+    "dv16t100": (40, 100, 2, 2, 64, 32, 32, 16),
+    # EmbedS LayerNorm rows of D floats: VPT = 2, 4, 8, 16, the float4 kernels <1> and <4>, and the
+    # workgroup-per-row kernels <8> and <16> (D > 1024: contribution-form backward, the pre_conv
+    # bias gradient as its own column sum)
+    "d128": (40, 12, 3, 3, 128, 32, 32),
+    "d200": (40, 12, 3, 3, 200, 32, 32),
+    "d256": (40, 12, 3, 3, 256, 32, 32),
+    "d500": (40, 12, 3, 3, 500, 32, 32),
+    "d1000": (40, 12, 3, 3, 1000, 32, 32),
+    "d1024": (40, 12, 3, 3, 1024, 32, 32),
+    "d1040": (40, 12, 3, 3, 1040, 32, 32),
+    "d2100": (40, 12, 3, 3, 2100, 32, 32),
+    # TAt / EmbedT LayerNorm rows of N floats with h = 2 (the fused TAt kernels refuse): VPT = 2, 4,
+    # float4 <1> and <4> (EmbedT: backward only, its forward reads x with element stride T), and
+    # the workgroup-per-row kernel <8>
+    "n100h2": (100, 12, 3, 2, 64, 32, 32),
+    "n200h2": (200, 12, 3, 2, 64, 32, 32),
+    "n256h2": (256, 12, 3, 2, 64, 32, 32),
+    "n1024h2": (1024, 12, 3, 2, 64, 32, 32),
+    "n1030h2": (1030, 12, 3, 2, 64, 32, 32),
+    # C outside {16, 32} (and F = 64 > 32): cheb_agg_ok refuses, the Theta-first sparse kernels run
+    # at NQ = cdiv(C T, 64) = 1, 2, 3, 4, 6, 8, 12; the GTU tail's runtime-C kernels and the
+    # K-concatenated input-gradient GEMM (gtu_tconv is C = 32 only)
+    "c8t7": (40, 7, 3, 2, 64, 32, 8),
+    "c8t12": (40, 12, 3, 2, 64, 32, 8),
+    "c24t8": (40, 8, 3, 2, 64, 32, 24),
+    "c24t10": (40, 10, 3, 2, 64, 32, 24),
+    "c24t12": (40, 12, 3, 2, 64, 32, 24),
+    "c64t8": (40, 8, 3, 2, 64, 32, 64),
+    "c64t12": (40, 12, 3, 2, 64, 32, 64),
+    # the split GTU tail off C = 32: C = 16 at T = 24, C = 4 at T = 20 (T >= 20 splits both directions)
+    "c16t24": (40, 24, 3, 2, 64, 32, 16),
+    "c4t20": (40, 20, 3, 2, 64, 32, 4),
+    # the two tail gates disagree: forward 28 172 B of LDS (one kernel), backward 33 236 B > 32 KB
+    # (LN / residual | GEMM | gates), so an unsplit forward's saved state feeds the split backward
+    "c72t19": (40, 19, 3, 2, 64, 32, 72),
+    # F = 6 is no multiple of 4: the matrix-core TAt backward cannot fold the broadcast res_att's
+    # gradient in-kernel and falls back to op_sum_middle
+    "c6t12": (40, 12, 3, 2, 64, 32, 6),
 }
+
+
+def config(name):
+    """(N, T, K, h, D, dk, C, dv) of a CONFIGS row; the optional eighth entry d_v defaults to d_k."""
+    row = CONFIGS[name]
+    return tuple(row[:7]) + (row[7] if len(row) > 7 else row[5],)
+
+
 RELU_EPS = 1e-5  # ReLU decisions may differ from the fp64 oracle's only where |z| <= RELU_EPS * max|z|
 
 
@@ -519,15 +583,15 @@ def _run_config_vs_oracle(name, first, B, seed=3, flash=None, tol=TOL, relu_eps=
     stats (dict, optional) receives "mask_elems", the number of ReLU decisions compared."""
     import dstagnn_drought_amd as D_
     from dstagnn_drought_amd.block_fn import dropout_masks, block_paths
-    N, T, K, h, D, dk, C = CONFIGS[name]
+    N, T, K, h, D, dk, C, dv = config(name)
     if res_kind is None:
         res_kind = 0 if first else 1
     ref, p, x, res, cheb, apa, dims, gen = _oracle_case(B, N, T, K, h, D, dk, C, first, res_kind, seed=seed,
-                                                            hub=hub)
+                                                            hub=hub, d_v=dv)
     g_out = torch.randn(B, N, C, T, generator=gen)
     g_re = torch.randn(B, x.shape[2], h, T, T, generator=gen)
     F = x.shape[2]
-    blk = D_.DSTAGNN_block("cpu", F, F, K, C, C, 1, cheb, apa, apa, N, T, D, dk, dk, h)
+    blk = D_.DSTAGNN_block("cpu", F, F, K, C, C, 1, cheb, apa, apa, N, T, D, dk, dv, h)
     blk.load_state_dict(p)
     blk = blk.cuda().train(train)
     blk.flash_cheb = flash
@@ -703,11 +767,11 @@ def test_flash_large_batch_vs_oracle(name, B, flash):
 
 def _pin(name, first, B, must, must_not=(), train=False, flash=None, hub=0):
     """One PINNED_CASES row; the fused temporal-attention bits are added from the gates'
-    conditions (tat_fused.hip tat_fused_fwd_ok / tat_fused_bwd_ok: h = 3, d_k = 32, N <= 320,
+    conditions (tat_fused.hip tat_fused_fwd_ok / tat_fused_bwd_ok: h = 3, d_k = d_v = 32, N <= 320,
     T in {8, 12, 16}; the backward with broadcast res_att — the inner-block default here —
     only where F T is a multiple of the 48-row tile), so both presence and absence are asserted."""
-    N, T, K, h, D, dk, C = CONFIGS[name]
-    fwd = h == 3 and dk == 32 and N <= 320 and T in (8, 12, 16)
+    N, T, K, h, D, dk, C, dv = config(name)
+    fwd = h == 3 and dk == 32 and dv == 32 and N <= 320 and T in (8, 12, 16)
     bwd = fwd and (first or (C * T) % 48 == 0)
     must, must_not = set(must), set(must_not)
     (must if fwd else must_not).add(TF_FWD)
@@ -779,6 +843,113 @@ def test_pinned_templates_vs_oracle(case):
     worst = max(errs, key=errs.get)
     print(f"PINNED {_pin_id(case)}: flips {flips} / {stats['mask_elems']}, worst err/scale {errs[worst]:.3e} on {worst}")
     assert flips <= FLIP_CAP * stats["mask_elems"], f"{name}: {flips} ReLU decisions of {stats['mask_elems']} differ"
+
+
+def _disp(name, first, B=2, train=False, res_kind=None):
+    """One DISPATCH_CASES row: (name, first, B, train, res_kind, must, must_not), the path bits
+    predicted from the gates' conditions as in _pin (sparse always: the test graphs' union support
+    is far below 1/4 dense)."""
+    N, T, K, h, D, dk, C, dv = config(name)
+    F = 1 if first else C
+    rk = (0 if first else 1) if res_kind is None else res_kind
+    fwd = h == 3 and dk == 32 and dv == 32 and N <= 320 and T in (8, 12, 16)
+    bwd = fwd and (rk != 1 or (F * T) % 48 == 0)
+    agg = F <= 32 and C in (16, 32) and 16 * K * F * T <= 160 << 10
+    gtu = C == 32 and T == 12
+    must, must_not = {"sparse"}, set()
+    for bit, on in ((TF_FWD, fwd), (TF_BWD, bwd), ("cheb_agg", agg), ("gtu_fused_fwd", gtu), ("gtu_fused_bwd", gtu),
+                    ("flash", dk == 32), ("flash_small", dk == 32 and N <= 512)):
+        (must if on else must_not).add(bit)
+    return (name, first, B, train, res_kind, frozenset(must), frozenset(must_not))
+
+
+def _disp_id(c):
+    name, first, B, train, res_kind = c[:5]
+    return f"{name}-{'first' if first else 'inner'}-B{B}" + ("-train" if train else "") + \
+        (f"-res{res_kind}" if res_kind is not None else "")
+
+
+# (name, first, B, train, res_kind (None: 0 on the first block, 1 = broadcast on an inner one), must,
+# must_not).  tests/kernel_coverage.py maps each row to the LayerNorm / unfused-TAt / GTU-tail /
+# Theta-first branches it runs; tests/test_parity_coverage_cpu.py holds this table against the
+# branches the gates admit.
+#
+# FLIP_CAP's condition, checked on the CPU for every row (seed 3): the fp32 oracle against the
+# fp64 oracle flips 0 of the 13 440 .. 1 186 560 ReLU decisions of each geometry (worst fraction
+# 0, against the 1e-5 the cap presumes).
+# Measured on the MI355X (worst err / scale over all tensors, per row; every row 0 flips; no row
+# needs the 2 x own arm of the bound — the largest value is 20 times below the flat 1e-4):
+#   TAt hand-overs   t63 1.1e-6 / 8.6e-7 (inner / first)  t64k2 1.7e-6 / 1.0e-6  t87 1.0e-6 / 1.1e-6
+#                    t88 1.0e-6 / 8.1e-7  t100 1.3e-6 / 9.3e-7, full res_att 9.4e-7
+#   d_k != d_v       dv16 8.7e-7 / 7.8e-7, train 9.0e-7  dk16dv32 8.8e-7  dk12dv20 1.1e-6 / 9.0e-7
+#                    dv16t24 1.1e-6, full res_att 1.0e-6  dv16t100 1.2e-6
+#   EmbedS LN        d128 1.0e-6  d200 1.7e-6 (train 1.0e-6)  d256 1.0e-6 (8.5e-7)  d500 1.9e-6  d1000 1.5e-6
+#                    d1024 1.1e-6 (1.1e-6)  d1040 1.5e-6 (1.7e-6)  d2100 1.7e-6
+#   LN over N        n100h2 7.6e-7 / 6.2e-7  n200h2 7.8e-7 / 7.5e-7  n256h2 6.1e-7 / 7.1e-7
+#                    n1024h2 6.3e-7 / 3.1e-6  n1030h2 9.7e-7 / 1.5e-6
+#   GTU / Theta      c8t7 5.3e-7 / 6.6e-7, full res_att 5.1e-7  c8t12 1.9e-6 / 1.3e-6, full res_att 8.8e-7
+#                    c24t8 7.8e-7 / 3.4e-6  c24t10 7.9e-7 / 9.1e-7  c24t12 7.9e-7  c64t8 8.9e-7 / 2.0e-6
+#                    c64t12 9.1e-7 / 5.8e-7  c16t24 6.7e-7 / 7.8e-7, train 6.6e-7  c72t19 2.3e-6 / 2.6e-6, train 1.4e-6
+#                    c4t20 5.0e-6 / 1.3e-6  c6t12 9.2e-7
+DISPATCH_CASES = (
+    # unfused TAt hand-overs and the partial column chunk; broadcast res_att on the inner block (the
+    # op_sum_middle fallback follows the column-chunk backward), once a full res_att
+    [_disp(n, first) for n in ("t63", "t64k2", "t87", "t88", "t100") for first in (False, True)] +
+    [_disp("t100", False, res_kind=2)] +
+    # d_k != d_v
+    [_disp("dv16", False), _disp("dv16", True), _disp("dv16", False, train=True), _disp("dk16dv32", False),
+     _disp("dk12dv20", False), _disp("dk12dv20", True), _disp("dv16t24", False), _disp("dv16t100", False)] +
+    # EmbedS LayerNorm; train where the kernel family changes (dropout rides in its epilogue)
+    [_disp(n, False) for n in ("d128", "d200", "d256", "d500", "d1000", "d1024", "d1040", "d2100")] +
+    [_disp(n, False, train=True) for n in ("d200", "d256", "d1024", "d1040")] +
+    # TAt / EmbedT LayerNorm over N
+    [_disp(n, first) for n in ("n100h2", "n200h2", "n256h2") for first in (False, True)] +
+    [_disp(n, first, B=1) for n in ("n1024h2", "n1030h2") for first in (False, True)] +
+    # GTU tail and Theta-first
+    [_disp(n, first) for n in ("c8t7", "c8t12", "c24t8", "c24t10", "c64t8", "c64t12", "c16t24", "c72t19")
+     for first in (False, True)] +
+    [_disp("c72t19", False, train=True), _disp("c16t24", False, train=True)] +
+    [_disp("c24t12", False), _disp("c4t20", False), _disp("c4t20", True), _disp("c6t12", False)] +
+    # a full res_att through the unfused kernels (d res_att written in place, no sum over f): the
+    # matrix cores, G = 64, G = 256 (the column chunks: t100 above)
+    [_disp("c8t12", False, res_kind=2), _disp("c8t7", False, res_kind=2), _disp("dv16t24", False, res_kind=2)])
+
+
+@pytest.mark.parametrize("case", DISPATCH_CASES, ids=_disp_id)
+def test_dispatch_branches_vs_oracle(case):
+    """Every branch of the LayerNorm (ops.hip op_ln_fwd / op_ln_bwd), unfused temporal-attention
+    (tat.hip tat_fwd_path / tat_bwd_path), GTU-tail (gtu_tail.hip tail_split_* / tail_ct) and
+    Theta-first (cheb_sparse.hip DS_NQ_DISPATCH) dispatchers that an admitted geometry reaches and
+    no other table does, each pinned by a tiny case whose path bits are asserted first.  Same
+    bound and flip cap as test_pinned_templates_vs_oracle."""
+    _need_gpu()
+    import kernel_coverage as kc
+    name, first, B, train, res_kind, must, must_not = case
+    N, T, K, h, D, dk, C, dv = config(name)
+    pred = kc.kernels(N, T, K, 1 if first else C, C, B, d_k=dk, h=h, D=D, d_v=dv, res_kind=res_kind, train=train)
+    errs, stats, owns = {}, {}, {}
+    flips = _run_config_vs_oracle(name, first, B, train=train, res_kind=res_kind, paths=(set(must), set(must_not)),
+                                  errs=errs, stats=stats, owns=owns)
+    worst = max(errs, key=errs.get)
+    own_arm = {k: f"{owns[k]:.1e}" for k in errs if errs[k] > TOL}  # tensors that needed the 2 x own arm
+    print(f"DISPATCH {_disp_id(case)}: kernels {sorted(kc.dispatch_only(pred))}; flips {flips} / {stats['mask_elems']}, "
+          f"worst err/scale {errs[worst]:.3e} on {worst}" + (f"; 2 x own arm: {own_arm}" if own_arm else ""))
+    assert flips <= FLIP_CAP * stats["mask_elems"], f"{name}: {flips} ReLU decisions of {stats['mask_elems']} differ"
+
+
+def test_layernorm_row_too_long_is_refused():
+    """A d_model past the LayerNorm kernels' 4096-float row (ops.hip op_ln_fwd) must raise from the
+    forward with the library's message, not return numbers."""
+    _need_gpu()
+    import dstagnn_drought_amd as D_
+    B, N, T, K, h, D, dk, C = 1, 40, 12, 3, 3, 4097, 32, 32
+    ref, p, x, res, cheb, apa, dims, gen = _oracle_case(B, N, T, K, h, D, dk, C, False, 1, seed=3)
+    blk = D_.DSTAGNN_block("cpu", C, C, K, C, C, 1, cheb, apa, apa, N, T, D, dk, dk, h)
+    blk.load_state_dict(p)
+    blk = blk.cuda().eval()
+    with pytest.raises(RuntimeError, match="ln_fwd: row too long"):
+        blk(x.cuda(), res.cuda())
+        torch.cuda.synchronize()
 
 
 BF16_TOL = 3e-2      # bf16-operand GEMM variant: normwise ||err||_2 / ||ref||_2 <= BF16_TOL per tensor
