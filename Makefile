@@ -7,6 +7,8 @@ OBJ := $(patsubst dstagnn_drought_amd/csrc/%.hip,build/%.o,$(SRC))
 LIB := dstagnn_drought_amd/libdstagnn.so
 # host build of the EMD solver for the CPU tests only (the package never loads it)
 EMD_HOST := tests/native/libemd_host.so
+# ... and of its rectangular entry (series with gaps: tests/test_emd_rect_cpu.py)
+EMD_RECT_HOST := tests/native/libemd_rect_host.so
 # the PyTorch-ROCm operator library (TORCH_LIBRARY(dstagnn, ...)) over libdstagnn.so
 EXT := dstagnn_drought_amd/_C.so
 PY ?= python3
@@ -24,7 +26,7 @@ RACEBUG := abtest/racebug/libdstagnn.so
 # hipcc-built host program driving the block through the C-ABI alone (tests/test_gpu_native_abi.py)
 ABI_TEST := tests/native/block_abi_test
 
-all: $(LIB) $(EXT) $(EMD_HOST) tools/fetch_calib $(RACEBUG) $(ABI_TEST)
+all: $(LIB) $(EXT) $(EMD_HOST) $(EMD_RECT_HOST) tools/fetch_calib $(RACEBUG) $(ABI_TEST)
 
 racebug: $(RACEBUG)
 
@@ -65,6 +67,9 @@ $(ABI_TEST): tests/native/block_abi_main.cpp include/dstagnn.h $(LIB)
 $(EMD_HOST): tests/native/emd_host.cpp dstagnn_drought_amd/csrc/emd_simplex.hpp
 	g++ -O2 -std=c++17 -fPIC -shared -Wall -o $@ $<
 
+$(EMD_RECT_HOST): tests/native/emd_rect_host.cpp dstagnn_drought_amd/csrc/emd_simplex.hpp
+	g++ -O2 -std=c++17 -fPIC -shared -Wall -o $@ $<
+
 build/%.o: dstagnn_drought_amd/csrc/%.hip dstagnn_drought_amd/csrc/*.hpp include/dstagnn.h
 	@mkdir -p build
 	$(HIPCC) $(CXXFLAGS) -c $< -o $@
@@ -73,6 +78,6 @@ $(LIB): $(OBJ)
 	$(HIPCC) -shared --offload-arch=$(ARCH) -o $@ $(OBJ)
 
 clean:
-	rm -rf build $(LIB) $(EXT) $(EMD_HOST) $(ABI_TEST) tools/fetch_calib abtest/racebug abtest/tftime
+	rm -rf build $(LIB) $(EXT) $(EMD_HOST) $(EMD_RECT_HOST) $(ABI_TEST) tools/fetch_calib abtest/racebug abtest/tftime
 
 .PHONY: all clean racebug tftime

@@ -13,10 +13,14 @@
 // col's points down.  Potentials: tree arcs have c + pi[tail] - pi[head] = 0, pi[root] = 0.
 // Start: the all-artificial star (every flow > 0: strongly feasible).  Entering arc: block
 // search over the T^2 real arcs (most negative reduced cost of the first block that has
-// one, block = ceil64(max(T,64)) arcs, ties to the earliest arc in scan order).  Leaving arc:
+// one, block = ceil64(max(T,Tc,64)) arcs, ties to the earliest arc in scan order).  Leaving arc:
 // the strongly feasible rule (first blocking arc on the tail side with <, last on the head
 // side with <=) which rules out cycling under degeneracy.  At the end the potentials are
 // recomputed from the tree and a full pricing pass re-checks optimality (drift guard).
+//
+// Rectangular problems (a series with gaps: each node's distribution lives on its own observed
+// steps): T rows and Tc columns, cols T..T+Tc-1, root T+Tc, T*Tc real arcs.  With Tc == T every
+// index, block length and floating-point operation is the square problem's, in the same order.
 //
 // Shared by the gfx950 kernel (stag.hip: one wave per pair, workspace in LDS, pricing split
 // over the 64 lanes, tree updates executed redundantly by every lane) and a host build of
@@ -33,15 +37,16 @@
 namespace emd {
 
 constexpr double kRcEps = 1e-11;       // enter only below -kRcEps * max(1, max|c|)
-constexpr int kMaxPivotFactor = 64;    // give up (status 2) after 64 * T^2 pivots
+constexpr int kMaxPivotFactor = 64;    // give up (status 2) after 64 * T * Tc pivots
 
-// Per-pair workspace (node arrays sized n = 2T + 1).
+// Per-pair workspace (node arrays sized n = T + Tc + 1).
 struct Work {
-  int T, F;
+  int T, F;           // T: row count
+  int Tc;             // column count (== T for the square problem)
   const double* xh;   // (T, F) unit rows of node i (zero rows stay 0)
-  const double* yh;   // (T, F) unit rows of node j
+  const double* yh;   // (Tc, F) unit rows of node j
   const double* p;    // (T) supply
-  const double* q;    // (T) demand
+  const double* q;    // (Tc) demand
   double* flow;       // (n) flow on the tree arc to parent
   double* pi;         // (n) potentials
   int16_t* parent;    // (n)
@@ -49,7 +54,7 @@ struct Work {
   int16_t* nsib;      // (n) next sibling, -1 none
   int16_t* psib;      // (n) previous sibling, -1 none
   int32_t* stamp;     // (n) ancestor marks for the join search
-  const double* Dm;   // optional dense (T, T) cost (wasserstein_distance(p, q, D) entry); null: cosine
+  const double* Dm;   // optional dense (T, Tc) cost (wasserstein_distance(p, q, D) entry); null: cosine
 };
 
 // The reference's LP has equality rows for p and columns for q; HiGHS declares it infeasible
@@ -70,24 +75,25 @@ EMD_HD double clean_cost(double c) {
   return c;
 }
 
-// bytes of one Work for T, F (8-byte aligned pieces: doubles first)
-EMD_HD int64_t work_bytes(int T, int F) {
-  const int64_t n = 2 * (int64_t)T + 1;
-  int64_t b = 8 * (2 * (int64_t)T * F + 2 * (int64_t)T + 2 * n);
+// bytes of one Work for Tr rows, Tc columns, F (8-byte aligned pieces: doubles first)
+EMD_HD int64_t work_bytes_rect(int Tr, int Tc, int F) {
+  const int64_t tt = (int64_t)Tr + Tc, n = tt + 1;
+  int64_t b = 8 * (tt * F + tt + 2 * n);
   b += 2 * 4 * n;
   b = (b + 7) & ~7ll;
   b += 4 * n;
   return (b + 15) & ~15ll;
 }
+EMD_HD int64_t work_bytes(int T, int F) { return work_bytes_rect(T, T, F); }
 
-EMD_HD void carve(Work& w, char* base, int T, int F) {
-  const int64_t n = 2 * (int64_t)T + 1;
+EMD_HD void carve_rect(Work& w, char* base, int Tr, int Tc, int F) {
+  const int64_t n = (int64_t)Tr + Tc + 1;
   double* d = (double*)base;
-  w.T = T; w.F = F;
-  w.xh = d; d += (int64_t)T * F;
-  w.yh = d; d += (int64_t)T * F;
-  w.p = d; d += T;
-  w.q = d; d += T;
+  w.T = Tr; w.Tc = Tc; w.F = F;
+  w.xh = d; d += (int64_t)Tr * F;
+  w.yh = d; d += (int64_t)Tc * F;
+  w.p = d; d += Tr;
+  w.q = d; d += Tc;
   w.flow = d; d += n;
   w.pi = d; d += n;
   int16_t* s = (int16_t*)d;
@@ -100,10 +106,11 @@ EMD_HD void carve(Work& w, char* base, int T, int F) {
   w.stamp = (int32_t*)c;
   w.Dm = nullptr;
 }
+EMD_HD void carve(Work& w, char* base, int T, int F) { carve_rect(w, base, T, T, F); }
 
 // D_rc of data/STAG_gen.py:50-57: 1 - cosine, nan -> 1, clipped to [0, 1]
 EMD_HD double cost(const Work& w, int r, int c) {
-  if (w.Dm) return clean_cost(w.Dm[(int64_t)r * w.T + c]);
+  if (w.Dm) return clean_cost(w.Dm[(int64_t)r * w.Tc + c]);
   const double* a = w.xh + (int64_t)r * w.F;
   const double* b = w.yh + (int64_t)c * w.F;
   double s = 0.0;
@@ -116,7 +123,7 @@ EMD_HD double cost(const Work& w, int r, int c) {
 // cost of the tree arc between v and parent[v]
 EMD_HD double tree_cost(const Work& w, int v, int par, double art) {
   const int T = w.T;
-  if (par == 2 * T) return v < T ? 0.0 : art;
+  if (par == T + w.Tc) return v < T ? 0.0 : art;
   return v < T ? cost(w, v, par - T) : cost(w, par, v - T);
 }
 
@@ -143,7 +150,7 @@ struct Cand {
 
 // Recompute every potential from the tree (preorder walk from the root).
 EMD_HD void potentials_from_tree(Work& w, double art) {
-  const int root = 2 * w.T;
+  const int root = w.T + w.Tc;
   w.pi[root] = 0.0;
   int u = w.fchild[root];
   while (u >= 0) {
@@ -163,9 +170,9 @@ EMD_HD void potentials_from_tree(Work& w, double art) {
 // sync(): makes the lane-parallel initialisation visible to every lane before the serial part.
 template <int NL, class Reduce, class Sync>
 EMD_HD double solve(Work& w, int lane, Reduce reduce, Sync sync, double cmax, int* status, int64_t* pivots_out) {
-  const int T = w.T;
-  const int n = 2 * T + 1, root = 2 * T;
-  const int64_t narcs = (int64_t)T * T;
+  const int T = w.T, Tc = w.Tc;
+  const int n = T + Tc + 1, root = T + Tc;
+  const int64_t narcs = (int64_t)T * Tc;
   const double art = (cmax + 1.0) * n;   // > any path cost
   const double eps = kRcEps * (cmax > 1.0 ? cmax : 1.0);
   // the all-artificial start
@@ -180,7 +187,8 @@ EMD_HD double solve(Work& w, int lane, Reduce reduce, Sync sync, double cmax, in
     w.stamp[v] = 0;
   }
   sync();
-  int64_t blk = ((T > 64 ? T : 64) + 63) / 64 * 64;
+  const int tb = T > Tc ? T : Tc;
+  int64_t blk = ((tb > 64 ? tb : 64) + 63) / 64 * 64;
   if (blk > narcs) blk = narcs;
   int64_t next = 0, piv = 0;
   const int64_t cap = (int64_t)kMaxPivotFactor * narcs + 16 * n;
@@ -197,7 +205,7 @@ EMD_HD double solve(Work& w, int lane, Reduce reduce, Sync sync, double cmax, in
       for (int64_t o = lane; o < len; o += NL) {
         int64_t a = pos + o;
         if (a >= narcs) a -= narcs;
-        const int r = (int)(a / T), c = (int)(a - (int64_t)r * T);
+        const int r = (int)(a / Tc), c = (int)(a - (int64_t)r * Tc);
         const double rc = cost(w, r, c) + w.pi[r] - w.pi[T + c];
         if (rc < mine.rc) { mine.rc = rc; mine.off = (int)o; }
       }
@@ -224,7 +232,7 @@ EMD_HD double solve(Work& w, int lane, Reduce reduce, Sync sync, double cmax, in
     rechecked = false;
     if (++piv > cap) { *status = 2; break; }
     next = pos;
-    const int r_in = best.off / T, c_in = best.off - r_in * T;
+    const int r_in = best.off / Tc, c_in = best.off - r_in * Tc;
     const int first = r_in, second = T + c_in;
     const double rc_in = best.rc;
     // ---- join: lowest common ancestor ----

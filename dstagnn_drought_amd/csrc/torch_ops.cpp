@@ -23,7 +23,8 @@
 //                           with gaps: statistics of the observed values, forward fill, in-gather imputation
 //   dstagnn::gemm_f32      the strided f32-MFMA GEMM (tests / tools)
 //   dstagnn::colsum         the fixed-order column-sum reduction (bias / LayerNorm affine grads; tests)
-//   dstagnn::stag_* / emd_dense / fast_stag_distances / graph_topk   the graph builders
+//   dstagnn::stag_* / emd_dense / fast_stag_distances / graph_topk[_masked]   the graph builders
+//                           (stag_prep_masked / stag_emd_pairs_masked: a series with gaps)
 //                           (data/STAG_gen.py:17-129, data/fast_STAG_gen.py:16-74)
 //
 // Conventions: inputs are borrowed (contiguous, on the HIP device, fp32 —
@@ -1189,6 +1190,48 @@ std::tuple<Tensor, Tensor, Tensor> stag_emd_pairs(const Tensor& xhat, const Tens
 
 int64_t stag_emd_lds_bytes(int64_t T, int64_t F) { return dstagnn_stag_emd_lds_bytes((int)T, (int)F); }
 
+// series with gaps: data (T,N,F) -> (xhat (N,T,F), p (N,T), psum (N), cnt (N) int32, tidx (N,T) int32)
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> stag_prep_masked(const Tensor& data, double null_val) {
+  check_dev(data, at::kDouble, "data");
+  TORCH_CHECK(data.dim() == 3, "data must be (T, N, F)");
+  const int64_t T = data.size(0), N = data.size(1), F = data.size(2);
+  c10::DeviceGuard guard(data.device());
+  auto o = data.options();
+  Tensor xhat = at::empty({N, T, F}, o), p = at::empty({N, T}, o), psum = at::empty({N}, o);
+  Tensor cnt = at::empty({N}, o.dtype(at::kInt)), tidx = at::empty({N, T}, o.dtype(at::kInt));
+  check_rc(dstagnn_stag_prep_masked(data.data_ptr<double>(), (int)T, (int)N, (int)F, null_val,
+                                    xhat.data_ptr<double>(), p.data_ptr<double>(), psum.data_ptr<double>(),
+                                    cnt.data_ptr<int32_t>(), tidx.data_ptr<int32_t>(), stream_of(data)),
+           "dstagnn_stag_prep_masked");
+  return {xhat, p, psum, cnt, tidx};
+}
+
+// the pair solve on the compacted prep; tmax >= every cnt (read once by the caller)
+std::tuple<Tensor, Tensor, Tensor> stag_emd_pairs_masked(const Tensor& xhat, const Tensor& p, const Tensor& psum,
+                                                         const Tensor& cnt, int64_t tmax, int64_t min_observed,
+                                                         const Tensor& pairs, bool with_pivots) {
+  check_dev(xhat, at::kDouble, "xhat");
+  check_dev(p, at::kDouble, "p");
+  check_dev(psum, at::kDouble, "psum");
+  check_dev(cnt, at::kInt, "cnt");
+  check_dev(pairs, at::kInt, "pairs");
+  const int64_t N = xhat.size(0), T = xhat.size(1), F = xhat.size(2), P = pairs.size(0);
+  TORCH_CHECK(cnt.numel() == N && psum.numel() == N && p.numel() == N * T, "stag_emd_pairs_masked: shapes disagree");
+  c10::DeviceGuard guard(xhat.device());
+  Tensor out = at::empty({P}, xhat.options());
+  Tensor st = at::empty({P}, pairs.options());
+  Tensor piv = at::empty({with_pivots ? P : 0}, pairs.options().dtype(at::kLong));
+  check_rc(dstagnn_stag_emd_pairs_masked(xhat.data_ptr<double>(), p.data_ptr<double>(), psum.data_ptr<double>(),
+                                         cnt.data_ptr<int32_t>(), (int)T, (int)tmax, (int)min_observed, (int)N,
+                                         (int)F, pairs.data_ptr<int32_t>(), P, out.data_ptr<double>(),
+                                         st.data_ptr<int32_t>(), with_pivots ? piv.data_ptr<int64_t>() : nullptr,
+                                         stream_of(xhat)),
+           "dstagnn_stag_emd_pairs_masked");
+  return {out, st, piv};
+}
+
+int64_t stag_emd_lds_bytes_rect(int64_t Tr, int64_t Tc) { return dstagnn_stag_emd_lds_bytes_rect((int)Tr, (int)Tc); }
+
 // p, q (B,T), D (B,T,T) -> (emd (B), status (B))
 std::tuple<Tensor, Tensor> emd_dense(const Tensor& p, const Tensor& q, const Tensor& D) {
   check_dev(p, at::kDouble, "p");
@@ -1229,6 +1272,26 @@ std::tuple<Tensor, Tensor, Tensor> graph_topk(const Tensor& sta, int64_t k, int6
   check_rc(dstagnn_graph_topk(sta.data_ptr<double>(), (int)N, (int)k, (int)mode, A.data_ptr<double>(),
                               R.data_ptr<double>(), nbr.data_ptr<int32_t>(), stream_of(sta)),
            "dstagnn_graph_topk");
+  return {A, R, nbr};
+}
+
+// graph_topk with excluded (N) uint8 nodes (none: graph_topk)
+std::tuple<Tensor, Tensor, Tensor> graph_topk_masked(const Tensor& sta, int64_t k, int64_t mode,
+                                                     const c10::optional<Tensor>& excluded) {
+  check_dev(sta, at::kDouble, "sta");
+  const int64_t N = sta.size(0);
+  const uint8_t* ex = nullptr;
+  if (excluded.has_value()) {
+    check_dev(*excluded, at::kByte, "excluded");
+    TORCH_CHECK(excluded->numel() == N, "excluded must have one entry per node");
+    ex = excluded->data_ptr<uint8_t>();
+  }
+  c10::DeviceGuard guard(sta.device());
+  Tensor A = at::empty({N, N}, sta.options()), R = at::empty({N, N}, sta.options());
+  Tensor nbr = at::empty({N, k}, sta.options().dtype(at::kInt));
+  check_rc(dstagnn_graph_topk_masked(sta.data_ptr<double>(), (int)N, (int)k, (int)mode, ex, A.data_ptr<double>(),
+                                     R.data_ptr<double>(), nbr.data_ptr<int32_t>(), stream_of(sta)),
+           "dstagnn_graph_topk_masked");
   return {A, R, nbr};
 }
 
@@ -1317,9 +1380,14 @@ TORCH_LIBRARY(dstagnn, m) {
   m.def("stag_prep(Tensor data) -> (Tensor, Tensor, Tensor)");
   m.def("stag_emd_pairs(Tensor xhat, Tensor p, Tensor psum, Tensor pairs, bool with_pivots) -> (Tensor, Tensor, Tensor)");
   m.def("stag_emd_lds_bytes(int T, int F) -> int", stag_emd_lds_bytes);
+  m.def("stag_prep_masked(Tensor data, float null_val) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("stag_emd_pairs_masked(Tensor xhat, Tensor p, Tensor psum, Tensor cnt, int tmax, int min_observed, "
+        "Tensor pairs, bool with_pivots) -> (Tensor, Tensor, Tensor)");
+  m.def("stag_emd_lds_bytes_rect(int Tr, int Tc) -> int", stag_emd_lds_bytes_rect);
   m.def("emd_dense(Tensor p, Tensor q, Tensor D) -> (Tensor, Tensor)");
   m.def("fast_stag_distances(Tensor coords, Tensor feats, float max_distance) -> Tensor");
   m.def("graph_topk(Tensor sta, int k, int mode) -> (Tensor, Tensor, Tensor)");
+  m.def("graph_topk_masked(Tensor sta, int k, int mode, Tensor? excluded) -> (Tensor, Tensor, Tensor)");
   m.def("version() -> int", library_version);
   m.def("prof_start(int capacity) -> ()", prof_start);
   m.def("set_splitk_target(int target) -> int", set_splitk_target);
@@ -1362,9 +1430,12 @@ TORCH_LIBRARY_IMPL(dstagnn, CUDA, m) {
   m.impl("window_gather_masked", window_gather_masked);
   m.impl("stag_prep", stag_prep);
   m.impl("stag_emd_pairs", stag_emd_pairs);
+  m.impl("stag_prep_masked", stag_prep_masked);
+  m.impl("stag_emd_pairs_masked", stag_emd_pairs_masked);
   m.impl("emd_dense", emd_dense);
   m.impl("fast_stag_distances", fast_stag_distances);
   m.impl("graph_topk", graph_topk);
+  m.impl("graph_topk_masked", graph_topk_masked);
 }
 
 TORCH_LIBRARY_IMPL(dstagnn, Autograd, m) {

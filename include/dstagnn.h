@@ -527,6 +527,38 @@ int dstagnn_stag_emd_pairs(const double* xhat, const double* p, const double* ps
                            const int32_t* pairs, int64_t P, double* out, int32_t* status, int64_t* pivots,
                            dstagnn_stream_t stream);
 
+/* STAG_gen on a series with gaps.  An element v of data (T,N,F) is MISSING by the rule of the
+ * window calls above: when null_val is NaN, v != v; otherwise v == null_val (IEEE ==; a NaN
+ * element is then valid and poisons its node as in dstagnn_stag_prep).  Step t of node n is
+ * OBSERVED when none of its F features is missing; cnt[n] counts the observed steps.
+ *
+ * dstagnn_stag_prep_masked: dstagnn_stag_prep over the observed steps only, compacted in their
+ * order to the front of the node's slices: row r < cnt[n] of xhat (N,T,F) / p (N,T) is the
+ * node's r-th observed step, tidx (N,T) int32 its original step; beyond cnt[n] xhat and p are 0
+ * and tidx is -1.  p_r = |x_r| / (sum over observed |x| + 1e-12), the 1e-12 zero-norm guard
+ * kept on observed all-zero rows; psum (N) = sum p (0 for a node with no observed step).  On a
+ * series with no missing element xhat, p and psum have dstagnn_stag_prep's bits.
+ *
+ * dstagnn_stag_emd_pairs_masked: the EMD of pair (i, j) is the optimal transport cost between
+ * the two nodes' norm distributions, each on its OWN observed steps: rows = the cnt[i] observed
+ * steps of i with their p, columns = the cnt[j] observed steps of j, cost
+ * clip(1 - xhat_r . xhat_c, 0, 1) — the reference's LP restricted to those rows and columns,
+ * equivalently the full T x T LP with zero marginals at the missing steps.  With cnt == T
+ * everywhere, out, status and pivots are dstagnn_stag_emd_pairs'.  A node is EXCLUDED when
+ * cnt[n] < min_observed (min_observed >= 1, else DSTAGNN_E_ARG); a pair with an excluded node,
+ * or whose totals differ by > 1e-7 (e.g. a node whose observed rows are all zero), gets 1.0 with
+ * status 1.  status 2: solver pivot cap; 3: a cnt above Tmax (both bugs: raise).  Tmax >= every
+ * cnt[n] of a node in `pairs`, 1 <= Tmax <= T: the LDS workspace is
+ * dstagnn_stag_emd_lds_bytes_rect(Tmax, Tmax), sized by the longest observed support and not by
+ * T.  Needs 2 Tmax + 1 <= 32767 and that size <= 160 KiB.
+ * dstagnn_stag_emd_lds_bytes_rect(Tr, Tc): the workspace of one Tr x Tc problem. */
+int dstagnn_stag_prep_masked(const double* data, int T, int N, int F, double null_val, double* xhat, double* p,
+                             double* psum, int32_t* cnt, int32_t* tidx, dstagnn_stream_t stream);
+int64_t dstagnn_stag_emd_lds_bytes_rect(int Tr, int Tc);
+int dstagnn_stag_emd_pairs_masked(const double* xhat, const double* p, const double* psum, const int32_t* cnt, int T,
+                                  int Tmax, int min_observed, int N, int F, const int32_t* pairs, int64_t P,
+                                  double* out, int32_t* status, int64_t* pivots, dstagnn_stream_t stream);
+
 /* Batched wasserstein_distance(p, q, D) (data/STAG_gen.py:17-38): p, q (B,T), D (B,T,T) dense
  * costs (nan -> 0, +-inf -> +-1e12 as the reference).  1.0 / status 1 when infeasible
  * (negative mass or totals differing by > 1e-7). */
@@ -545,6 +577,15 @@ int dstagnn_fast_stag_distances(const double* coords, int N, int Dc, const doubl
  * written; nbr (N,k) optional, ascending by (key, index).  N <= 8192. */
 int dstagnn_graph_topk(const double* sta, int N, int k, int mode, double* A, double* R, int32_t* nbr,
                        dstagnn_stream_t stream);
+
+/* dstagnn_graph_topk with excluded nodes.  excluded (N) uint8, non-zero = excluded; NULL means
+ * dstagnn_graph_topk exactly.  An excluded node is never a neighbour: its key sorts after every
+ * real key (a NaN's included).  An excluded node's own row of A and R is all zero and its nbr
+ * row all -1.  Any other row takes min(k, #eligible columns) neighbours, the eligible columns
+ * being the non-excluded ones (the row's own included, as in dstagnn_graph_topk); the rest of
+ * its nbr row is -1.  Same checks (k <= N, N <= 8192). */
+int dstagnn_graph_topk_masked(const double* sta, int N, int k, int mode, const uint8_t* excluded, double* A,
+                              double* R, int32_t* nbr, dstagnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * GEMM-family profiling (benchmark support).  dstagnn_prof_start(capacity) arms a timing
