@@ -21,6 +21,7 @@ RES_NONE, RES_BCAST, RES_FULL = 0, 1, 2
 # dstagnn::block flags
 F_TRAIN, F_SPARSE, F_DIRECT, F_POISON, F_FLASH = 1, 2, 4, 8, 16
 F_FULL_FWD = 32  # keep the full (backward-state-writing) forward where no autograd node is recorded
+F_FIRST_MULTI = 64  # multi-feature first block: the first block's branches whatever F (1 <= F <= 8)
 
 _ops = None
 

@@ -105,26 +105,28 @@ def cfg_of(meta):
 SAMPLE_SHIFT = 32  # flags bits 32..: the call's first global sample index (torch_ops.cpp kSampleShift)
 
 
-def flags_of(train, sparse, direct, flash=False, sample_base=0, forward_only=True):
+def flags_of(train, sparse, direct, flash=False, sample_base=0, forward_only=True, first_multi=False):
     if sample_base < 0:
         raise ValueError("sample_base must be >= 0")
     return ((_lib.F_TRAIN if train else 0) | (_lib.F_SPARSE if sparse else 0) | (_lib.F_DIRECT if direct else 0)
             | (_lib.F_POISON if _POISON else 0) | (_lib.F_FLASH if flash else 0)
-            | (0 if forward_only else _lib.F_FULL_FWD) | (int(sample_base) << SAMPLE_SHIFT))
+            | (0 if forward_only else _lib.F_FULL_FWD) | (_lib.F_FIRST_MULTI if first_multi else 0)
+            | (int(sample_base) << SAMPLE_SHIFT))
 
 
 def block_call(x, res_att, params, slots, graph, meta, train, seed, direct=False, flash=None, plan_cache=None,
-               sample_base=0, forward_only=True):
+               sample_base=0, forward_only=True, first_multi=False):
     """(out, re_at) = dstagnn::block(...) — autograd-tracked.  In direct-gradient mode with a
     plan_cache dict (the module's), the block's constant arguments go to the library once, as a
     cached BlockPlan (dstagnn::block_planned): same kernels, less host work per call.
     sample_base: global index of x[0] (a data-parallel shard's offset; keys the dropout masks).
-    forward_only=False: a call that records no autograd node still runs the full forward (A/B tools)."""
+    forward_only=False: a call that records no autograd node still runs the full forward (A/B tools).
+    first_multi: a multi-feature first block (the first block's branches whatever x.shape[2])."""
     ops = _lib.load()
     x = x.float().contiguous()
     sparse = use_sparse(graph, meta, x.shape[3])
     fl = use_flash(graph, meta, x.shape[3], flash, x.shape[0])
-    flags = flags_of(train, sparse, direct, fl, sample_base, forward_only)
+    flags = flags_of(train, sparse, direct, fl, sample_base, forward_only, first_multi)
     if direct and plan_cache is not None:
         key = (id(params), id(graph), sparse, fl)
         ent = plan_cache.get("plan")
@@ -162,7 +164,11 @@ def dropout_masks(meta, x_shape, seed, sample_base=0):
 
 # dstagnn_block_paths bits (include/dstagnn.h DSTAGNN_PATH_*)
 PATH_BITS = {"sparse": 1, "flash": 2, "flash_small": 4, "cheb_agg": 8, "tat_fused_fwd": 16, "tat_fused_bwd": 32,
-             "gtu_fused_fwd": 64, "gtu_fused_bwd": 128}
+             "gtu_fused_fwd": 64, "gtu_fused_bwd": 128, "first_multi": 512}
+
+
+def _first_multi(blk):
+    return bool(getattr(blk, "multi_feature", False))
 
 
 def _explicit_args(blk, x, res_att, train=False, seed=0, poison=False):
@@ -173,7 +179,7 @@ def _explicit_args(blk, x, res_att, train=False, seed=0, poison=False):
     fl = use_flash(graph, blk.meta, x.shape[3], blk.flash_cheb, x.shape[0])
     if fl:
         graph = blk._flash_graph(graph)
-    flags = flags_of(train, sparse, False, fl) | (_lib.F_POISON if poison else 0)
+    flags = flags_of(train, sparse, False, fl, first_multi=_first_multi(blk)) | (_lib.F_POISON if poison else 0)
     return (x.detach().float().contiguous(), res_arg(res_att, x.shape[2]), list(ps), slots,
             graph_list(graph, sparse, fl), cfg_of(blk.meta), float(blk.meta.get("drop_p", 0.05)), int(seed), flags)
 
@@ -197,5 +203,6 @@ def block_paths(blk, x, res_att, train=False):
     if fl:
         graph = blk._flash_graph(graph)
     bits = ops.block_paths(x.detach().float().contiguous(), res_arg(res_att, x.shape[2]), list(ps), slots,
-                           graph_list(graph, sparse, fl), cfg_of(blk.meta), 0.05, 0, flags_of(train, sparse, False, fl))
+                           graph_list(graph, sparse, fl), cfg_of(blk.meta), 0.05, 0,
+                           flags_of(train, sparse, False, fl, first_multi=_first_multi(blk)))
     return {n for n, b in PATH_BITS.items() if bits & b}

@@ -52,6 +52,7 @@ struct Dims {
   int64_t FT, BFT, BN, NN, HQ, HV, QW, KD, KC, CT, KCT, S;
   int Tg[3], ks[3];
   bool first, sparse, flash;
+  bool mf;          // multi-feature first block (DSTAGNN_TRAIN_FIRST_MULTI, F > 1): F -> C residual, generic tail
   bool fsmall;      // flash on a small graph (flash_small): the LDS-staged kernels
   bool agg;         // sparse path in aggregate-first order (cheb_agg.hip): no x Theta GEMM
   bool dth;         // ... with dTheta from the transposed SpMM itself: agg_k is not stored
@@ -65,6 +66,10 @@ struct Dims {
   int64_t apa_nnz;  // small-graph flash: A_pa support entries
 };
 
+// dstagnn_block_dims::train is a flag word: the first-block flag, and dropout on any other bit
+bool first_flag(const dstagnn_block_dims& d) { return (d.train & DSTAGNN_TRAIN_FIRST_MULTI) != 0; }
+bool drop_on(const dstagnn_block_dims& d) { return (d.train & ~DSTAGNN_TRAIN_FIRST_MULTI) != 0 && d.drop_p > 0.f; }
+
 Dims mkdims(const dstagnn_block_dims& d) {
   Dims m;
   m.B = d.B; m.N = d.N; m.F = d.F; m.T = d.T; m.h = d.n_heads; m.dk = d.d_k; m.dv = d.d_v;
@@ -73,7 +78,8 @@ Dims mkdims(const dstagnn_block_dims& d) {
   m.HQ = (int64_t)m.h * m.dk; m.HV = (int64_t)m.h * m.dv; m.QW = 2 * m.HQ + m.HV; m.KD = (int64_t)m.K * m.dk;
   m.KC = (int64_t)m.K * m.C; m.CT = (int64_t)m.C * m.T; m.KCT = m.KC * m.T; m.S = 3 * (int64_t)m.T - 12;
   for (int g = 0; g < 3; ++g) { m.ks[g] = 3 + 2 * g; m.Tg[g] = m.T - m.ks[g] + 1; }
-  m.first = (m.F == 1);
+  m.first = first_flag(d) || m.F == 1;
+  m.mf = m.first && m.F > 1;
   m.sparse = d.cheb_sparse != 0;
   m.flash = m.sparse && d.cheb_flash != 0;
   m.nnz = m.flash ? d.cheb_nnz : 0;
@@ -86,8 +92,9 @@ Dims mkdims(const dstagnn_block_dims& d) {
   m.NP = m.tfused ? tat_fused_np(m.N) : 0;
   m.tfused_bwd = m.tfused && tat_fused_bwd_ok(m.N, m.T, m.h, m.dk, m.dv, m.F, d.res_mode);
   m.tf_wg = m.tfused_bwd ? tat_fused_bwd_wgs(m.BFT) : 0;
-  m.gfused = gtu_fused_fwd_ok(m.C, m.T);
-  m.gbfused = gtu_fused_bwd_ok(m.C, m.T);
+  // (a multi-feature first block's F -> C residual lives in the runtime-generic tail kernels only)
+  m.gfused = !m.mf && gtu_fused_fwd_ok(m.C, m.T);
+  m.gbfused = !m.mf && gtu_fused_bwd_ok(m.C, m.T);
   return m;
 }
 
@@ -150,9 +157,9 @@ SaveBufs plan_save(const Dims& m, Arena& a) {
   s.mu_c = a.take(m.BN * m.T);
   s.rs_c = a.take(m.BN * m.T);
   if (m.first) {
-    s.u_et = a.take((int64_t)m.B * m.T * m.N);
-    s.mu_et = a.take((int64_t)m.B * m.T);
-    s.rs_et = a.take((int64_t)m.B * m.T);
+    s.u_et = a.take(m.BFT * m.N);
+    s.mu_et = a.take(m.BFT);
+    s.rs_et = a.take(m.BFT);
   } else {
     s.u_et = s.mu_et = s.rs_et = nullptr;
   }
@@ -182,12 +189,13 @@ Scratch plan_scratch(const Dims& m, Arena& a) {
   s.dWqk = a.take(2 * m.KD * m.D);
   // (the fused GTU backward's ticket-tree rows live here too: at small B they outgrow BN CT)
   s.gcon_t = a.take(m.gbfused ? std::max<int64_t>(m.BN * m.CT, gtu_fused_bwd_part_floats(m.BN)) : m.BN * m.CT);
-  s.bcon_t = a.take(m.BN * m.CT);
+  // (first block: the residual_conv partials [bn][C F] | [bn][C]; they outgrow BN CT where F + 1 > T)
+  s.bcon_t = a.take(std::max<int64_t>(m.BN * m.CT, m.first ? m.BN * m.C * (m.F + 1) : 0));
   s.dres_t = a.take(m.BN * m.CT);
   s.gcon_s = a.take(m.BN * m.D);
   s.bcon_s = a.take(m.BN * m.D);
   s.gcon_a = a.take(m.BFT * m.N);
-  s.gcon_e = m.first ? a.take((int64_t)m.B * m.T * m.N) : nullptr;
+  s.gcon_e = m.first ? a.take(m.BFT * m.N) : nullptr;
   for (int g = 0; g < 3; ++g) s.dconv[g] = a.take((m.BN * m.T + m.ks[g] - 1) * 2 * m.C);  // gtu_tail.hip layout
   s.dW = m.flash ? nullptr : a.take((int64_t)m.B * m.K * m.NN);
   s.dzs = m.flash ? a.take((int64_t)m.B * m.K * m.nnz) : nullptr;
@@ -205,8 +213,8 @@ Scratch plan_scratch(const Dims& m, Arena& a) {
   s.dctx = a.take(m.BFT * m.HV);
   s.dqkv = a.take(m.BFT * m.QW);
   s.dscore = a.take(m.BFT * m.h * m.T);
-  s.du_et = m.first ? a.take((int64_t)m.B * m.T * m.N) : nullptr;
-  s.dGt = gtu_tail_bwd_split(m.C, m.T) ? a.take(m.BN * m.C * m.S) : nullptr;  // long series only
+  s.du_et = m.first ? a.take(m.BFT * m.N) : nullptr;
+  s.dGt = gtu_tail_bwd_split(m.C, m.T, m.first ? m.F : 0) ? a.take(m.BN * m.C * m.S) : nullptr;  // long series only
   return s;
 }
 
@@ -298,7 +306,14 @@ int check_dims(const dstagnn_block_dims* d) {
     return DSTAGNN_E_SHAPE;
   }
   if (d->sample_base < 0) { set_last_error("sample_base < 0"); return DSTAGNN_E_ARG; }
-  if (d->F != 1 && d->F != d->C) {
+  if (first_flag(*d)) {
+    if (d->F > DSTAGNN_MAX_FIRST_F) {
+      set_last_error("multi-feature first block: F = " + std::to_string(d->F) + " exceeds the limit of " +
+                     std::to_string(DSTAGNN_MAX_FIRST_F) + " input features (1 <= F <= " +
+                     std::to_string(DSTAGNN_MAX_FIRST_F) + ")");
+      return DSTAGNN_E_SHAPE;
+    }
+  } else if (d->F != 1 && d->F != d->C) {
     // the reference fails at model/DSTAGNN_my.py:252 (x.permute + time_conv_output)
     set_last_error("The size of tensor a (" + std::to_string(d->F) + ") must match the size of tensor b (" +
                    std::to_string(d->C) + ") at non-singleton dimension 1");
@@ -587,8 +602,9 @@ struct Fwd {
     // E: TAt input (B,F,T,N)
     if (m.first) {
       LnFwd a;
-      a.R = m.B * m.T; a.L = m.N;
-      a.src[0].p = x; a.src[0].row = idx2(m.T, 1, (int64_t)m.N * m.T); a.src[0].es = m.T;
+      // rows (b, f, t): x[b, n, f, t] along n, the position row of t shared by the F features
+      a.R = (int)m.BFT; a.L = m.N;
+      a.src[0].p = x; a.src[0].row = idx2(m.FT, 1, (int64_t)m.N * m.FT); a.src[0].es = m.FT;
       a.src[1].p = p.embT_pos; a.src[1].row = idx2(m.T, m.N, 0); a.src[1].es = 1;
       a.nsrc = 2;
       a.g = p.embT_g; a.b = p.embT_b;
@@ -714,7 +730,7 @@ struct Fwd {
       a.g = p.embS_g; a.b = p.embS_b;
       a.y = s.Zd; a.yrow = idx1(m.D);
       a.u = lean ? nullptr : s.u_s; a.mu = s.mu_s; a.rs = s.rs_s;
-      if (d.train && d.drop_p > 0.f) {
+      if (drop_on(d)) {
         a.drop_p = d.drop_p; a.seed = d.seed; a.which = 0; a.drop_off = drop_off(d, 0);
       }
       DS_TRY(op_ln_fwd(a, st));
@@ -774,7 +790,7 @@ struct Fwd {
       for (int q = 0; q < 3; ++q) { g.wt[q] = s.Wgt[q]; g.bias[q] = p.gtu_b[q]; g.conv[q] = s.conv[q]; }
       g.fcmy_w = p.fcmy_w; g.fcmy_b = p.fcmy_b; g.res_w = p.res_w; g.res_b = p.res_b;
       g.ln_g = p.ln_g; g.ln_b = p.ln_b;
-      if (d.train && d.drop_p > 0.f) { g.drop_p = d.drop_p; g.seed = d.seed; g.drop_off = drop_off(d, 1); }
+      if (drop_on(d)) { g.drop_p = d.drop_p; g.seed = d.seed; g.drop_off = drop_off(d, 1); }
       // G only for the unfused backward's fcmy weight gradient (the fused one recomputes the gates)
       g.G = m.gbfused ? nullptr : s.G;
       g.tco = s.tco; g.r = s.r; g.mu = s.mu_c; g.rs = s.rs_c; g.out = out;
@@ -784,13 +800,13 @@ struct Fwd {
     const Gemm convs[3] = {gtu_conv(0), gtu_conv(1), gtu_conv(2)};
     DS_TRY(run_gemm_group(convs, 3, w.gemm_ws, kGemmWs, st));
     GtuTailArgs t;  // gates + fcmy + dropout + residual + LN, one workgroup per node
-    t.BN = m.BN; t.C = m.C; t.T = m.T; t.first = m.first;
+    t.BN = m.BN; t.C = m.C; t.T = m.T; t.first = m.first; t.F = m.first ? m.F : 1;
     for (int q = 0; q < 3; ++q) t.conv[q] = s.conv[q];
     t.fcmy_w = p.fcmy_w; t.fcmy_b = p.fcmy_b;
     t.X = s.X; t.x = x; t.res_w = p.res_w; t.res_b = p.res_b; t.ln_g = p.ln_g; t.ln_b = p.ln_b;
-    if (d.train && d.drop_p > 0.f) { t.drop_p = d.drop_p; t.seed = d.seed; t.drop_off = drop_off(d, 1); }
+    if (drop_on(d)) { t.drop_p = d.drop_p; t.seed = d.seed; t.drop_off = drop_off(d, 1); }
     t.G = s.G; t.tco = s.tco; t.r = s.r; t.mu = s.mu_c; t.rs = s.rs_c; t.out = out;
-    if (lean && gtu_tail_fwd_split(m.C, m.T)) {
+    if (lean && gtu_tail_fwd_split(m.C, m.T, m.first ? m.F : 0)) {
       // forward-only, split tail: G in the main GEMM workspace (idle since the convolutions), as
       // many nodes at a time as fit it; the fcmy GEMM's output passes through the out buffer (a
       // workgroup of the tail kernel reads its node's values before it stores that node's
@@ -803,7 +819,7 @@ struct Fwd {
         c.BN = std::min(nb, m.BN - bn0);
         for (int q = 0; q < 3; ++q) c.conv[q] = t.conv[q] + bn0 * m.Tg[q] * 2 * m.C;
         c.X = t.X + bn0 * m.CT;
-        c.x = t.x + bn0 * (m.first ? (int64_t)m.T : m.CT);
+        c.x = t.x + bn0 * (m.first ? m.FT : m.CT);
         c.drop_off = t.drop_off + (uint64_t)(bn0 * m.CT);
         c.out = out + bn0 * m.CT;
         c.tco = c.out;
@@ -940,7 +956,7 @@ struct Bwd {
     g.dout = dout; g.r = s.r; g.tco = s.tco; g.mu = s.mu_c; g.rs = s.rs_c; g.x = x; g.X = s.X;
     for (int q = 0; q < 3; ++q) { g.conv[q] = s.conv[q]; g.wf[q] = s.Wgf[q]; g.dconv[q] = w.dconv[q]; }
     g.fcmy_w = p.fcmy_w; g.ln_g = p.ln_g; g.res_w = p.res_w;
-    if (d.train && d.drop_p > 0.f) { g.drop_p = d.drop_p; g.seed = d.seed; g.drop_off = drop_off(d, 1); }
+    if (drop_on(d)) { g.drop_p = d.drop_p; g.seed = d.seed; g.drop_off = drop_off(d, 1); }
     g.dx = dx; g.gpre = w.gpre;
     // the LN / residual_conv / fcmy parameter gradients summed in-kernel (ticket tree over
     // per-workgroup rows in gcon_t): no column sums on the side stream
@@ -960,18 +976,18 @@ struct Bwd {
   int stage_tail() {
     if (m.gbfused) return stage_tail_fused();
     GtuTailArgs t;  // LN / residual backward -> dtc -> dG = dtc W -> gates backward, per node
-    t.BN = m.BN; t.C = m.C; t.T = m.T; t.first = m.first;
+    t.BN = m.BN; t.C = m.C; t.T = m.T; t.first = m.first; t.F = m.first ? m.F : 1;
     for (int q = 0; q < 3; ++q) { t.conv[q] = s.conv[q]; t.dconv_pad[q] = w.dconv[q]; }
     t.fcmy_w = p.fcmy_w;
     t.X = s.X; t.x = x; t.res_w = p.res_w; t.res_b = p.res_b; t.ln_g = p.ln_g; t.ln_b = p.ln_b;
-    if (d.train && d.drop_p > 0.f) { t.drop_p = d.drop_p; t.seed = d.seed; t.drop_off = drop_off(d, 1); }
+    if (drop_on(d)) { t.drop_p = d.drop_p; t.seed = d.seed; t.drop_off = drop_off(d, 1); }
     t.tco = s.tco; t.r = s.r; t.mu = s.mu_c; t.rs = s.rs_c;
     t.dout = dout; t.gcontrib = w.gcon_t; t.dtc = w.dtc; t.dX = w.dX; t.dx = dx;
     t.rcontrib = w.bcon_t; t.dres = w.dres_t; t.dG = w.dGt;
     // per-node [bn][C] partial sums of the LN gamma / beta (and first-block residual_conv)
     // contributions instead of the (B,N,C,T) tensors: the column sums below read BN*C floats
     t.gpart = w.gcon_t; t.bpart = w.gcon_t + m.BN * m.C;
-    if (m.first) { t.rpart = w.bcon_t; t.dpart = w.bcon_t + m.BN * m.C; }
+    if (m.first) { t.rpart = w.bcon_t; t.dpart = w.bcon_t + m.BN * m.C * m.F; }
     // the LN gamma / beta (and residual_conv) sums folded in-kernel where the compile-time tail
     // runs (no colsum2d launch on the side stream); level-2 rows after the partials in gcon_t
     const bool tail_fold = gtu_tail_bwd_folds(t);
@@ -1012,7 +1028,11 @@ struct Bwd {
       }
       return run_gemm_kcat(segs, 3, st, sig);
     }));
-    if (!tail_fold)
+    if (!tail_fold && m.mf) {  // residual_conv.weight (C, F): its own shape, its own column sum
+      DS_TRY(colsums({{w.gcon_t, gd.ln_g}, {w.gcon_t + m.BN * m.C, gd.ln_b}, {w.bcon_t + m.BN * m.C * m.F, gd.res_b}},
+                     m.BN, m.C, 1));
+      DS_TRY(colsums({{w.bcon_t, gd.res_w}}, m.BN, m.C * m.F, 1));
+    } else if (!tail_fold)
       DS_TRY(colsums({{w.gcon_t, gd.ln_g}, {w.gcon_t + m.BN * m.C, gd.ln_b}, {w.bcon_t, m.first ? gd.res_w : nullptr},
                       {w.bcon_t + m.BN * m.C, m.first ? gd.res_b : nullptr}}, m.BN, m.C, 1));
     return stage_tail_wgrads(false);
@@ -1231,7 +1251,7 @@ struct Bwd {
       a.R = (int)m.BN; a.L = m.D;
       a.dy = w.dZd; a.dyrow = idx1(m.D);
       a.u = s.u_s; a.mu = s.mu_s; a.rs = s.rs_s; a.g = p.embS_g;
-      if (d.train && d.drop_p > 0.f) {
+      if (drop_on(d)) {
         a.drop_p = d.drop_p; a.seed = d.seed; a.which = 0; a.drop_off = drop_off(d, 0);
       }
       a.dx = w.dY; a.dxrow = idx1(m.D);
@@ -1336,21 +1356,22 @@ struct Bwd {
   int embedT_backward() {
     const int64_t N = m.N;
     LnBwd a;
-    a.R = m.B * m.T; a.L = m.N;
+    a.R = (int)m.BFT; a.L = m.N;  // rows (b, f, t)
     a.dy = w.dE; a.dyrow = idx1(N);
     a.u = s.u_et; a.mu = s.mu_et; a.rs = s.rs_et; a.g = p.embT_g;
     a.dx = w.du_et; a.dxrow = idx1(N);
-    const int64_t pb = ln_bwd_part_blocks((int64_t)m.B * m.T);
-    const bool part = ln_bwd_partials_ok(m.N) && 2 * pb <= (int64_t)m.B * m.T;
+    const int64_t pb = ln_bwd_part_blocks(m.BFT);
+    const bool part = ln_bwd_partials_ok(m.N) && 2 * pb <= m.BFT;
     if (part) { a.gpart = w.gcon_e; a.bpart = w.gcon_e + pb * N; }
     else a.gcontrib = w.gcon_e;
     DS_TRY(op_ln_bwd(a, st));
     DS_TRY(fork());
     if (part) DS_TRY(colsums({{w.gcon_e, gd.embT_g}, {w.gcon_e + pb * N, gd.embT_b}}, pb, m.N, 1));
-    else DS_TRY(colsums({{w.gcon_e, gd.embT_g}, {w.dE, gd.embT_b}}, (int64_t)m.B * m.T, m.N, 1));
-    if (gd.embT_pos) DS_TRY(op_sum_middle(w.du_et, 1, m.B, (int64_t)m.T * m.N, gd.embT_pos, 0.f, ks.side()));
+    else DS_TRY(colsums({{w.gcon_e, gd.embT_g}, {w.dE, gd.embT_b}}, m.BFT, m.N, 1));
+    // the position gradient: summed over b and f (one row per t serves the F features)
+    if (gd.embT_pos) DS_TRY(op_sum_middle(w.du_et, 1, m.B * m.F, (int64_t)m.T * m.N, gd.embT_pos, 0.f, ks.side()));
     DS_TRY(wait_side(dx_ready));  // dx += the Chebyshev-path gradient (side stream) first
-    return op_transpose(w.du_et, dx, m.T, m.N, m.B, (int64_t)m.T * m.N, (int64_t)m.N * m.T, 1.f, st);
+    return op_transpose(w.du_et, dx, (int)m.FT, m.N, m.B, m.FT * m.N, (int64_t)m.N * m.FT, 1.f, st);
   }
 
   int stage_tat() {
@@ -1576,7 +1597,8 @@ int dstagnn_block_paths(const dstagnn_block_dims* d, uint32_t* bits) {
   *bits = (m.sparse ? DSTAGNN_PATH_SPARSE : 0u) | (m.flash ? DSTAGNN_PATH_FLASH : 0u) |
           (m.fsmall ? DSTAGNN_PATH_FLASH_SMALL : 0u) | (m.agg ? DSTAGNN_PATH_CHEB_AGG : 0u) |
           (m.tfused ? DSTAGNN_PATH_TAT_FUSED_FWD : 0u) | (m.tfused_bwd ? DSTAGNN_PATH_TAT_FUSED_BWD : 0u) |
-          (m.gfused ? DSTAGNN_PATH_GTU_FUSED_FWD : 0u) | (m.gbfused ? DSTAGNN_PATH_GTU_FUSED_BWD : 0u);
+          (m.gfused ? DSTAGNN_PATH_GTU_FUSED_FWD : 0u) | (m.gbfused ? DSTAGNN_PATH_GTU_FUSED_BWD : 0u) |
+          (m.mf ? DSTAGNN_PATH_FIRST_MULTI : 0u);
   return 0;
 }
 

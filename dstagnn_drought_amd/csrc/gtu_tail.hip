@@ -95,6 +95,23 @@ __device__ __forceinline__ float fast_tanh(float x) {
 constexpr int kNT = 64;
 constexpr int kU = 8;
 
+// n floats from global memory into LDS, a chunk's kU loads per lane issued before its LDS stores
+// (one memory round trip per NT * kU floats, not one per element)
+template <int NT>
+__device__ __forceinline__ void stage_floats(float* dst, const float* src, int n, int tid) {
+  #pragma unroll 1
+  for (int e0 = 0; e0 < n; e0 += NT * kU) {
+    float v[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) v[u] = src[min(e0 + tid + NT * u, n - 1)];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int e = e0 + tid + NT * u;
+      if (e < n) dst[e] = v[u];
+    }
+  }
+}
+
 // WL: the fcmy
 // weight (T x 3T-12) staged in LDS; false for long series (GAMBIA T=144: 242 KB), where
 // it is read through L1/L2 instead.
@@ -107,13 +124,16 @@ constexpr int kU = 8;
 
 // LDS layout (floats), shared by the kernel and the host size computation
 struct TailFwdLds {
-  int SP, CP, P, gs, rl, xs, red, mus, rss, wl, total;
-  __host__ __device__ TailFwdLds(int C, int T, bool stage_w, bool has_g = true, int nt = kNT) {
+  int SP, CP, P, gs, rl, xs, red, mus, rss, wl, xf, rw, total;
+  // nf: the feature count of a multi-feature first block (MF kernels), else 0: the node's (F, T)
+  // inputs and the (C, F) residual_conv weight after everything else (no other offset moves)
+  __host__ __device__ TailFwdLds(int C, int T, bool stage_w, bool has_g = true, int nt = kNT, int nf = 0) {
     const int S = 3 * T - 12;
     SP = S + 1; CP = C + 1; P = T < nt ? nt / T : 1;
     gs = 0; rl = gs + (has_g ? C * SP : 0); xs = rl + C * T; red = xs + T * CP;
     mus = red + (P * T > nt ? P * T : nt); rss = mus + T; wl = rss + T;
-    total = wl + (stage_w ? T * SP : 0);
+    xf = wl + (stage_w ? T * SP : 0); rw = xf + nf * T;
+    total = rw + C * nf;
   }
 };
 
@@ -140,11 +160,16 @@ __device__ __forceinline__ void col_sums_over_c(const float* v, int C, int T, in
 // in gtu_gates_kernel).  SAVE = false (the forward-only block): no store of G, tco, r, mu or rs
 // (PH == 2 still reads the GEMM's tc through a.tco, which may then be the out buffer itself: a
 // workgroup reads its node's tc before the barriers that precede its out stores)
-template <bool WL, int PH = 0, int NT = kNT, bool SAVE = true>
+// MF (multi-feature first block, a.first with a.F > 1): the residual is the 1x1 convolution
+// xres[c, t] = b[c] + sum_f W[c, f] x[f, t] (f ascending, one fma each) from LDS — the (C, F)
+// weight staged once per workgroup, the node's (F, T) inputs once per node; the MF = false
+// forms hold none of it (the F = 1 and inner-block code is what it was).
+template <bool WL, int PH = 0, int NT = kNT, bool SAVE = true, bool MF = false>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 8))) void gtu_tail_fwd_kernel(GtuTailArgs a) {
   extern __shared__ float lds[];
   const int C = a.C, T = a.T, S = 3 * T - 12, CT = C * T, C2 = 2 * C, CS = C * S;
-  const TailFwdLds L(C, T, WL, PH != 2, NT);
+  const int F = MF ? a.F : 1, FT = F * T;
+  const TailFwdLds L(C, T, WL, PH != 2, NT, MF ? F : 0);
   const int SP = L.SP, CP = L.CP;
   float* Gs = lds + L.gs;    // [c][SP]
   float* rl = lds + L.rl;    // [c][t]
@@ -153,13 +178,17 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 8))) void
   float* mus = lds + L.mus;
   float* rss = lds + L.rss;
   float* Wl = lds + L.wl;    // [t][SP] (WL only)
+  float* xf = lds + L.xf;    // [f][t] (MF only)
+  float* Wr = lds + L.rw;    // [c][f] (MF only)
   const float* Ws = WL ? Wl : a.fcmy_w;
   const int WS = WL ? SP : S;
   const int tid = threadIdx.x;
   if (WL)
     for (int e = tid; e < T * S; e += NT) Wl[(e / S) * SP + e % S] = a.fcmy_w[e];
+  if (MF) stage_floats<NT>(Wr, a.res_w, C * F, tid);
   for (int64_t bn = blockIdx.x; bn < a.BN; bn += gridDim.x) {
     const int64_t base = bn * CT;
+    if (MF) stage_floats<NT>(xf, a.x + bn * FT, FT, tid);  // the node's F input rows (read behind the barrier below)
     // gates, element (s, c) with c fastest: coalesced conv-row reads
     #pragma unroll 1
     for (int e0 = 0; e0 < (PH == 2 ? 0 : CS); e0 += NT * kU) {
@@ -199,7 +228,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 8))) void
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
         const int e = min(e0 + tid + NT * u, CT - 1);
-        xv[u] = a.first ? a.x[bn * T + e % T] : a.x[base + e];
+        xv[u] = MF ? 0.f : (a.first ? a.x[bn * T + e % T] : a.x[base + e]);
         if (PH == 2) tcv[u] = a.tco[base + e];  // fcmy output (bias included) from the GEMM
       }
 #pragma unroll 1
@@ -218,7 +247,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 8))) void
         }
         if (a.drop_p > 0.f) tc *= drop_scale(a.seed, 1, (uint64_t)(base + e) + a.drop_off, a.drop_p);
         float tco, xres;
-        if (a.first) {
+        if (MF) {
+          tco = fmaxf(tc, 0.f);
+          xres = a.res_b[c];
+          for (int f = 0; f < F; ++f) xres = fmaf(Wr[c * F + f], xf[f * T + t], xres);
+        } else if (a.first) {
           tco = fmaxf(tc, 0.f);
           xres = a.res_w[c] * xv[u] + a.res_b[c];
         } else {
@@ -367,8 +400,8 @@ __global__ __launch_bounds__(256) void gtu_gates_bwd_kernel(GtuTailArgs a, int n
 
 // dG, the dX tile and the LN reduction scratch share one region (disjoint phases)
 struct TailBwdLds {
-  int SP, CP, P, dxh, xhl, rr, dg, dxs, red, s1, s2, wl, total;
-  __host__ __device__ TailBwdLds(int C, int T, bool stage_w, bool has_g = true, int nt = kNT) {
+  int SP, CP, P, dxh, xhl, rr, dg, dxs, red, s1, s2, wl, xf, rw, total;
+  __host__ __device__ TailBwdLds(int C, int T, bool stage_w, bool has_g = true, int nt = kNT, int nf = 0) {  // nf: as TailFwdLds
     const int S = 3 * T - 12, CT = C * T;
     SP = S + 1; CP = C + 1; P = T < nt ? nt / T : 1;
     const int nred = 2 * (P * T > nt ? P * T : nt);
@@ -376,7 +409,8 @@ struct TailBwdLds {
     if (T * CP > shared) shared = T * CP;
     if (nred > shared) shared = nred;
     dxh = 0; xhl = dxh + CT; rr = xhl + CT; dg = rr + CT; dxs = dg; red = dg; s1 = dg + shared; s2 = s1 + T; wl = s2 + T;
-    total = wl + (stage_w ? T * S : 0);
+    xf = wl + (stage_w ? T * S : 0); rw = xf + nf * T;
+    total = rw + C * nf;
   }
 };
 
@@ -384,11 +418,15 @@ struct TailBwdLds {
 
 // PH: 0 = fused, 1 = split path: LN / residual backward to dtc only (dG by a GEMM, the
 // gates backward in gtu_gates_bwd_kernel)
-template <bool WL, int PH = 0, int NT = kNT>
+// MF (multi-feature first block; needs a.rpart / a.dpart): with dr = d xres in LDS,
+// dx[f, t] = sum_c W[c, f] dr[c, t] (c ascending), the per-node partials rpart[bn][c F + f] =
+// sum_t dr[c, t] x[f, t] (t ascending; the layout of residual_conv.weight (C, F)) and dpart[bn][c]
+template <bool WL, int PH = 0, int NT = kNT, bool MF = false>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 8))) void gtu_tail_bwd_kernel(GtuTailArgs a) {
   extern __shared__ float lds[];
   const int C = a.C, T = a.T, S = 3 * T - 12, CT = C * T, C2 = 2 * C;
-  const TailBwdLds L(C, T, WL, PH == 0, NT);
+  const int F = MF ? a.F : 1, FT = F * T;
+  const TailBwdLds L(C, T, WL, PH == 0, NT, MF ? F : 0);
   const int SP = L.SP, CP = L.CP;
   float* dxh = lds + L.dxh;   // CT  (LN dxhat, then dtc)
   float* xhl = lds + L.xhl;   // CT
@@ -399,12 +437,16 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 8))) void
   float* dXs = lds + L.dxs;   // [t][CP] (dX tile, written to HBM coalesced)
   float* red = lds + L.red;
   float* Wl = lds + L.wl;     // T*S (WL only)
+  float* xf = lds + L.xf;     // [f][t] (MF only)
+  float* Wr = lds + L.rw;     // [c][f] (MF only)
   const float* Ws = WL ? Wl : a.fcmy_w;
   const int tid = threadIdx.x;
   if (WL)
     for (int e = tid; e < T * S; e += NT) Wl[e] = a.fcmy_w[e];
+  if (MF) stage_floats<NT>(Wr, a.res_w, C * F, tid);
   for (int64_t bn = blockIdx.x; bn < a.BN; bn += gridDim.x) {
     const int64_t base = bn * CT;
+    if (MF) stage_floats<NT>(xf, a.x + bn * FT, FT, tid);  // the node's F input rows (read behind the barriers below)
     const float* mu = a.mu + bn * T;
     const float* rsv = a.rs + bn * T;
     // LayerNorm over C backward
@@ -470,7 +512,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 8))) void
         const int t = e % T;
         tcov[u] = a.tco[base + e];
 
-        xv[u] = a.first ? a.x[bn * T + t] : 0.f;
+        xv[u] = (!MF && a.first) ? a.x[bn * T + t] : 0.f;
         rsw[u] = rsv[t];
       }
 #pragma unroll
@@ -486,7 +528,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 8))) void
         a.dtc[base + e] = dtc;
         if (a.first) {
           dXs[t * CP + c] = 0.f;
-          if (!a.rpart) {
+          if (!MF && !a.rpart) {
             a.rcontrib[base + e] = dr * xv[u];
             a.dres[base + e] = dr;
           }
@@ -501,7 +543,25 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 8))) void
     __syncthreads();
     for (int e = tid; e < CT; e += NT) a.dX[base + e] = dXs[(e / C) * CP + e % C];  // coalesced
     __syncthreads();  // dXs shares its LDS with dGs
-    if (a.first) {
+    if (MF) {
+      for (int i = tid; i < FT; i += NT) {  // dx[f][t]: lanes along t (conflict-free LDS rows)
+        const int f = i / T, t = i - f * T;
+        float sum = 0.f;
+        for (int c = 0; c < C; ++c) sum = fmaf(Wr[c * F + f], xhl[c * T + t], sum);
+        a.dx[bn * FT + i] = sum;
+      }
+      for (int i = tid; i < C * F; i += NT) {  // residual_conv.weight partials, (c, f) order
+        const int c = i / F, f = i - c * F;
+        float rw = 0.f;
+        for (int t = 0; t < T; ++t) rw = fmaf(xhl[c * T + t], xf[f * T + t], rw);
+        a.rpart[bn * (int64_t)(C * F) + i] = rw;
+      }
+      for (int c = tid; c < C; c += NT) {
+        float rb = 0.f;
+        for (int t = 0; t < T; ++t) rb += xhl[c * T + t];
+        a.dpart[bn * C + c] = rb;
+      }
+    } else if (a.first) {
       for (int t = tid; t < T; t += NT) {
         float sum = 0.f;
         for (int c = 0; c < C; ++c) sum += a.res_w[c] * xhl[c * T + t];
@@ -928,11 +988,22 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 8))) void
   }
 }
 
+// a multi-feature first block (the MF kernel forms)
+bool tail_mf(const GtuTailArgs& a) { return a.first && a.F > 1; }
 size_t fwd_lds(const GtuTailArgs& a, bool wl, bool has_g = true, int nt = kNT) {
-  return sizeof(float) * (size_t)TailFwdLds(a.C, a.T, wl, has_g, nt).total;
+  return sizeof(float) * (size_t)TailFwdLds(a.C, a.T, wl, has_g, nt, tail_mf(a) ? a.F : 0).total;
 }
 size_t bwd_lds(const GtuTailArgs& a, bool wl, bool has_g = true, int nt = kNT) {
-  return sizeof(float) * (size_t)TailBwdLds(a.C, a.T, wl, has_g, nt).total;
+  return sizeof(float) * (size_t)TailBwdLds(a.C, a.T, wl, has_g, nt, tail_mf(a) ? a.F : 0).total;
+}
+// which path a shape takes (fused or split) does not depend on F: the F = 1 layout decides
+size_t fwd_lds_f1(const GtuTailArgs& a) { return sizeof(float) * (size_t)TailFwdLds(a.C, a.T, true).total; }
+size_t bwd_lds_f1(const GtuTailArgs& a) { return sizeof(float) * (size_t)TailBwdLds(a.C, a.T, true).total; }
+int check_mf(const GtuTailArgs& a, bool bwd) {
+  if (!tail_mf(a)) return 0;
+  if (a.F > DSTAGNN_MAX_FIRST_F) { set_last_error("gtu_tail: multi-feature first block with F > DSTAGNN_MAX_FIRST_F"); return DSTAGNN_E_SHAPE; }
+  if (bwd && (!a.rpart || !a.dpart)) { set_last_error("gtu_tail: the multi-feature backward needs rpart / dpart"); return DSTAGNN_E_ARG; }
+  return 0;
 }
 
 unsigned node_grid(int64_t BN) { return (unsigned)std::min<int64_t>(BN, 65536); }
@@ -977,17 +1048,19 @@ constexpr int kTailSplitT = 20;
 // tools/gpu_check.sh cfgab); DSTAGNN_TAIL_CT24=0 keeps the split path (A/B)
 static bool tail_ct24(const GtuTailArgs& a) {
   static const bool on = env_flag("DSTAGNN_TAIL_CT24", true);
-  return on && a.C == 32 && a.T == 24;
+  return on && a.C == 32 && a.T == 24 && !tail_mf(a);
 }
-// the one-round-of-loads compile-time kernels: C = 32 at T = 12 (and T = 24, tail_ct24)
-static bool tail_ct(const GtuTailArgs& a) { return tail_ct24(a) || (a.C == 32 && a.T == 12); }
+// the one-round-of-loads compile-time kernels: C = 32 at T = 12 (and T = 24, tail_ct24); never a
+// multi-feature first block, whose F -> C residual only the runtime-generic kernels hold: at
+// T = 12 it takes gtu_tail_*_kernel<true, 0, 64, ., MF>, at T = 24 the split path
+static bool tail_ct(const GtuTailArgs& a) { return !tail_mf(a) && (tail_ct24(a) || (a.C == 32 && a.T == 12)); }
 bool tail_split_fwd(const GtuTailArgs& a) {
   if (tail_ct24(a)) return false;
-  return fwd_lds(a, true) > 32 * 1024 || a.T >= kTailSplitT;
+  return fwd_lds_f1(a) > 32 * 1024 || a.T >= kTailSplitT;
 }
 bool tail_split_bwd(const GtuTailArgs& a) {
   if (tail_ct24(a)) return false;
-  return bwd_lds(a, true) > 32 * 1024 || a.T >= kTailSplitT;
+  return bwd_lds_f1(a) > 32 * 1024 || a.T >= kTailSplitT;
 }
 
 // threads per node in the split path's residual / LayerNorm kernels: a long series' node
@@ -995,15 +1068,15 @@ bool tail_split_bwd(const GtuTailArgs& a) {
 // threads each keep 8 waves per CU in flight instead of 2
 constexpr int kSplitNT = 256;
 
-bool gtu_tail_fwd_split(int C, int T) {
+bool gtu_tail_fwd_split(int C, int T, int first_F) {
   GtuTailArgs a;
-  a.C = C; a.T = T;
+  a.C = C; a.T = T; a.first = first_F > 0; a.F = first_F > 0 ? first_F : 1;
   return tail_split_fwd(a);
 }
 
-bool gtu_tail_bwd_split(int C, int T) {
+bool gtu_tail_bwd_split(int C, int T, int first_F) {
   GtuTailArgs a;
-  a.C = C; a.T = T;
+  a.C = C; a.T = T; a.first = first_F > 0; a.F = first_F > 0 ? first_F : 1;
   return tail_split_bwd(a);
 }
 
@@ -1022,7 +1095,8 @@ static void launch_tail_ct(const GtuTailArgs& a, bool save, hipStream_t st) {
 int op_gtu_tail_fwd(const GtuTailArgs& a, hipStream_t st) {
   // forward-only (r null): none of the saved-for-backward outputs is written, so all of them
   // must be null — but for the split path's G and tc (a.tco), which its own GEMM reads
-  const bool save = a.r != nullptr;
+  DS_TRY(check_mf(a, false));
+  const bool save = a.r != nullptr, mf = tail_mf(a);
   const bool split = tail_split_fwd(a);
   if (save ? (!a.G || !a.tco || !a.mu || !a.rs) : (a.mu || a.rs || (split ? (!a.G || !a.tco) : (a.G || a.tco)))) {
     set_last_error("gtu_tail_fwd: saved outputs must be all set, or null for the forward-only form");
@@ -1041,6 +1115,10 @@ int op_gtu_tail_fwd(const GtuTailArgs& a, hipStream_t st) {
     }
     DS_TRY(rows_gemm(a.G, S, a.fcmy_w, idx1(1), idx1(S), a.tco, a.T, a.BN * a.C, a.T, S, a.fcmy_b, st));
     const size_t lds = fwd_lds(a, false, false, kSplitNT);
+    if (mf) {
+      if (save) return launch_node_kernel(gtu_tail_fwd_kernel<false, 2, kSplitNT, true, true>, lds, a, st, kSplitNT);
+      return launch_node_kernel(gtu_tail_fwd_kernel<false, 2, kSplitNT, false, true>, lds, a, st, kSplitNT);
+    }
     if (save) return launch_node_kernel(gtu_tail_fwd_kernel<false, 2, kSplitNT>, lds, a, st, kSplitNT);
     return launch_node_kernel(gtu_tail_fwd_kernel<false, 2, kSplitNT, false>, lds, a, st, kSplitNT);
   }
@@ -1049,6 +1127,10 @@ int op_gtu_tail_fwd(const GtuTailArgs& a, hipStream_t st) {
     else launch_tail_ct<12>(a, save, st);
     DS_CHECK_LAUNCH();
     return 0;
+  }
+  if (mf) {
+    if (save) return launch_node_kernel(gtu_tail_fwd_kernel<true, 0, kNT, true, true>, fwd_lds(a, true), a, st);
+    return launch_node_kernel(gtu_tail_fwd_kernel<true, 0, kNT, false, true>, fwd_lds(a, true), a, st);
   }
   if (save) return launch_node_kernel(gtu_tail_fwd_kernel<true>, fwd_lds(a, true), a, st);
   return launch_node_kernel(gtu_tail_fwd_kernel<true, 0, kNT, false>, fwd_lds(a, true), a, st);
@@ -1065,7 +1147,9 @@ bool gtu_tail_bwd_folds(const GtuTailArgs& a) {
 }
 
 int op_gtu_tail_bwd(const GtuTailArgs& a0, hipStream_t st) {
+  DS_TRY(check_mf(a0, true));
   GtuTailArgs a = a0;
+  const bool mf = tail_mf(a0);
   a.fold = a0.fold && gtu_tail_bwd_folds(a0) && a0.fold_ws;
   if (a.fold) {
     a.fold_cnt = stream_counters(st, (int)cdiv64(std::min<int64_t>(a.BN, kTailFoldWgs), 64) + 1);
@@ -1075,7 +1159,8 @@ int op_gtu_tail_bwd(const GtuTailArgs& a0, hipStream_t st) {
     if (!a.dG) { set_last_error("gtu_tail: split backward needs the dG scratch"); return DSTAGNN_E_ARG; }
     const int S = 3 * a.T - 12;
     if (bwd_lds(a, false, false) > kLdsMax) { set_last_error("gtu_tail: C*T too large for LDS"); return DSTAGNN_E_SHAPE; }
-    DS_TRY(launch_node_kernel(gtu_tail_bwd_kernel<false, 1, kSplitNT>, bwd_lds(a, false, false, kSplitNT), a, st, kSplitNT));
+    if (mf) DS_TRY(launch_node_kernel(gtu_tail_bwd_kernel<false, 1, kSplitNT, true>, bwd_lds(a, false, false, kSplitNT), a, st, kSplitNT));
+    else DS_TRY(launch_node_kernel(gtu_tail_bwd_kernel<false, 1, kSplitNT>, bwd_lds(a, false, false, kSplitNT), a, st, kSplitNT));
     DS_TRY(rows_gemm(a.dtc, a.T, a.fcmy_w, idx1(S), idx1(1), a.dG, S, a.BN * a.C, S, a.T, nullptr, st));
     const int nchunk = (a.T + 6 + kGsW - 1) / kGsW;  // rows of the longest padded output (ks = 7)
     const int64_t nwg = a.BN * 3 * nchunk;
@@ -1103,5 +1188,6 @@ int op_gtu_tail_bwd(const GtuTailArgs& a0, hipStream_t st) {
     DS_CHECK_LAUNCH();
     return 0;
   }
+  if (mf) return launch_node_kernel(gtu_tail_bwd_kernel<true, 0, kNT, true>, bwd_lds(a, true), a, st);
   return launch_node_kernel(gtu_tail_bwd_kernel<true>, bwd_lds(a, true), a, st);
 }

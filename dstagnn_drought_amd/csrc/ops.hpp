@@ -108,6 +108,7 @@ struct ParamPrep {
 // fused per-node GTU gates + fcmy + dropout + residual + LayerNorm (gtu_tail.hip)
 struct GtuTailArgs {
   int64_t BN = 0; int C = 0, T = 0; int first = 0;
+  int F = 1;                      // first block: the input's feature count (> 1: multi-feature, x (BN, F, T), res_w (C, F))
   const float* conv[3] = {};      // GTU conv outputs [bn][T-ks+1][2C] (bias included)
   const float* fcmy_w = nullptr;  // (T, 3T-12)
   const float* fcmy_b = nullptr;  // (T)
@@ -369,9 +370,11 @@ int op_pack_rows(const PackRows& a, hipStream_t st);
 int op_gtu_tail_fwd(const GtuTailArgs& a, hipStream_t st);
 int op_gtu_tail_bwd(const GtuTailArgs& a, hipStream_t st);
 // true when the backward runs split (LN | dG GEMM | gates) and needs GtuTailArgs::dG
-bool gtu_tail_bwd_split(int C, int T);
+// (first_F: the feature count of a first block, 0 for an inner block: a multi-feature first
+// block at C = 32, T = 24 takes the split path, not the compile-time kernels)
+bool gtu_tail_bwd_split(int C, int T, int first_F = 0);
 // true when the forward runs split (gates | fcmy GEMM | tail): G and tc (GtuTailArgs::tco) are
 // then intermediates of the forward itself
-bool gtu_tail_fwd_split(int C, int T);
+bool gtu_tail_fwd_split(int C, int T, int first_F = 0);
 int op_param_prep(const ParamPrep& a, hipStream_t st);
 int op_dropout_mask(float* out, int64_t n, uint64_t seed, uint32_t which, float p, uint64_t off, hipStream_t st);

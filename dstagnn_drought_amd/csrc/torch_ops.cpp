@@ -79,16 +79,17 @@ at::TensorOptions f32(const Tensor& like) { return like.options().dtype(at::kFlo
 constexpr int kSlots = 16 + 2 * DSTAGNN_MAX_K + 3 + 3 + 6;
 static_assert(sizeof(dstagnn_block_params) == kSlots * sizeof(void*), "params struct layout");
 static_assert(sizeof(dstagnn_block_grads) == kSlots * sizeof(void*), "grads struct layout");
-// slots of the parameters an INNER block (F != 1) never uses (EmbedT, residual_conv:
+// slots of the parameters an INNER block (F != 1, no first-block flag) never uses (EmbedT, residual_conv:
 // quirk 11, their .grad stays None)
 bool unused_inner(int64_t slot) { return slot == 2 || slot == 3 || slot == 4 || slot == 38 || slot == 39; }
 
 // cfg = [n_heads, d_k, d_v, d_model, K, C]; flags: 1 train, 2 sparse, 4 direct grads, 8 poison,
 // 16 fused (flash) Chebyshev attention, 32 full forward (save / scratch written) even where no
-// autograd node is recorded (DSTAGNN_block.forward_only = False; A/B tools); bits 32.. carry the
+// autograd node is recorded (DSTAGNN_block.forward_only = False; A/B tools), 64 multi-feature
+// first block (DSTAGNN_TRAIN_FIRST_MULTI: the first block's branches whatever F); bits 32.. carry the
 // call's first global sample index (dstagnn_block_dims::sample_base: a data-parallel shard's
 // offset, keys the dropout masks)
-enum { kTrain = 1, kSparse = 2, kDirect = 4, kPoison = 8, kFlash = 16, kFullFwd = 32 };
+enum { kTrain = 1, kSparse = 2, kDirect = 4, kPoison = 8, kFlash = 16, kFullFwd = 32, kFirstMulti = 64 };
 constexpr int kSampleShift = 32;
 
 int res_mode_of(const c10::optional<Tensor>& res, int64_t F) {
@@ -130,7 +131,7 @@ BlockCall make_call(const Tensor& x, const c10::optional<Tensor>& res, at::Tenso
   d.n_heads = (int)cfg[0]; d.d_k = (int)cfg[1]; d.d_v = (int)cfg[2]; d.d_model = (int)cfg[3]; d.K = (int)cfg[4];
   d.C = (int)cfg[5];
   d.res_mode = c.mode;
-  d.train = (flags & kTrain) ? 1 : 0;
+  d.train = ((flags & kTrain) ? DSTAGNN_TRAIN_DROPOUT : 0) | ((flags & kFirstMulti) ? DSTAGNN_TRAIN_FIRST_MULTI : 0);
   d.drop_p = (float)drop_p;
   d.seed = (uint64_t)seed;
   TORCH_CHECK(flags >= 0, "flags: negative sample base");
@@ -142,6 +143,13 @@ BlockCall make_call(const Tensor& x, const c10::optional<Tensor>& res, at::Tenso
     if (!params[i].defined()) continue;
     check_dev(params[i], at::kFloat, "parameter");
     arr[slots[i]] = params[i].data_ptr<float>();
+  }
+  if (flags & kFirstMulti) {  // the sizes the F-strided first-block kernels index by
+    const Tensor* rw = nullptr;
+    for (size_t i = 0; i < params.size(); ++i)
+      if (slots[i] == 38 && params[i].defined()) rw = &params[i];
+    TORCH_CHECK(rw && rw->numel() == (int64_t)d.C * d.F, "multi-feature first block: residual_conv.weight must be (C, F, 1, 1) = (",
+                d.C, ", ", d.F, ", 1, 1)");
   }
   c.g = graph_of(graph, d.cheb_sparse != 0, d.K, d.N);
   d.cheb_flash = (flags & kFlash) ? 1 : 0;
@@ -227,7 +235,7 @@ BwdResult run_backward(const BlockCall& c, const Tensor& x, const c10::optional<
   d_out = d_out.contiguous();
   Tensor dre;
   if (d_re_at.has_value() && d_re_at->defined()) dre = d_re_at->contiguous();
-  const bool first = d.F == 1;
+  const bool first = d.F == 1 || (c.flags & kFirstMulti);
   // every used parameter's gradient is a view of ONE flat buffer, packed in parameter
   // order (the library writes the stacked Q|K|V, Q'|K', Theta_k gradients in place)
   int64_t total = 0;

@@ -22,6 +22,15 @@ from .block_fn import FLASH_SMALL_N, block_call, slots_of, use_flash
 from .head_fn import DSTAGNNHeadFunction
 from .graph import cheb_polynomial, scaled_Laplacian
 
+MAX_FIRST_F = 8  # include/dstagnn.h DSTAGNN_MAX_FIRST_F: input features of a multi-feature first block
+
+
+def _check_first_f(F):
+    if not 1 <= F <= MAX_FIRST_F:
+        raise ValueError(f"multi_feature: a multi-feature first block takes 1 <= F <= {MAX_FIRST_F} input features, "
+                         f"got F = {F} (the limit is {MAX_FIRST_F})")
+
+
 HIP_ONLY = ("dstagnn_drought_amd: DSTAGNN_block runs only on the MI355X HIP path; "
             "move the model and inputs to a 'cuda' (HIP) device. There is no CPU fallback.")
 
@@ -216,8 +225,19 @@ class DSTAGNN_block(nn.Module):
     forward_only = True
 
     def __init__(self, DEVICE, num_of_d, in_channels, K, nb_chev_filter, nb_time_filter, time_strides,
-                 cheb_polynomials, adj_pa, adj_TMD, num_of_vertices, num_of_timesteps, d_model, d_k, d_v, n_heads):
+                 cheb_polynomials, adj_pa, adj_TMD, num_of_vertices, num_of_timesteps, d_model, d_k, d_v, n_heads,
+                 *, multi_feature=False):
+        """multi_feature=True: this is a FIRST block over x (B, N, F, T) with F = in_channels = num_of_d
+        input features, 1 <= F <= 8 — the reference's block with its three `num_of_features == 1`
+        branches keyed on "first block": EmbedT over the F features (one position row per t),
+        tco = ReLU(tc), the residual through residual_conv (F -> C).  Every parameter is used."""
         super().__init__()
+        self.multi_feature = bool(multi_feature)
+        self.in_channels = in_channels
+        if self.multi_feature:
+            _check_first_f(in_channels)
+            if num_of_d != in_channels:
+                raise ValueError(f"multi_feature: num_of_d ({num_of_d}) must equal in_channels ({in_channels})")
         if time_strides != 1:
             raise ValueError("time_strides must be 1 (train_DSTAGNN_my.py:93 forces it)")
         if nb_chev_filter != nb_time_filter:
@@ -257,7 +277,12 @@ class DSTAGNN_block(nn.Module):
 
     def forward(self, x, res_att):
         B, N, Fd, T = x.shape
-        if Fd != 1 and Fd != self.nb_time_filter:
+        if self.multi_feature:
+            _check_first_f(Fd)
+            if Fd != self.in_channels:
+                raise RuntimeError(f"multi_feature: x has {Fd} features, the block was built for in_channels = "
+                                   f"{self.in_channels}")
+        elif Fd != 1 and Fd != self.nb_time_filter:
             # reference: RuntimeError at model/DSTAGNN_my.py:252 (quirk 8)
             raise RuntimeError(f"The size of tensor a ({Fd}) must match the size of tensor b "
                                f"({self.nb_time_filter}) at non-singleton dimension 1")
@@ -277,7 +302,7 @@ class DSTAGNN_block(nn.Module):
             graph = self._flash_graph(graph)
         out, re_at = block_call(x, res_att, params, slots, graph, meta, meta["train"], meta["seed"],
                                 self.direct_grads, flash=self.flash_cheb, plan_cache=self.__dict__.setdefault("_pcache", {}),
-                                sample_base=base, forward_only=self.forward_only)
+                                sample_base=base, forward_only=self.forward_only, first_multi=self.multi_feature)
         if self.grads_ready is not None and out.requires_grad:
             # DP overlap (dp.GradAllReducer.attach): once this block's backward node has run,
             # its parameter gradients are final — hand them over from a post-hook on the node
@@ -341,13 +366,20 @@ class DSTAGNN_submodule(nn.Module):
 
     def __init__(self, DEVICE, num_of_d, nb_block, in_channels, K, nb_chev_filter, nb_time_filter, time_strides,
                  cheb_polynomials, adj_pa, adj_TMD, num_for_predict, len_input, num_of_vertices, d_model, d_k, d_v,
-                 n_heads):
+                 n_heads, *, multi_feature=False):
+        """multi_feature=True: block 0 is a multi-feature first block over the F = in_channels input
+        features; the inner blocks are built for the C features block 0 hands them (pre_conv
+        (D, T, 1, C), where the reference's num_of_d * nb_time_filter is wrong for F > 1), and they
+        receive block 0's re_At averaged over its F features, (B, 1, h, T, T), in the broadcast form.
+        With F = 1 this is the default model, bit for bit."""
         super().__init__()
+        self.multi_feature = bool(multi_feature)
+        inner_d = nb_time_filter if self.multi_feature else num_of_d * nb_time_filter
         self.BlockList = nn.ModuleList([DSTAGNN_block(DEVICE, num_of_d, in_channels, K, nb_chev_filter,
                                                       nb_time_filter, time_strides, cheb_polynomials, adj_pa,
                                                       adj_TMD, num_of_vertices, len_input, d_model, d_k, d_v,
-                                                      n_heads)])
-        self.BlockList.extend([DSTAGNN_block(DEVICE, num_of_d * nb_time_filter, nb_chev_filter, K, nb_chev_filter,
+                                                      n_heads, multi_feature=self.multi_feature)])
+        self.BlockList.extend([DSTAGNN_block(DEVICE, inner_d, nb_chev_filter, K, nb_chev_filter,
                                              nb_time_filter, 1, cheb_polynomials, adj_pa, adj_TMD, num_of_vertices,
                                              len_input // time_strides, d_model, d_k, d_v, n_heads)
                                for _ in range(nb_block - 1)])
@@ -359,8 +391,12 @@ class DSTAGNN_submodule(nn.Module):
     def forward(self, x):
         need_concat = []
         res_att = 0
-        for block in self.BlockList:
+        for i, block in enumerate(self.BlockList):
             x, res_att = block(x, res_att)
+            if self.multi_feature and i == 0 and res_att.shape[1] > 1:
+                # the hand-off: the mean over block 0's F features (the identity at F = 1, and a
+                # score scale that does not grow with F)
+                res_att = res_att.mean(dim=1, keepdim=True)
             need_concat.append(x)
         # cat -> final_conv -> [..., -1] -> final_fc as one HIP head op (head.hip): the
         # concatenation is never materialised (model/DSTAGNN_my.py:276-280)
@@ -369,15 +405,18 @@ class DSTAGNN_submodule(nn.Module):
 
 
 def make_model(DEVICE, num_of_d, nb_block, in_channels, K, nb_chev_filter, nb_time_filter, time_strides, adj_mx,
-               adj_pa, adj_TMD, num_for_predict, len_input, num_of_vertices, d_model, d_k, d_v, n_heads):
+               adj_pa, adj_TMD, num_for_predict, len_input, num_of_vertices, d_model, d_k, d_v, n_heads,
+               *, multi_feature=False):
     """model/DSTAGNN_my.py:282-297: scaled Laplacian + Chebyshev polynomials, then the
-    xavier (dim>1) / U(0,1) (dim<=1, LayerNorm gamma/beta included) initialisation."""
+    xavier (dim>1) / U(0,1) (dim<=1, LayerNorm gamma/beta included) initialisation.
+    multi_feature=True: a model whose first block takes all F = in_channels = num_of_d input
+    features, 1 <= F <= 8 (DSTAGNN_submodule)."""
     L_tilde = scaled_Laplacian(adj_mx)
     Lt = L_tilde if isinstance(L_tilde, np.ndarray) else L_tilde.cpu().numpy()
     cheb_polynomials = [torch.from_numpy(np.asarray(c)).type(torch.FloatTensor) for c in cheb_polynomial(Lt, K)]
     model = DSTAGNN_submodule(DEVICE, num_of_d, nb_block, in_channels, K, nb_chev_filter, nb_time_filter,
                               time_strides, cheb_polynomials, adj_pa, adj_TMD, num_for_predict, len_input,
-                              num_of_vertices, d_model, d_k, d_v, n_heads)
+                              num_of_vertices, d_model, d_k, d_v, n_heads, multi_feature=multi_feature)
     for p in model.parameters():
         if p.dim() > 1:
             nn.init.xavier_uniform_(p)

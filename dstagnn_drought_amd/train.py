@@ -283,8 +283,9 @@ def predict_and_save_results_mstgcn(net, data_loader, data_target_tensor, global
     return excel_list
 
 
-def build(config, device):
-    """Graphs + model exactly as train_DSTAGNN_my.py:62-107 (model built on CPU, then moved)."""
+def build(config, device, multi_feature=None):
+    """Graphs + model exactly as train_DSTAGNN_my.py:62-107 (model built on CPU, then moved).
+    multi_feature (None: the [Training] key, model_options()) goes to make_model."""
     dc, tc = config['Data'], config['Training']
     N = int(dc['num_of_vertices'])
     if dc['dataset_name'] in ['PEMS04', 'PEMS08', 'PEMS07', 'PEMS03']:
@@ -298,7 +299,8 @@ def build(config, device):
     net = make_model('cpu', int(tc['in_channels']), int(tc['nb_block']), int(tc['in_channels']), int(tc['K']),
                      int(tc['nb_chev_filter']), int(tc['nb_time_filter']), 1, adj_merge, adj_pa, adj_TMD,
                      int(dc['num_for_predict']), int(dc['len_input']), N, int(tc['d_model']), int(tc['d_k']),
-                     int(tc['d_k']), int(tc['n_heads']))
+                     int(tc['d_k']), int(tc['n_heads']),
+                     multi_feature=model_options(tc) if multi_feature is None else bool(multi_feature))
     return net.to(device)
 
 
@@ -572,6 +574,22 @@ def scoring_options(tc):
     return tc.getboolean('test_metrics', fallback=False), tc.getboolean('node_scores', fallback=False)
 
 
+def model_options(tc):
+    """Optional [Training] key ``multi_feature`` of a configuration (a ConfigParser section) -> bool.
+    True: the first block takes all ``in_channels`` input features (model.make_model's
+    multi_feature; 1 <= in_channels <= 8).  Absent: False, today's model (which fails in its first
+    forward for 1 < in_channels < nb_time_filter, like the reference)."""
+    return tc.getboolean('multi_feature', fallback=False)
+
+
+def check_input_features(F, in_channels):
+    """The data's feature count against the model's ``in_channels`` (run() with multi_feature): a
+    ValueError that names both, instead of a shape error out of the first forward."""
+    if int(F) != int(in_channels):
+        raise ValueError(f"the data has F = {int(F)} features per node but [Training] in_channels = {int(in_channels)}: "
+                         f"a multi-feature model takes exactly in_channels features")
+
+
 def make_criterion(name=None, missing_value=None, smooth_l1_beta=1.0, huber_delta=1.0):
     """The driver's criterion.  With no name and no missing value: ``nn.SmoothL1Loss()``
     (train_DSTAGNN_my.py:132), the object every run without the keys of loss_options() has
@@ -687,7 +705,7 @@ def load_best(net, path):
 
 def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches=None, root='myexperiments',
         log=print, max_grad_norm=None, weight_decay=None, loss=None, missing_value=None, stream_windows=None,
-        input_fill=None, input_max_gap=None, test_metrics=None, node_scores=None):
+        input_fill=None, input_max_gap=None, test_metrics=None, node_scores=None, multi_feature=None):
     """Whole script: data, graphs, model, training, best-checkpoint test loss.  The optional
     [Training] keys of training_options() switch clipping / weight decay on; max_grad_norm /
     weight_decay given here override them.  loss / missing_value override the keys of
@@ -710,7 +728,10 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
     there is one; with node_scores also per node, which implies test_metrics).  Rank 0 logs one
     line per horizon and one overall and writes ``test_metrics.json`` (and
     ``test_node_scores.npz``) into the params path; the returned dict gains ``test_metrics`` (the
-    list of predict_and_save_results_mstgcn), ``test_scores`` and ``test_node_scores``."""
+    list of predict_and_save_results_mstgcn), ``test_scores`` and ``test_node_scores``.
+    multi_feature (None: the [Training] key of model_options(), off when absent): the model's first
+    block takes all ``in_channels`` features of the data (both data paths feed (B, N, F, T));
+    ValueError when the data's F differs from in_channels."""
     config = configparser.ConfigParser()
     config.read(config_path)
     dc, tc = config['Data'], config['Training']
@@ -749,7 +770,10 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
                                             int(tc['num_of_days']), int(tc['num_of_weeks']), 'cpu',
                                             int(tc['batch_size']))
         next(iter(train_loader))  # the reference probes one batch (:59-61): same RNG draw before the init
-    net = build(config, device)
+    multi_feature = model_options(tc) if multi_feature is None else bool(multi_feature)
+    if multi_feature:
+        check_input_features(train_x.shape[2], tc['in_channels'])
+    net = build(config, device, multi_feature)
     set_direct_grads(net)  # the loop only uses loss.backward() + .grad
     if dropout is not None:
         set_dropout(net, dropout)
@@ -822,7 +846,7 @@ def _windowed_series(dc, tc, device, missing_value=None, fill=None, max_gap=None
                                     points_per_hour=int(dc['points_per_hour']), device=device, stats=stats)
 
 
-def main(argv=None):
+def arg_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--config", default='configurations/PEMS04_dstagnn.conf', type=str)
     ap.add_argument("--epochs", type=int, default=None, help="override [Training] epochs")
@@ -858,7 +882,14 @@ def main(argv=None):
     ap.add_argument("--node-scores", action="store_true", default=None,
                     help="also score every node over all samples and horizons (test_node_scores.npz; implies "
                          "--test-metrics; overrides [Training] node_scores)")
-    a = ap.parse_args(argv)
+    ap.add_argument("--multi-feature", action="store_true", default=None,
+                    help="the first block takes all in_channels input features (1 <= in_channels <= 8) instead of "
+                         "failing for 1 < in_channels < nb_time_filter (overrides [Training] multi_feature)")
+    return ap
+
+
+def main(argv=None):
+    a = arg_parser().parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
         local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -870,7 +901,7 @@ def main(argv=None):
             max_batches=a.max_batches, root=a.out_root, max_grad_norm=a.max_grad_norm,
             weight_decay=a.weight_decay, loss=a.loss, missing_value=a.missing_value,
             stream_windows=a.stream_windows, input_fill=a.input_fill, input_max_gap=a.input_max_gap,
-            test_metrics=a.test_metrics, node_scores=a.node_scores)
+            test_metrics=a.test_metrics, node_scores=a.node_scores, multi_feature=a.multi_feature)
     finally:
         if world > 1:
             dist.destroy_process_group()

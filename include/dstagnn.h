@@ -48,6 +48,19 @@ enum {
  * 2 = tensor (B,F,h,T,T)                                                      */
 enum { DSTAGNN_RES_NONE = 0, DSTAGNN_RES_BCAST = 1, DSTAGNN_RES_FULL = 2 };
 
+/* dstagnn_block_dims::train is a word of flags (the struct keeps its layout): bit 0 turns the
+ * dropout sites on; DSTAGNN_TRAIN_FIRST_MULTI marks a MULTI-FEATURE FIRST BLOCK — x (B,N,F,T)
+ * with 1 <= F <= DSTAGNN_MAX_FIRST_F takes the first block's branches whatever F is:
+ *   E = LN_N(x.permute(0,2,3,1) + P_T[t,:]) (B,F,T,N), one position row per t shared by the F
+ *   features; tco = ReLU(tc); xres[b,c,n,t] = sum_f W_res[c,f] x[b,n,f,t] + b_res[c];
+ *   out = LN_C(ReLU(xres + tco)).  Every parameter is used and gets a gradient; d_x is (B,N,F,T).
+ * With the flag and F == 1 the call is the default first block, bit for bit.  Without it F must
+ * be 1 or C (the reference's behaviour and error); with it, F outside 1..DSTAGNN_MAX_FIRST_F is
+ * DSTAGNN_E_SHAPE.  Dropout is on when any bit other than DSTAGNN_TRAIN_FIRST_MULTI is set (so
+ * every earlier caller's non-zero `train` keeps its meaning).                                */
+enum { DSTAGNN_TRAIN_DROPOUT = 1, DSTAGNN_TRAIN_FIRST_MULTI = 256 };
+#define DSTAGNN_MAX_FIRST_F 8
+
 /* Shape of one DSTAGNN_block (DSTAGNN_block.__init__, model/DSTAGNN_my.py:200-201).
  * F = num_of_features of x (1 for the first block, else == C).               */
 typedef struct dstagnn_block_dims {
@@ -57,7 +70,7 @@ typedef struct dstagnn_block_dims {
   int K;                   /* Chebyshev order == SAt heads (quirk 6)              */
   int C;                   /* nb_chev_filter == nb_time_filter                    */
   int res_mode;            /* DSTAGNN_RES_*                                       */
-  int train;               /* 1: Dropout(0.05) at :234 and :221 active           */
+  int train;               /* DSTAGNN_TRAIN_* flags; bit 0: Dropout(0.05) at :234 and :221 active */
   float drop_p;            /* 0.05 in the reference                               */
   uint64_t seed;           /* dropout RNG seed (counter-based hash, per call)     */
   int cheb_sparse;         /* 1: aggregate over the CSC/CSR support in dstagnn_graph
@@ -78,7 +91,7 @@ typedef struct dstagnn_block_dims {
 } dstagnn_block_dims;
 
 /* Parameter pointers in state_dict order.  For the first block
- * (F==1) residual_conv / EmbedT are used; for inner blocks they are ignored
+ * (F==1, or DSTAGNN_TRAIN_FIRST_MULTI) residual_conv / EmbedT are used; for inner blocks they are ignored
  * (their grads stay untouched, matching the reference's None grads, quirk 11). */
 typedef struct dstagnn_block_params {
   const float* pre_conv_w;   /* (D, T, 1, F)          :207 */
@@ -194,7 +207,11 @@ enum {
   DSTAGNN_PATH_TAT_FUSED_BWD = 32,  /* ... and its backward                                      */
   DSTAGNN_PATH_GTU_FUSED_FWD = 64,  /* GTU stage as one kernel (gtu_fused.hip)                   */
   DSTAGNN_PATH_GTU_FUSED_BWD = 128, /* ... and its backward                                      */
-  DSTAGNN_PATH_SAT_LN_FUSED = 256   /* retired (that kernel is gone): never reported             */
+  DSTAGNN_PATH_SAT_LN_FUSED = 256,  /* retired (that kernel is gone): never reported             */
+  DSTAGNN_PATH_FIRST_MULTI = 512    /* multi-feature first block (DSTAGNN_TRAIN_FIRST_MULTI, F > 1): the
+                                       GTU stage runs the runtime-generic node kernels of gtu_tail.hip
+                                       with the F -> C residual (never gtu_fused.hip or the C = 32
+                                       compile-time tail)                                         */
 };
 int dstagnn_block_paths(const dstagnn_block_dims* d, uint32_t* bits);
 
