@@ -27,6 +27,13 @@
 //                        p), LDS folds the strip over nl (per horizon: a partial handed off as
 //                        above) and over p (per node: added straight into the node table, whose
 //                        rows have one owning workgroup each).
+//   pinball_fwd_kernel / pinball_bwd_kernel   the quantile (pinball) criterion of an (M, Q)
+//                        prediction, q fastest, against an (M) target: loss_fwd / loss_bwd's plan
+//                        over the M Q stream (element i: target i / Q, level i mod Q).
+//   metrics_quantile_kernel (B, N, P, Q) predictions -> running (P, 2 + 3 Q) and optional
+//                        (N, 2 + 3 Q) tables of the calibration sums (valid and crossing counts;
+//                        per level the pinball sum, the count of t <= y_q, the sum of y_q), on
+//                        metrics_masked_kernel's plan.
 //
 // A masked entry is selected out (never multiplied by zero): a NaN target under the NaN mask
 // leaves the loss finite and its gradient entry exactly 0.  A NaN prediction at a valid entry makes
@@ -326,6 +333,273 @@ __global__ __launch_bounds__(kMmThreads) void metrics_masked_kernel(int B, int N
   }
 }
 
+// ---- quantile forecasts: the pinball criterion and the calibration sums -----------------------
+// Prediction (M, Q), q fastest; target (M).  Element i of the prediction stream belongs to target
+// i / Q and level i mod Q: the stream itself is read as loss_fwd_kernel reads y (consecutive lanes,
+// consecutive floats; 16-byte loads on whole aligned tiles), the target through the cache (Q
+// neighbouring lanes share one).  The levels sit in LDS: tau and 1 - tau, both formed on the host.
+constexpr int kMaxQ = DSTAGNN_MAX_QUANTILES;
+struct PinballArgs {  // a checked dstagnn_pinball_cfg and the 1 - tau of its levels
+  int mask_mode;
+  float null_val;
+  int num_quantiles;
+  float tau[kMaxQ], one_minus_tau[kMaxQ];
+};
+
+// term and slope of d = y_q - t: d > 0: (1 - tau) d, slope 1 - tau; d < 0: tau (-d), slope -tau;
+// d = 0: 0 and 0 (DSTAGNN_LOSS_MAE's sign(0) = 0); a NaN d stays NaN
+__device__ __forceinline__ float pinball_term(float tau, float omt, float d) {
+  return d > 0.f ? omt * d : d < 0.f ? tau * -d : d == 0.f ? 0.f : d;
+}
+__device__ __forceinline__ float pinball_slope(float tau, float omt, float d) {
+  return d > 0.f ? omt : d < 0.f ? -tau : d == 0.f ? 0.f : d;
+}
+
+// (target index, level) of the four stream elements i0 .. i0 + 3
+__device__ __forceinline__ void pinball_walk(unsigned i0, unsigned Q, unsigned (&m)[4], unsigned (&q)[4]) {
+  m[0] = i0 / Q;
+  q[0] = i0 - m[0] * Q;
+#pragma unroll
+  for (int j = 1; j < 4; ++j) {
+    const bool wrap = q[j - 1] + 1 == Q;
+    q[j] = wrap ? 0u : q[j - 1] + 1;
+    m[j] = m[j - 1] + (wrap ? 1u : 0u);
+  }
+}
+
+__global__ __launch_bounds__(kLossThreads) void pinball_fwd_kernel(PinballArgs cfg, int64_t n,
+                                                                  const float* __restrict__ y,
+                                                                  const float* __restrict__ tg, int vec,
+                                                                  double* __restrict__ part, int* ticket,
+                                                                  double* __restrict__ stat,
+                                                                  float* __restrict__ loss) {
+  __shared__ double ws[kLossThreads / 64], wc[kLossThreads / 64];
+  __shared__ float tau[kMaxQ], omt[kMaxQ];
+  __shared__ int last;
+  const int t = threadIdx.x;
+  const unsigned Q = (unsigned)cfg.num_quantiles;
+  if (t < kMaxQ) tau[t] = cfg.tau[t], omt[t] = cfg.one_minus_tau[t];
+  __syncthreads();
+  double sum = 0.0, cnt = 0.0;  // cnt counts stream elements: Q per valid target entry
+  for (int64_t base = (int64_t)blockIdx.x * kLossTile; base < n; base += (int64_t)gridDim.x * kLossTile) {
+    if (vec && base + kLossTile <= n) {  // (uniform) a whole tile: four 16-byte loads of y
+      const float4* __restrict__ y4 = reinterpret_cast<const float4*>(y + base);
+      float4 a[kLossPer / 4];
+#pragma unroll
+      for (int u = 0; u < kLossPer / 4; ++u) a[u] = y4[u * kLossThreads + t];
+#pragma unroll
+      for (int u = 0; u < kLossPer / 4; ++u) {
+        unsigned m[4], q[4];
+        pinball_walk((unsigned)base + 4u * (unsigned)(u * kLossThreads + t), Q, m, q);
+        const float yv[4] = {a[u].x, a[u].y, a[u].z, a[u].w};
+        float tv[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) tv[j] = tg[m[j]];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (is_valid(cfg.mask_mode, cfg.null_val, tv[j])) {
+            sum += (double)pinball_term(tau[q[j]], omt[q[j]], yv[j] - tv[j]);
+            cnt += 1.0;
+          }
+      }
+    } else {
+      float yv[kLossPer], tv[kLossPer];
+      unsigned qv[kLossPer];
+#pragma unroll
+      for (int u = 0; u < kLossPer; ++u) {
+        const int64_t i = base + t + (int64_t)kLossThreads * u;
+        const bool ok = i < n;
+        const unsigned m = ok ? (unsigned)i / Q : 0u;
+        qv[u] = ok ? (unsigned)i - m * Q : 0u;
+        yv[u] = ok ? y[i] : 0.f;
+        tv[u] = ok ? tg[m] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < kLossPer; ++u) {
+        const int64_t i = base + t + (int64_t)kLossThreads * u;
+        if (i < n && is_valid(cfg.mask_mode, cfg.null_val, tv[u])) {
+          sum += (double)pinball_term(tau[qv[u]], omt[qv[u]], yv[u] - tv[u]);
+          cnt += 1.0;
+        }
+      }
+    }
+  }
+  sum = wave_sum_f64(sum);
+  cnt = wave_sum_f64(cnt);
+  if ((t & 63) == 0) ws[t >> 6] = sum, wc[t >> 6] = cnt;
+  __syncthreads();
+  if (t == 0) {  // the hand-off of handoff.hpp, as loss_fwd_kernel
+    st_agent(part + 2 * (int64_t)blockIdx.x, (ws[0] + ws[1]) + (ws[2] + ws[3]));
+    st_agent(part + 2 * (int64_t)blockIdx.x + 1, (wc[0] + wc[1]) + (wc[2] + wc[3]));
+  }
+  if (!last_arrival(ticket, (int)gridDim.x, &last)) return;
+  if (t >= 64) return;
+  double a = 0.0, c = 0.0;
+  for (int64_t k = t; k < (int64_t)gridDim.x; k += 64) {
+    a += ld_agent(part + 2 * k);
+    c += ld_agent(part + 2 * k + 1);
+  }
+  a = wave_sum_f64(a);
+  c = wave_sum_f64(c);
+  if (t == 0) {
+    stat[0] = a;
+    stat[1] = c / (double)Q;  // the valid target entries (c is a multiple of Q: exact)
+    loss[0] = c > 0.0 ? (float)(a / c) : 0.f;
+  }
+}
+
+__global__ __launch_bounds__(kLossThreads) void pinball_bwd_kernel(PinballArgs cfg, int64_t n,
+                                                                  const float* __restrict__ y,
+                                                                  const float* __restrict__ tg, int vec,
+                                                                  const double* __restrict__ stat,
+                                                                  const float* __restrict__ gout,
+                                                                  float* __restrict__ dy) {
+  __shared__ float tau[kMaxQ], omt[kMaxQ];
+  const int t = threadIdx.x;
+  const unsigned Q = (unsigned)cfg.num_quantiles;
+  if (t < kMaxQ) tau[t] = cfg.tau[t], omt[t] = cfg.one_minus_tau[t];
+  __syncthreads();
+  const double cnt = stat[1] * (double)Q;
+  const float g = gout != nullptr ? gout[0] : 1.f;
+  const float scale = cnt > 0.0 ? (float)((double)g / cnt) : 0.f;
+  const int64_t base = (int64_t)blockIdx.x * kLossTile;
+  if (vec && base + kLossTile <= n) {
+    const float4* __restrict__ y4 = reinterpret_cast<const float4*>(y + base);
+    float4* __restrict__ d4 = reinterpret_cast<float4*>(dy + base);
+    float4 a[kLossPer / 4];
+#pragma unroll
+    for (int u = 0; u < kLossPer / 4; ++u) a[u] = y4[u * kLossThreads + t];
+#pragma unroll
+    for (int u = 0; u < kLossPer / 4; ++u) {
+      unsigned m[4], q[4];
+      pinball_walk((unsigned)base + 4u * (unsigned)(u * kLossThreads + t), Q, m, q);
+      const float yv[4] = {a[u].x, a[u].y, a[u].z, a[u].w};
+      float tv[4], r[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) tv[j] = tg[m[j]];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float s = pinball_slope(tau[q[j]], omt[q[j]], yv[j] - tv[j]);
+        r[j] = is_valid(cfg.mask_mode, cfg.null_val, tv[j]) && s != 0.f ? s * scale : 0.f;
+      }
+      d4[u * kLossThreads + t] = make_float4(r[0], r[1], r[2], r[3]);
+    }
+    return;
+  }
+  float yv[kLossPer], tv[kLossPer];
+  unsigned qv[kLossPer];
+#pragma unroll
+  for (int u = 0; u < kLossPer; ++u) {
+    const int64_t i = base + t + (int64_t)kLossThreads * u;
+    const bool ok = i < n;
+    const unsigned m = ok ? (unsigned)i / Q : 0u;
+    qv[u] = ok ? (unsigned)i - m * Q : 0u;
+    yv[u] = ok ? y[i] : 0.f;
+    tv[u] = ok ? tg[m] : 0.f;
+  }
+#pragma unroll
+  for (int u = 0; u < kLossPer; ++u) {
+    const int64_t i = base + t + (int64_t)kLossThreads * u;
+    if (i < n) {
+      const float s = pinball_slope(tau[qv[u]], omt[qv[u]], yv[u] - tv[u]);
+      dy[i] = is_valid(cfg.mask_mode, cfg.null_val, tv[u]) && s != 0.f ? s * scale : 0.f;
+    }
+  }
+}
+
+// The calibration sums of (B, N, P, Q) predictions against (B, N, P) targets: metrics_masked_kernel's
+// shape (a workgroup owns a strip of 256 / P nodes, thread nl P + p walks the samples of element
+// (n0 + nl, p)) with 2 + 3 Q sums per thread: valid count, crossing count and, per level, the pinball
+// sum (fp32 term), the count of t <= y_q (fp32 compare) and the sum of y_q (exact as doubles).
+// A thread reads the Q floats of its entry (the wave: 64 Q contiguous floats, every byte used) and
+// keeps its sums in registers; the loops over q are unrolled to kMaxQ under the uniform q < Q so
+// every index is a constant.  The LDS folds go kQmChunk columns at a time.
+constexpr int kQmThreads = 256, kQmCols = 2 + 3 * kMaxQ, kQmChunk = 8, kQmFold = 8;
+
+__global__ __launch_bounds__(kQmThreads) void metrics_quantile_kernel(int B, int N, int P, PinballArgs cfg,
+                                                                     const float* __restrict__ pred,
+                                                                     const float* __restrict__ tg,
+                                                                     double* __restrict__ part, int* ticket,
+                                                                     double* __restrict__ htable,
+                                                                     double* __restrict__ ntable) {
+  __shared__ double red[kQmChunk][kQmThreads];
+  __shared__ int last;
+  const int t = threadIdx.x;
+  const int Q = cfg.num_quantiles, cols = 2 + 3 * Q;
+  const int TN = kQmThreads / P;
+  const int n0 = (int)blockIdx.x * TN;       // (the grid is ceil(N / TN): n0 < N)
+  const int tn = N - n0 < TN ? N - n0 : TN;  // nodes of this strip
+  double s[kQmCols];
+#pragma unroll
+  for (int c = 0; c < kQmCols; ++c) s[c] = 0.0;
+  if (t < tn * P) {
+    const int64_t step = (int64_t)N * P;
+    const float* __restrict__ tp = tg + (int64_t)n0 * P + t;
+    const float* __restrict__ pp = pred + ((int64_t)n0 * P + t) * Q;
+    for (int b = 0; b < B; ++b) {
+      const float tv = tp[b * step];
+      float yv[kMaxQ];
+#pragma unroll
+      for (int q = 0; q < kMaxQ; ++q) yv[q] = q < Q ? pp[b * step * Q + q] : 0.f;
+      if (!is_valid(cfg.mask_mode, cfg.null_val, tv)) continue;  // selected out
+      bool cross = false;
+#pragma unroll
+      for (int q = 0; q < kMaxQ; ++q)
+        if (q < Q) {
+          s[2 + 3 * q] += (double)pinball_term(cfg.tau[q], cfg.one_minus_tau[q], yv[q] - tv);
+          s[3 + 3 * q] += tv <= yv[q] ? 1.0 : 0.0;
+          s[4 + 3 * q] += (double)yv[q];
+          if (q > 0) cross = cross || yv[q] < yv[q - 1];
+        }
+      s[0] += 1.0;
+      s[1] += cross ? 1.0 : 0.0;
+    }
+  }
+  const int items = cols * P;  // of a workgroup's horizon partial; item = c P + p
+#pragma unroll
+  for (int c0 = 0; c0 < kQmCols; c0 += kQmChunk) {
+    if (c0 >= cols) break;  // (uniform)
+    __syncthreads();        // the previous chunk's readers are done
+#pragma unroll
+    for (int j = 0; j < kQmChunk; ++j) {
+      const int c = c0 + j;  // (a constant once unrolled)
+      red[j][t] = c < kQmCols ? s[c < kQmCols ? c : 0] : 0.0;
+    }
+    __syncthreads();
+    const int cw = cols - c0 < kQmChunk ? cols - c0 : kQmChunk;  // columns of this chunk
+    // per node, over p in order; this workgroup is the only one that ever touches these rows
+    if (ntable != nullptr) {
+      for (int item = t; item < cw * tn; item += kQmThreads) {
+        const int nl = item / cw, j = item - nl * cw;
+        double a = 0.0;
+        for (int p = 0; p < P; ++p) a += red[j][nl * P + p];
+        ntable[(int64_t)(n0 + nl) * cols + c0 + j] += a;
+      }
+    }
+    // per horizon, over nl in order (the idle rows of a partial strip hold zeros)
+    for (int item = t; item < cw * P; item += kQmThreads) {
+      const int j = item / P, p = item - j * P;
+      double a = 0.0;
+      for (int nl = 0; nl < TN; ++nl) a += red[j][nl * P + p];
+      st_agent(part + (int64_t)blockIdx.x * items + (c0 + j) * P + p, a);
+    }
+  }
+  if (!last_arrival(ticket, (int)gridDim.x, &last)) return;
+  const int G = (int)gridDim.x;
+  for (int item = t; item < items; item += kQmThreads) {
+    const int c = item / P, p = item - c * P;
+    double a = 0.0;
+    for (int k0 = 0; k0 < G; k0 += kQmFold) {
+      double u[kQmFold];
+#pragma unroll
+      for (int k = 0; k < kQmFold; ++k) u[k] = k0 + k < G ? ld_agent(part + (int64_t)(k0 + k) * items + item) : 0.0;
+#pragma unroll
+      for (int k = 0; k < kQmFold; ++k) a += u[k];
+    }
+    htable[p * cols + c] += a;
+  }
+}
+
 int64_t loss_grid(int64_t n) {
   const int64_t tiles = (n + kLossTile - 1) / kLossTile;
   return tiles < 1 ? 1 : tiles > kLossMaxWg ? kLossMaxWg : tiles;
@@ -501,6 +775,165 @@ int dstagnn_metrics_accumulate_masked(int64_t B, int64_t N, int P, const float* 
   }
   hipLaunchKernelGGL(metrics_masked_kernel, dim3((unsigned)grid), dim3(kMmThreads), 0, st, (int)B, (int)N, P, pred,
                      target, mask_mode, null_val, mape_null, static_cast<double*>(scratch), ticket, htable, ntable);
+  DS_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- quantile forecasts -----------------------------------------------------------------------
+namespace {
+
+// the level rule (include/dstagnn.h): 1 <= Q <= 16 levels, each strictly inside (0, 1), strictly
+// increasing; the mask mode as loss_args reads it.  Fills the kernels' argument block.
+int pinball_args(const std::string& w, const dstagnn_pinball_cfg* cfg, PinballArgs* out) {
+  if (!cfg) {
+    set_last_error(w + ": null cfg");
+    return DSTAGNN_E_ARG;
+  }
+  const int Q = cfg->num_quantiles;
+  if (Q < 1 || Q > kMaxQ) {
+    set_last_error(w + ": num_quantiles must be in [1, " + std::to_string(kMaxQ) + "], got " + std::to_string(Q));
+    return DSTAGNN_E_ARG;
+  }
+  for (int q = 0; q < Q; ++q) {
+    const float v = cfg->tau[q];
+    if (!(v > 0.f && v < 1.f)) {  // (a NaN fails too)
+      set_last_error(w + ": every quantile level must be strictly inside (0, 1), got " + std::to_string(v));
+      return DSTAGNN_E_ARG;
+    }
+    if (q > 0 && !(cfg->tau[q - 1] < v)) {
+      set_last_error(w + ": the quantile levels must be strictly increasing");
+      return DSTAGNN_E_ARG;
+    }
+  }
+  if (cfg->mask_mode < DSTAGNN_MASK_NONE || cfg->mask_mode > DSTAGNN_MASK_NAN) {
+    set_last_error(w + ": unknown mask mode " + std::to_string(cfg->mask_mode));
+    return DSTAGNN_E_ARG;
+  }
+  out->mask_mode = cfg->mask_mode;
+  out->null_val = cfg->null_val;
+  out->num_quantiles = Q;
+  if (out->mask_mode == DSTAGNN_MASK_NEQ && std::isnan(out->null_val)) out->mask_mode = DSTAGNN_MASK_NAN;
+  for (int q = 0; q < kMaxQ; ++q) {
+    out->tau[q] = q < Q ? cfg->tau[q] : 0.5f;
+    out->one_minus_tau[q] = 1.0f - out->tau[q];  // fp32, once
+  }
+  return 0;
+}
+
+// the checks shared by forward and backward; *n = m * Q, the length of the prediction stream
+int pinball_pair(const std::string& w, const dstagnn_pinball_cfg* cfg, int64_t m, const void* y, const void* target,
+                 PinballArgs* out, int64_t* n) {
+  if (int rc = pinball_args(w, cfg, out)) return rc;
+  if (m <= 0 || m > ((1ll << 31) - 1) / out->num_quantiles) {
+    set_last_error(w + ": m must be >= 1 and m * num_quantiles < 2^31");
+    return DSTAGNN_E_SHAPE;
+  }
+  if (!y || !target) {
+    set_last_error(w + ": null y / target");
+    return DSTAGNN_E_ARG;
+  }
+  *n = m * out->num_quantiles;
+  return 0;
+}
+
+}  // namespace
+
+int64_t dstagnn_pinball_scratch_bytes(int64_t m, int num_quantiles) {
+  if (m <= 0 || num_quantiles < 1 || num_quantiles > kMaxQ || m > ((1ll << 31) - 1) / num_quantiles) return 0;
+  return loss_grid(m * num_quantiles) * 2 * (int64_t)sizeof(double);
+}
+
+int dstagnn_pinball_forward(const dstagnn_pinball_cfg* cfg, int64_t m, const float* y, const float* target,
+                            float* loss, double* stat, void* scratch, size_t scratch_bytes,
+                            dstagnn_stream_t stream) {
+  PinballArgs a;
+  int64_t n = 0;
+  if (int rc = pinball_pair("pinball_forward", cfg, m, y, target, &a, &n)) return rc;
+  if (!loss || !stat || !scratch) {
+    set_last_error("pinball_forward: null loss / stat / scratch");
+    return DSTAGNN_E_ARG;
+  }
+  if (scratch_bytes < (size_t)dstagnn_pinball_scratch_bytes(m, a.num_quantiles)) {
+    set_last_error("pinball_forward: scratch smaller than dstagnn_pinball_scratch_bytes(m, num_quantiles)");
+    return DSTAGNN_E_SPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  int* ticket = stream_counters(st, 1);
+  if (!ticket) {
+    set_last_error("pinball_forward: no ticket counter for this stream");
+    return DSTAGNN_E_ARG;
+  }
+  const int vec = aligned16(y);  // (the target is read through the cache, one float at a time)
+  hipLaunchKernelGGL(pinball_fwd_kernel, dim3((unsigned)loss_grid(n)), dim3(kLossThreads), 0, st, a, n, y, target, vec,
+                     static_cast<double*>(scratch), ticket, stat, loss);
+  DS_CHECK_LAUNCH();
+  return 0;
+}
+
+int dstagnn_pinball_backward(const dstagnn_pinball_cfg* cfg, int64_t m, const float* y, const float* target,
+                             const double* stat, const float* gout, float* dy, dstagnn_stream_t stream) {
+  PinballArgs a;
+  int64_t n = 0;
+  if (int rc = pinball_pair("pinball_backward", cfg, m, y, target, &a, &n)) return rc;
+  if (!stat || !dy) {
+    set_last_error("pinball_backward: null stat / dy");
+    return DSTAGNN_E_ARG;
+  }
+  const int vec = aligned16(y) && aligned16(dy);
+  const int64_t tiles = (n + kLossTile - 1) / kLossTile;
+  hipLaunchKernelGGL(pinball_bwd_kernel, dim3((unsigned)tiles), dim3(kLossThreads), 0, (hipStream_t)stream, a, n, y,
+                     target, vec, stat, gout, dy);
+  DS_CHECK_LAUNCH();
+  return 0;
+}
+
+int64_t dstagnn_metrics_quantile_scratch_bytes(int64_t B, int64_t N, int P, int num_quantiles) {
+  if (num_quantiles < 1 || num_quantiles > kMaxQ) return 0;
+  const int64_t grid = masked_grid(B, N, P);
+  if (grid == 0 || B * N * P > ((1ll << 31) - 1) / num_quantiles) return 0;
+  return grid * (2 + 3 * (int64_t)num_quantiles) * P * (int64_t)sizeof(double);
+}
+
+int dstagnn_metrics_accumulate_quantile(int64_t B, int64_t N, int P, const dstagnn_pinball_cfg* cfg,
+                                        const float* pred, const float* target, double* htable, double* ntable,
+                                        void* scratch, size_t scratch_bytes, dstagnn_stream_t stream) {
+  const std::string w("metrics_accumulate_quantile");
+  if (!cfg) {
+    set_last_error(w + ": null cfg");
+    return DSTAGNN_E_ARG;
+  }
+  if (P < 1 || P > kMetMaxP) {
+    set_last_error(w + ": P (the horizon axis) must be in [1, 256], got " + std::to_string(P));
+    return DSTAGNN_E_SHAPE;
+  }
+  const int Q = cfg->num_quantiles;
+  if (Q < 1 || Q > kMaxQ) {
+    set_last_error(w + ": Q (the last axis) must be in [1, " + std::to_string(kMaxQ) + "], got " + std::to_string(Q));
+    return DSTAGNN_E_SHAPE;
+  }
+  const int64_t grid = masked_grid(B, N, P);
+  if (grid == 0 || B * N * P > ((1ll << 31) - 1) / Q) {
+    set_last_error(w + ": B and N must be >= 1 and B * N * P * Q in [1, 2^31)");
+    return DSTAGNN_E_SHAPE;
+  }
+  if (!pred || !target || !htable || !scratch) {
+    set_last_error(w + ": null pred / target / htable / scratch");
+    return DSTAGNN_E_ARG;
+  }
+  PinballArgs a;
+  if (int rc = pinball_args(w, cfg, &a)) return rc;
+  if (scratch_bytes < (size_t)dstagnn_metrics_quantile_scratch_bytes(B, N, P, Q)) {
+    set_last_error(w + ": scratch smaller than dstagnn_metrics_quantile_scratch_bytes(B, N, P, Q)");
+    return DSTAGNN_E_SPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  int* ticket = stream_counters(st, 1);
+  if (!ticket) {
+    set_last_error(w + ": no ticket counter for this stream");
+    return DSTAGNN_E_ARG;
+  }
+  hipLaunchKernelGGL(metrics_quantile_kernel, dim3((unsigned)grid), dim3(kQmThreads), 0, st, (int)B, (int)N, P, a,
+                     pred, target, static_cast<double*>(scratch), ticket, htable, ntable);
   DS_CHECK_LAUNCH();
   return 0;
 }

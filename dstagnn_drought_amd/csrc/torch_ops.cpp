@@ -16,6 +16,8 @@
 //   dstagnn::loss_fwd/bwd   the criterion (train_DSTAGNN_my.py:132, :156-157) and its masked variants
 //   dstagnn::metrics_update per-horizon MAE / RMSE / MAPE sums on the device (lib/utils1.py:418-431)
 //   dstagnn::metrics_update_masked the same over the valid entries only, per horizon and per node
+//   dstagnn::pinball_fwd/bwd the quantile (pinball) criterion over (..., Q) predictions
+//   dstagnn::metrics_update_quantile coverage / pinball / mean-quantile / crossing sums, per horizon and per node
 //   dstagnn::window_gather  a batch's input windows and targets cut from the raw series, transposed
 //                           and z-scored (prepareData.py:63-161 per batch instead of once per label)
 //   dstagnn::window_stats   the training windows' mean / std from the raw series (prepareData.py:149-161)
@@ -1021,6 +1023,96 @@ void metrics_update_masked(const Tensor& pred, const Tensor& target, int64_t mas
            "dstagnn_metrics_accumulate_masked");
 }
 
+// quantile forecasts: the levels as a checked-by-the-library dstagnn_pinball_cfg (a count outside
+// [1, 16] travels as it is, for the library's DSTAGNN_E_ARG / DSTAGNN_E_SHAPE)
+dstagnn_pinball_cfg pinball_cfg(c10::ArrayRef<double> quantiles, int64_t mask_mode, double null_val) {
+  dstagnn_pinball_cfg cfg{};
+  cfg.mask_mode = (int)mask_mode;
+  cfg.null_val = (float)null_val;
+  cfg.num_quantiles = (int)std::min<size_t>(quantiles.size(), 1u << 20);
+  for (size_t q = 0; q < quantiles.size() && q < DSTAGNN_MAX_QUANTILES; ++q) cfg.tau[q] = (float)quantiles[q];
+  return cfg;
+}
+
+void check_pinball_pair(const Tensor& y, const Tensor& target, size_t Q, const char* who) {
+  check_dev(y, at::kFloat, "y");
+  check_dev(target, at::kFloat, "target");
+  TORCH_CHECK(y.dim() >= 1 && y.dim() == target.dim() + 1 && y.sizes().slice(0, y.dim() - 1) == target.sizes() &&
+                  (size_t)y.size(-1) == Q,
+              who, ": y ", y.sizes(), " must be target ", target.sizes(), " with a last axis of ", Q, " quantiles");
+  TORCH_CHECK(y.device() == target.device(), who, ": y and target on different devices");
+}
+
+// y (..., Q), target (...) -> (loss: 0-dim fp32, stat: {fp64 sum of the terms, valid count}); no host sync
+std::tuple<Tensor, Tensor> pinball_fwd(const Tensor& y, const Tensor& target, c10::ArrayRef<double> quantiles,
+                                       int64_t mask_mode, double null_val) {
+  check_pinball_pair(y, target, quantiles.size(), "pinball_fwd");
+  c10::DeviceGuard guard(y.device());
+  const int64_t m = target.numel();
+  const dstagnn_pinball_cfg cfg = pinball_cfg(quantiles, mask_mode, null_val);
+  const int64_t sb = std::max<int64_t>(dstagnn_pinball_scratch_bytes(m, cfg.num_quantiles), 16);
+  Tensor loss = at::empty({}, f32(y)), buf = at::empty({2 + sb / 8}, y.options().dtype(at::kDouble));
+  check_rc(dstagnn_pinball_forward(&cfg, m, y.data_ptr<float>(), target.data_ptr<float>(), loss.data_ptr<float>(),
+                                   buf.data_ptr<double>(), buf.data_ptr<double>() + 2, (size_t)sb, stream_of(y)),
+           "dstagnn_pinball_forward");
+  return {loss, buf.narrow(0, 0, 2)};
+}
+
+// dy = gout * slope / (stat[1] * Q) on valid entries, 0 elsewhere
+Tensor pinball_bwd(const Tensor& y, const Tensor& target, const Tensor& stat, const c10::optional<Tensor>& gout,
+                   c10::ArrayRef<double> quantiles, int64_t mask_mode, double null_val) {
+  check_pinball_pair(y, target, quantiles.size(), "pinball_bwd");
+  check_dev(stat, at::kDouble, "stat");
+  TORCH_CHECK(stat.numel() == 2 && stat.device() == y.device(), "pinball_bwd: stat must be pinball_fwd's two doubles");
+  if (gout.has_value() && gout->defined()) {
+    check_dev(*gout, at::kFloat, "gout");
+    TORCH_CHECK(gout->numel() == 1 && gout->device() == y.device(),
+                "pinball_bwd: gout must be one float on y's device");
+  }
+  c10::DeviceGuard guard(y.device());
+  const dstagnn_pinball_cfg cfg = pinball_cfg(quantiles, mask_mode, null_val);
+  Tensor dy = at::empty(y.sizes(), f32(y));
+  check_rc(dstagnn_pinball_backward(&cfg, target.numel(), y.data_ptr<float>(), target.data_ptr<float>(),
+                                    stat.data_ptr<double>(), ptr_or_null<float>(gout), dy.data_ptr<float>(),
+                                    stream_of(y)),
+           "dstagnn_pinball_backward");
+  return dy;
+}
+
+// pred (..., N, P, Q), target (..., N, P): the 2 + 3 Q calibration sums added into the running
+// (P, 2 + 3 Q) horizon table and, where given, the running (N, 2 + 3 Q) node table; one launch
+void metrics_update_quantile(const Tensor& pred, const Tensor& target, c10::ArrayRef<double> quantiles,
+                             int64_t mask_mode, double null_val, Tensor htable,
+                             const c10::optional<Tensor>& ntable) {
+  check_pinball_pair(pred, target, quantiles.size(), "metrics_update_quantile");
+  check_dev(htable, at::kDouble, "htable");
+  TORCH_CHECK(target.dim() >= 2, "metrics_update_quantile: target must have a node and a horizon axis");
+  const int64_t Q = (int64_t)quantiles.size(), cols = 2 + 3 * Q;
+  const int64_t P = target.size(-1), N = target.size(-2), B = P > 0 && N > 0 ? target.numel() / (N * P) : 0;
+  // (a P outside [1, 256] or a Q outside [1, 16] is the library's DSTAGNN_E_SHAPE below)
+  const bool in_range = P >= 1 && P <= 256 && Q >= 1 && Q <= DSTAGNN_MAX_QUANTILES;
+  TORCH_CHECK(!in_range || (htable.dim() == 2 && htable.size(0) == P && htable.size(1) == cols),
+              "metrics_update_quantile: htable must be (", P, ", ", cols, "), got ", htable.sizes());
+  TORCH_CHECK(htable.device() == pred.device(), "metrics_update_quantile: htable on another device");
+  const bool nodes = ntable.has_value() && ntable->defined();
+  if (nodes) {
+    check_dev(*ntable, at::kDouble, "ntable");
+    TORCH_CHECK(!in_range || (ntable->dim() == 2 && ntable->size(0) == N && ntable->size(1) == cols),
+                "metrics_update_quantile: ntable must be (", N, ", ", cols, "), got ", ntable->sizes());
+    TORCH_CHECK(ntable->device() == pred.device(), "metrics_update_quantile: ntable on another device");
+  }
+  c10::DeviceGuard guard(pred.device());
+  const dstagnn_pinball_cfg cfg = pinball_cfg(quantiles, mask_mode, null_val);
+  const int Pi = (int)std::min<int64_t>(P, INT32_MAX);
+  const int64_t sb = std::max<int64_t>(dstagnn_metrics_quantile_scratch_bytes(B, N, Pi, cfg.num_quantiles), 16);
+  Tensor scratch = at::empty({sb / 8}, pred.options().dtype(at::kDouble));
+  check_rc(dstagnn_metrics_accumulate_quantile(B, N, Pi, &cfg, pred.data_ptr<float>(), target.data_ptr<float>(),
+                                               htable.data_ptr<double>(),
+                                               nodes ? ntable->data_ptr<double>() : nullptr,
+                                               scratch.data_ptr<double>(), (size_t)sb, stream_of(pred)),
+           "dstagnn_metrics_accumulate_quantile");
+}
+
 // -------------------------------------------------------------------------------------
 // training windows from the raw series (windows.hip)
 // -------------------------------------------------------------------------------------
@@ -1375,6 +1467,11 @@ TORCH_LIBRARY(dstagnn, m) {
   m.def("metrics_update(Tensor pred, Tensor target, float null_val, Tensor(a!) table) -> ()");
   m.def("metrics_update_masked(Tensor pred, Tensor target, int mask_mode, float null_val, float mape_null, "
         "Tensor(a!) htable, Tensor(b!)? ntable) -> ()");
+  m.def("pinball_fwd(Tensor y, Tensor target, float[] quantiles, int mask_mode, float null_val) -> (Tensor, Tensor)");
+  m.def("pinball_bwd(Tensor y, Tensor target, Tensor stat, Tensor? gout, float[] quantiles, int mask_mode, "
+        "float null_val) -> Tensor");
+  m.def("metrics_update_quantile(Tensor pred, Tensor target, float[] quantiles, int mask_mode, float null_val, "
+        "Tensor(a!) htable, Tensor(b!)? ntable) -> ()");
   m.def("window_gather(Tensor series, Tensor rel, Tensor labels, Tensor idx, Tensor mean, Tensor std, int P) "
         "-> (Tensor, Tensor)");
   m.def("window_stats(Tensor series, Tensor w, float wtotal) -> Tensor");
@@ -1431,6 +1528,9 @@ TORCH_LIBRARY_IMPL(dstagnn, CUDA, m) {
   m.impl("loss_bwd", loss_bwd);
   m.impl("metrics_update", metrics_update);
   m.impl("metrics_update_masked", metrics_update_masked);
+  m.impl("pinball_fwd", pinball_fwd);
+  m.impl("pinball_bwd", pinball_bwd);
+  m.impl("metrics_update_quantile", metrics_update_quantile);
   m.impl("window_gather", window_gather);
   m.impl("window_stats", window_stats);
   m.impl("window_stats_masked", window_stats_masked);

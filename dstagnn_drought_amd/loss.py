@@ -11,6 +11,9 @@ a (P, 4) fp64 table on the device: one launch per batch, one device-to-host copy
 With a missing value and / or a node count: the masked (P, 8) and (N, 8) tables of
 ``metrics_masked_kernel``, which also give the bias, the Nash-Sutcliffe skill and per-node scores.
 
+``QuantileLoss`` / ``QuantileMetrics``: the pinball criterion of a (..., P, Q) quantile forecast and
+its calibration scores (coverage, pinball, interval width, crossing rate), on the same kernels' plan.
+
 HIP tensors only: there is no CPU fallback.
 """
 import math
@@ -280,4 +283,216 @@ class ForecastMetrics:
         rows = torch.tensor([self.rows], dtype=torch.int64, device=self.table.device)
         dist.all_reduce(rows)
         self.rows = int(rows.item())
+        return self
+
+
+# ---- quantile forecasts ------------------------------------------------------------------------
+MAX_QUANTILES = 16  # include/dstagnn.h DSTAGNN_MAX_QUANTILES
+
+
+def check_quantiles(quantiles, who="quantiles"):
+    """The level rule (include/dstagnn.h): 1 <= Q <= 16 levels, each strictly inside (0, 1),
+    strictly increasing, all of it as the fp32 values the kernels hold.  Returns the levels as a
+    tuple of Python floats; a ValueError that names the broken rule otherwise.  No device."""
+    try:
+        levels = [float(v) for v in quantiles]
+    except TypeError:
+        raise ValueError(f"{who}: a sequence of quantile levels, got {quantiles!r}") from None
+    if not 1 <= len(levels) <= MAX_QUANTILES:
+        raise ValueError(f"{who}: between 1 and {MAX_QUANTILES} quantile levels, got {len(levels)}")
+    held = [float(np.float32(v)) for v in levels]  # what the kernels see
+    for v in held:
+        if not 0.0 < v < 1.0:  # (a NaN fails too)
+            raise ValueError(f"{who}: every quantile level must be strictly inside (0, 1), got {v!r}")
+    for a, b in zip(held, held[1:]):
+        if not a < b:
+            raise ValueError(f"{who}: the quantile levels must be strictly increasing, got {a!r} before {b!r}")
+    return tuple(levels)
+
+
+def point_index_of(quantiles):
+    """The column that serves as the point forecast: the level nearest 0.5, ties to the lower
+    index."""
+    levels = [float(np.float32(v)) for v in check_quantiles(quantiles)]
+    return min(range(len(levels)), key=lambda q: (abs(levels[q] - 0.5), q))
+
+
+class _PinballFn(torch.autograd.Function):
+    """pinball_fwd / pinball_bwd as one autograd node; saved as _HipLossFn saves."""
+
+    @staticmethod
+    def forward(ctx, y, target, levels, mask_mode, null_val):
+        loss, stat = _lib.load().pinball_fwd(y, target, levels, mask_mode, null_val)
+        ctx.save_for_backward(y, target, stat)
+        ctx.cfg = (levels, mask_mode, null_val)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        y, target, stat = ctx.saved_tensors
+        if gout.dtype != torch.float32 or not gout.is_contiguous():
+            gout = gout.float().contiguous()
+        dy = _lib.load().pinball_bwd(y, target, stat, gout, *ctx.cfg)
+        return dy, None, None, None, None
+
+
+class QuantileLoss(nn.Module):
+    """The pinball (quantile) loss of a (..., P, Q) prediction against a (..., P) target in one HIP
+    launch per direction: with d = input[..., q] - target, the term is (1 - tau_q) d for d > 0,
+    tau_q (-d) for d < 0 and 0 at d = 0 (slope 0 there), and
+
+        loss = sum over valid entries and levels of the term / (count_valid * Q).
+
+    ``quantiles``: 1 to 16 strictly increasing levels strictly inside (0, 1) (ValueError
+    otherwise), held as fp32.  ``null_val`` masks by the TARGET as ``HipLoss(null_val=)`` does (NaN:
+    the NaN targets); a masked entry gives no term and a gradient of exactly 0 to all its Q
+    predictions, and with every entry masked the loss and the gradient are 0.  ``QuantileLoss((0.5,))``
+    is half of ``HipLoss('mae')``.
+
+    ``forward(input, target)``: ``input.shape[:-1] == target.shape`` and ``input.shape[-1] == Q`` (no
+    broadcasting, ValueError), fp32 HIP tensors (RuntimeError otherwise), made contiguous if they
+    are not; a 0-dim fp32 tensor.  The target takes no gradient (one that requires it raises) and
+    the backward is once-differentiable.  ``point_index``: the column nearest 0.5."""
+
+    def __init__(self, quantiles, null_val=None):
+        super().__init__()
+        self.quantiles = check_quantiles(quantiles, "QuantileLoss")
+        self.point_index = point_index_of(self.quantiles)
+        self.null_val = null_val
+        self._cfg = (list(self.quantiles),) + mask_of(null_val)
+
+    def extra_repr(self):
+        return f"quantiles={self.quantiles}, null_val={self.null_val}"
+
+    def forward(self, input, target):
+        Q = len(self.quantiles)
+        if input.dim() < 1 or tuple(input.shape[:-1]) != tuple(target.shape) or input.shape[-1] != Q:
+            raise ValueError(f"QuantileLoss: input {tuple(input.shape)} must be target {tuple(target.shape)} with a "
+                             f"last axis of {Q} quantiles (no broadcasting)")
+        if not (input.is_cuda and target.is_cuda):
+            raise RuntimeError(HIP_ONLY)
+        if input.dtype != torch.float32 or target.dtype != torch.float32:
+            raise RuntimeError("QuantileLoss: fp32 tensors only")
+        if target.requires_grad:
+            raise RuntimeError("QuantileLoss: the target takes no gradient (detach it)")
+        input, target = input.contiguous(), target.contiguous()
+        if torch.is_grad_enabled() and input.requires_grad:
+            return _PinballFn.apply(input, target, *self._cfg)
+        return _lib.load().pinball_fwd(input, target, *self._cfg)[0]  # nothing saved
+
+
+class QuantileMetrics:
+    """Running calibration scores of (S, N, P, Q) quantile predictions against (S, N, P) targets,
+    in the mould of ``ForecastMetrics``: ``update(pred, target)`` is one launch of
+    ``metrics_quantile_kernel`` and no sync, no prediction is copied to the host.
+
+    ``table`` is (P, 2 + 3 Q) fp64 on the device and ``node_table`` (num_nodes, 2 + 3 Q) or None,
+    sums over the valid entries (``missing_value``: a number, or NaN for the NaN targets):
+    column 0 the valid count, 1 the count of crossing entries (some prediction below its lower
+    neighbour), 2 + 3 q the pinball sum of level q, 3 + 3 q the count of ``t <= pred_q``, 4 + 3 q the
+    sum of ``pred_q``.
+
+    ``scores()``: float64 arrays with one entry per horizon and a last, overall one from the column
+    sums; NaN wherever the divisor is 0.  ``count`` (P + 1,), ``crossing_rate`` (P + 1,), ``pinball``
+    (P + 1, Q), ``mean_pinball`` (P + 1,), ``coverage`` (P + 1, Q) (hits / count: a calibrated model
+    gives about tau_q), ``mean_quantile`` (P + 1, Q), and for the pairs (q, Q - 1 - q), q < Q // 2:
+    ``interval_width`` = mean_quantile[hi] - mean_quantile[lo] and ``interval_coverage`` =
+    coverage[hi] - coverage[lo], both (P + 1, Q // 2).  ``interval_coverage`` is the share of targets
+    in (pred_lo, pred_hi]; it is exact where no entry crosses (a crossing entry with pred_hi < t <=
+    pred_lo counts -1).  ``node_scores()``: the same keys per node, without the overall entry.
+    ``merge(other)`` adds another object's tables; ``all_reduce()`` sums them over the ranks."""
+
+    def __init__(self, num_for_predict, quantiles, *, missing_value=None, num_nodes=None, device=None):
+        self.P = int(num_for_predict)
+        if not 1 <= self.P <= 256:
+            raise ValueError(f"QuantileMetrics: num_for_predict must be in [1, 256], got {num_for_predict!r}")
+        self.quantiles = check_quantiles(quantiles, "QuantileMetrics")
+        self.point_index = point_index_of(self.quantiles)
+        self.Q = len(self.quantiles)
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(HIP_ONLY)
+        self.missing_value = None if missing_value is None else float(missing_value)
+        self.num_nodes = None if num_nodes is None else int(num_nodes)
+        if self.num_nodes is not None and self.num_nodes < 1:
+            raise ValueError(f"QuantileMetrics: num_nodes must be >= 1, got {num_nodes!r}")
+        self._mask = mask_of(missing_value)
+        cols = 2 + 3 * self.Q
+        self.table = torch.zeros(self.P, cols, dtype=torch.float64, device=device)
+        self.node_table = (None if self.num_nodes is None else
+                           torch.zeros(self.num_nodes, cols, dtype=torch.float64, device=device))
+
+    def reset(self):
+        self.table.zero_()
+        if self.node_table is not None:
+            self.node_table.zero_()
+
+    def update(self, pred, target):
+        if (pred.dim() < 3 or tuple(pred.shape[:-1]) != tuple(target.shape) or pred.shape[-1] != self.Q
+                or pred.shape[-2] != self.P):
+            raise ValueError(f"QuantileMetrics: pred {tuple(pred.shape)} / target {tuple(target.shape)} must be "
+                             f"(..., N, {self.P}, {self.Q}) and (..., N, {self.P})")
+        if self.num_nodes is not None and pred.shape[-3] != self.num_nodes:
+            raise ValueError(f"QuantileMetrics: pred {tuple(pred.shape)} has {pred.shape[-3]} nodes, "
+                             f"num_nodes is {self.num_nodes}")
+        if not (pred.is_cuda and target.is_cuda):
+            raise RuntimeError(HIP_ONLY)
+        if pred.numel() == 0:
+            return
+        _lib.load().metrics_update_quantile(pred.detach().contiguous(), target.detach().contiguous(),
+                                            list(self.quantiles), self._mask[0], self._mask[1], self.table,
+                                            self.node_table)
+
+    @staticmethod
+    def scores_of_table(table, overall=True):
+        """The scores of a (K, 2 + 3 Q) table of sums (a numpy array), one entry per row and, with
+        ``overall``, one more from the column sums.  NaN wherever a divisor is 0."""
+        tab = np.asarray(table, dtype=np.float64)
+        if tab.ndim != 2 or tab.shape[1] < 5 or (tab.shape[1] - 2) % 3:
+            raise ValueError(f"QuantileMetrics: a table of sums is (K, 2 + 3 Q), got {tab.shape}")
+        if overall:
+            tab = np.concatenate([tab, tab.sum(0, keepdims=True)], 0)
+        Q = (tab.shape[1] - 2) // 3
+        count = tab[:, 0].copy()
+
+        def over(a):
+            b = count if a.ndim == 1 else np.broadcast_to(count[:, None], a.shape)
+            out = np.full(a.shape, np.nan)
+            np.divide(a, b, out=out, where=b != 0)
+            return out
+        pin, cov, mq = over(tab[:, 2::3]), over(tab[:, 3::3]), over(tab[:, 4::3])
+        lo, hi = np.arange(Q // 2), Q - 1 - np.arange(Q // 2)
+        return {"count": count, "crossing_rate": over(tab[:, 1]), "pinball": pin, "mean_pinball": pin.mean(1),
+                "coverage": cov, "mean_quantile": mq, "interval_width": mq[:, hi] - mq[:, lo],
+                "interval_coverage": cov[:, hi] - cov[:, lo]}
+
+    def scores(self):
+        return self.scores_of_table(self.table.cpu().numpy())
+
+    def node_scores(self):
+        if self.node_table is None:
+            raise ValueError("QuantileMetrics: node_scores() needs num_nodes")
+        return self.scores_of_table(self.node_table.cpu().numpy(), overall=False)
+
+    def _config(self):
+        return (self.P, self.quantiles, self._mask[0], repr(self._mask[1]), self.num_nodes)
+
+    def merge(self, other):
+        """Adds ``other``'s tables into this object's (the sums are additive)."""
+        if not isinstance(other, QuantileMetrics) or other._config() != self._config():
+            raise ValueError("QuantileMetrics.merge: the other object has a different configuration")
+        self.table += other.table.to(self.table.device)
+        if self.node_table is not None:
+            self.node_table += other.node_table.to(self.node_table.device)
+        return self
+
+    def all_reduce(self):
+        """One SUM all-reduce per table when a process group is up; nothing otherwise."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return self
+        dist.all_reduce(self.table)
+        if self.node_table is not None:
+            dist.all_reduce(self.node_table)
         return self

@@ -366,14 +366,25 @@ class DSTAGNN_submodule(nn.Module):
 
     def __init__(self, DEVICE, num_of_d, nb_block, in_channels, K, nb_chev_filter, nb_time_filter, time_strides,
                  cheb_polynomials, adj_pa, adj_TMD, num_for_predict, len_input, num_of_vertices, d_model, d_k, d_v,
-                 n_heads, *, multi_feature=False):
+                 n_heads, *, multi_feature=False, quantiles=None):
         """multi_feature=True: block 0 is a multi-feature first block over the F = in_channels input
         features; the inner blocks are built for the C features block 0 hands them (pre_conv
         (D, T, 1, C), where the reference's num_of_d * nb_time_filter is wrong for F > 1), and they
         receive block 0's re_At averaged over its F features, (B, 1, h, T, T), in the broadcast form.
-        With F = 1 this is the default model, bit for bit."""
+        With F = 1 this is the default model, bit for bit.
+        quantiles=(tau_0 < ... < tau_{Q-1}) (loss.check_quantiles: 1 to 16 levels strictly inside
+        (0, 1)): a quantile head.  final_fc is Linear(128, num_for_predict * Q) with row p Q + q, forward
+        returns (B, N, num_for_predict, Q), and the module carries the persistent fp32 buffer
+        ``quantile_levels`` (Q,), ``quantiles`` and ``point_index`` (the column nearest 0.5).  None: the
+        point model, with no buffer, the same keys and the same init draws as ever."""
         super().__init__()
         self.multi_feature = bool(multi_feature)
+        self.quantiles = self.point_index = None
+        self.num_for_predict = num_for_predict
+        if quantiles is not None:
+            from .loss import check_quantiles, point_index_of
+            self.quantiles = check_quantiles(quantiles, "quantiles")
+            self.point_index = point_index_of(self.quantiles)
         inner_d = nb_time_filter if self.multi_feature else num_of_d * nb_time_filter
         self.BlockList = nn.ModuleList([DSTAGNN_block(DEVICE, num_of_d, in_channels, K, nb_chev_filter,
                                                       nb_time_filter, time_strides, cheb_polynomials, adj_pa,
@@ -384,9 +395,23 @@ class DSTAGNN_submodule(nn.Module):
                                              len_input // time_strides, d_model, d_k, d_v, n_heads)
                                for _ in range(nb_block - 1)])
         self.final_conv = nn.Conv2d(int((len_input / time_strides) * nb_block), 128, kernel_size=(1, nb_time_filter))
-        self.final_fc = nn.Linear(128, num_for_predict)
+        self.final_fc = nn.Linear(128, num_for_predict * (1 if self.quantiles is None else len(self.quantiles)))
+        if self.quantiles is not None:
+            self.register_buffer("quantile_levels", torch.tensor(self.quantiles, dtype=torch.float32))
         self.DEVICE = DEVICE
         self.to(DEVICE)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        # a checkpoint trained for other levels has the right shapes and the wrong meaning
+        theirs = state_dict.get(prefix + "quantile_levels")
+        if self.quantiles is not None and theirs is not None:
+            mine = self.quantile_levels.detach().cpu()
+            if tuple(theirs.shape) != tuple(mine.shape) or not torch.equal(theirs.detach().cpu().float(), mine):
+                def show(t):
+                    return "(" + ", ".join(f"{float(v):.6g}" for v in t.flatten()) + ")"
+                raise ValueError(f"the checkpoint's quantile_levels {show(theirs)} differ from the model's "
+                                 f"{show(mine)}")
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     def forward(self, x):
         need_concat = []
@@ -400,23 +425,31 @@ class DSTAGNN_submodule(nn.Module):
             need_concat.append(x)
         # cat -> final_conv -> [..., -1] -> final_fc as one HIP head op (head.hip): the
         # concatenation is never materialised (model/DSTAGNN_my.py:276-280)
-        return DSTAGNNHeadFunction.apply(self.final_conv.weight, self.final_conv.bias, self.final_fc.weight,
-                                         self.final_fc.bias, *need_concat)
+        y = DSTAGNNHeadFunction.apply(self.final_conv.weight, self.final_conv.bias, self.final_fc.weight,
+                                      self.final_fc.bias, *need_concat)
+        if self.quantiles is None:
+            return y
+        return y.view(y.shape[0], y.shape[1], self.num_for_predict, len(self.quantiles))  # row p Q + q
 
 
 def make_model(DEVICE, num_of_d, nb_block, in_channels, K, nb_chev_filter, nb_time_filter, time_strides, adj_mx,
                adj_pa, adj_TMD, num_for_predict, len_input, num_of_vertices, d_model, d_k, d_v, n_heads,
-               *, multi_feature=False):
+               *, multi_feature=False, quantiles=None):
     """model/DSTAGNN_my.py:282-297: scaled Laplacian + Chebyshev polynomials, then the
     xavier (dim>1) / U(0,1) (dim<=1, LayerNorm gamma/beta included) initialisation.
     multi_feature=True: a model whose first block takes all F = in_channels = num_of_d input
-    features, 1 <= F <= 8 (DSTAGNN_submodule)."""
+    features, 1 <= F <= 8 (DSTAGNN_submodule).  quantiles=(...): a quantile head, output
+    (B, N, num_for_predict, Q) (DSTAGNN_submodule); the levels are checked before anything is built."""
+    if quantiles is not None:
+        from .loss import check_quantiles
+        quantiles = check_quantiles(quantiles, "quantiles")
     L_tilde = scaled_Laplacian(adj_mx)
     Lt = L_tilde if isinstance(L_tilde, np.ndarray) else L_tilde.cpu().numpy()
     cheb_polynomials = [torch.from_numpy(np.asarray(c)).type(torch.FloatTensor) for c in cheb_polynomial(Lt, K)]
     model = DSTAGNN_submodule(DEVICE, num_of_d, nb_block, in_channels, K, nb_chev_filter, nb_time_filter,
                               time_strides, cheb_polynomials, adj_pa, adj_TMD, num_for_predict, len_input,
-                              num_of_vertices, d_model, d_k, d_v, n_heads, multi_feature=multi_feature)
+                              num_of_vertices, d_model, d_k, d_v, n_heads, multi_feature=multi_feature,
+                              quantiles=quantiles)
     for p in model.parameters():
         if p.dim() > 1:
             nn.init.xavier_uniform_(p)

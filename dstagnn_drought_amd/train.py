@@ -33,6 +33,9 @@ process per GPU with torch.distributed over RCCL:
     HIP path, optionally leaving targets equal to a missing value out of the loss.  With
     ``input_fill`` (input_options(), ``--input-fill``) the streamed inputs equal to that value are
     imputed in the gather launch and the statistics taken over the observed values.
+  * with ``quantiles`` (quantile_options(), ``--quantiles 0.1,0.5,0.9``) the model has a quantile head
+    ((B, N, P, Q) forecasts), the criterion is the pinball loss.QuantileLoss, and the test scores gain
+    coverage / pinball / interval width / crossing rate (loss.QuantileMetrics).
 """
 import argparse
 import configparser
@@ -220,33 +223,49 @@ def evaluate_on_test_masked(net, test_loader, test_target_tensor, sw, epoch, *, 
     return (excel_list, metrics.node_scores()) if per_node else excel_list
 
 
-def score_batches(net, x, y, batch_size, missing_value=None, per_node=False):
+def score_batches(net, x, y, batch_size, missing_value=None, per_node=False, quantiles=None):
     """The test-set scores of `net` over (x, y), batched and sharded as eval_batches does it
     (batches of `batch_size` cut with _cut, round-robin over the ranks), accumulated on the device
     and summed over the ranks at the end.  Returns the loss.ForecastMetrics: masked by
     missing_value when there is one, with the node table when per_node; with neither, the
-    unmasked (P, 4) object.  x, y: tensors, or the arrays of a windows.WindowedSeries split."""
-    from .loss import ForecastMetrics
+    unmasked (P, 4) object.  x, y: tensors, or the arrays of a windows.WindowedSeries split.
+    quantiles (the levels of a quantile model): the ForecastMetrics is fed the ``point_index`` column
+    of the (B, N, P, Q) forecasts, and a loss.QuantileMetrics, fed all of them in the same pass, is
+    returned beside it: (ForecastMetrics, QuantileMetrics)."""
+    from .loss import ForecastMetrics, QuantileMetrics
     rank, world = _world()
-    metrics = ForecastMetrics(y.shape[-1], 0.0, x.device, missing_value=missing_value,
-                              num_nodes=y.shape[-2] if per_node else None)
+    nodes = y.shape[-2] if per_node else None
+    metrics = ForecastMetrics(y.shape[-1], 0.0, x.device, missing_value=missing_value, num_nodes=nodes)
+    qm = None
+    if quantiles is not None:
+        qm = QuantileMetrics(y.shape[-1], quantiles, missing_value=missing_value, num_nodes=nodes, device=x.device)
     with torch.no_grad():
         for b in list(range(0, x.shape[0], batch_size))[rank::world]:
             xb, yb = _cut(x, y, b, b + batch_size)
-            metrics.update(net(xb), yb)
-    return metrics.all_reduce()
+            out = net(xb)
+            if qm is not None:
+                qm.update(out, yb)
+                out = out[..., qm.point_index]
+            metrics.update(out, yb)
+    return metrics.all_reduce() if qm is None else (metrics.all_reduce(), qm.all_reduce())
 
 
 def predict_and_save_results_mstgcn(net, data_loader, data_target_tensor, global_step, _mean, _std, params_path,
-                                    type, missing_value=None):
+                                    type, missing_value=None, quantiles=None):
     """lib/utils1.py:441-510: predictions over `data_loader`, saved with the de-normalised
     inputs as ``output_epoch_{step}_{type}.npz`` (keys input, prediction,
     data_target_tensor); returns the per-horizon [MAE, RMSE, MAPE] list + the overall three.
     missing_value (a number, or NaN for the NaN targets): the targets equal to it are left out of
     the list, which then comes from the masked loss.ForecastMetrics on the device, each batch
     scored against its slice of the targets in loader order (sklearn raises on a NaN target and
-    scores a sentinel as data); the file is saved as before."""
+    scores a sentinel as data); the file is saved as before.
+    quantiles (the levels of a quantile model): ``prediction`` is stored as (S, N, P, Q) with the
+    levels beside it (key ``quantiles``), and the list is taken from the ``point_index`` column."""
     net.train(False)
+    point = None
+    if quantiles is not None:
+        from .loss import point_index_of
+        point = point_index_of(quantiles)
     with torch.no_grad():
         metrics, at = None, 0
         if missing_value is not None:
@@ -260,13 +279,17 @@ def predict_and_save_results_mstgcn(net, data_loader, data_target_tensor, global
             inputs.append(encoder_inputs[:, :, 0:1].cpu().numpy())
             outputs = net(encoder_inputs)
             if metrics is not None:
-                metrics.update(outputs, target_dev[at:at + outputs.shape[0]])
+                metrics.update(outputs if point is None else outputs[..., point],
+                               target_dev[at:at + outputs.shape[0]])
                 at += outputs.shape[0]
             prediction.append(outputs.detach().cpu().numpy())
         inputs = data_io.re_normalization(np.concatenate(inputs, 0), _mean, _std)
         prediction = np.concatenate(prediction, 0)
+        extra = {} if quantiles is None else {"quantiles": np.asarray(quantiles, dtype=np.float32)}
         np.savez(os.path.join(params_path, 'output_epoch_%s_%s' % (global_step, type)), input=inputs,
-                 prediction=prediction, data_target_tensor=data_target_tensor)
+                 prediction=prediction, data_target_tensor=data_target_tensor, **extra)
+        if point is not None:
+            prediction = prediction[..., point]
         if metrics is not None:
             assert data_target_tensor.shape[0] == at
             return metrics.compute()
@@ -283,9 +306,10 @@ def predict_and_save_results_mstgcn(net, data_loader, data_target_tensor, global
     return excel_list
 
 
-def build(config, device, multi_feature=None):
+def build(config, device, multi_feature=None, quantiles=None):
     """Graphs + model exactly as train_DSTAGNN_my.py:62-107 (model built on CPU, then moved).
-    multi_feature (None: the [Training] key, model_options()) goes to make_model."""
+    multi_feature (None: the [Training] key, model_options()) and quantiles (None: the [Training]
+    key, quantile_options(); absent: the point model) go to make_model."""
     dc, tc = config['Data'], config['Training']
     N = int(dc['num_of_vertices'])
     if dc['dataset_name'] in ['PEMS04', 'PEMS08', 'PEMS07', 'PEMS03']:
@@ -300,7 +324,8 @@ def build(config, device, multi_feature=None):
                      int(tc['nb_chev_filter']), int(tc['nb_time_filter']), 1, adj_merge, adj_pa, adj_TMD,
                      int(dc['num_for_predict']), int(dc['len_input']), N, int(tc['d_model']), int(tc['d_k']),
                      int(tc['d_k']), int(tc['n_heads']),
-                     multi_feature=model_options(tc) if multi_feature is None else bool(multi_feature))
+                     multi_feature=model_options(tc) if multi_feature is None else bool(multi_feature),
+                     quantiles=quantile_options(tc) if quantiles is None else quantiles)
     return net.to(device)
 
 
@@ -582,6 +607,34 @@ def model_options(tc):
     return tc.getboolean('multi_feature', fallback=False)
 
 
+def quantile_options(tc):
+    """Optional [Training] key ``quantiles`` of a configuration (a ConfigParser section), a comma
+    separated list such as ``0.1, 0.5, 0.9`` -> a tuple of levels checked by loss.check_quantiles
+    (ValueError for an empty list, more than 16, a level outside (0, 1), unsorted or repeated
+    levels).  Absent: None, today's point model and criterion."""
+    text = tc.get('quantiles', None)
+    return None if text is None else parse_quantiles(text)
+
+
+def parse_quantiles(text):
+    """``"0.1,0.5,0.9"`` -> (0.1, 0.5, 0.9), checked by loss.check_quantiles."""
+    from .loss import check_quantiles
+    try:
+        levels = [float(v) for v in str(text).replace(';', ',').split(',') if v.strip()]
+    except ValueError:
+        raise ValueError(f"quantiles: a comma separated list of numbers, got {text!r}") from None
+    return check_quantiles(levels, "quantiles")
+
+
+def check_quantile_loss(name, quantiles):
+    """``loss_function`` (or ``--loss``) beside ``quantiles``: only absent or ``pinball``."""
+    if quantiles is not None and name is not None and name != 'pinball':
+        raise ValueError(f"quantiles are trained with the pinball loss: loss_function must be absent or 'pinball' "
+                         f"when quantiles are given, got {name!r}")
+    if quantiles is None and name == 'pinball':
+        raise ValueError("loss_function = pinball needs quantiles ([Training] quantiles or quantiles=)")
+
+
 def check_input_features(F, in_channels):
     """The data's feature count against the model's ``in_channels`` (run() with multi_feature): a
     ValueError that names both, instead of a shape error out of the first forward."""
@@ -590,13 +643,19 @@ def check_input_features(F, in_channels):
                          f"a multi-feature model takes exactly in_channels features")
 
 
-def make_criterion(name=None, missing_value=None, smooth_l1_beta=1.0, huber_delta=1.0):
-    """The driver's criterion.  With no name and no missing value: ``nn.SmoothL1Loss()``
+def make_criterion(name=None, missing_value=None, smooth_l1_beta=1.0, huber_delta=1.0, quantiles=None):
+    """The driver's criterion.  With quantiles: loss.QuantileLoss(quantiles, null_val=missing_value)
+    (the name absent or ``pinball``: check_quantile_loss).  Otherwise, as ever:
+    With no name and no missing value: ``nn.SmoothL1Loss()``
     (train_DSTAGNN_my.py:132), the object every run without the keys of loss_options() has
     always used.  Any explicit name (``smooth_l1`` included) or missing value: a loss.HipLoss,
     one HIP launch per direction; a missing value alone masks the default ``smooth_l1``.  Raises
     ValueError for an unknown name and for ``masked_mae`` / ``masked_mse`` without a missing
     value."""
+    check_quantile_loss(name, quantiles)
+    if quantiles is not None:
+        from .loss import QuantileLoss
+        return QuantileLoss(quantiles, null_val=missing_value)
     if name is None and missing_value is None:
         return nn.SmoothL1Loss()
     from .loss import HipLoss
@@ -705,7 +764,8 @@ def load_best(net, path):
 
 def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches=None, root='myexperiments',
         log=print, max_grad_norm=None, weight_decay=None, loss=None, missing_value=None, stream_windows=None,
-        input_fill=None, input_max_gap=None, test_metrics=None, node_scores=None, multi_feature=None):
+        input_fill=None, input_max_gap=None, test_metrics=None, node_scores=None, multi_feature=None,
+        quantiles=None):
     """Whole script: data, graphs, model, training, best-checkpoint test loss.  The optional
     [Training] keys of training_options() switch clipping / weight decay on; max_grad_norm /
     weight_decay given here override them.  loss / missing_value override the keys of
@@ -731,7 +791,14 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
     list of predict_and_save_results_mstgcn), ``test_scores`` and ``test_node_scores``.
     multi_feature (None: the [Training] key of model_options(), off when absent): the model's first
     block takes all ``in_channels`` features of the data (both data paths feed (B, N, F, T));
-    ValueError when the data's F differs from in_channels."""
+    ValueError when the data's F differs from in_channels.
+    quantiles (None: the [Training] key of quantile_options(), absent: a point model): a tuple of
+    levels or a ``"0.1,0.5,0.9"`` string.  The model gets a quantile head, the criterion is
+    loss.QuantileLoss(levels, null_val=missing_value) for training, validation and test loss (a
+    loss name other than ``pinball`` beside it is a ValueError, raised before any data is read), and
+    with test_metrics the existing scores are taken from the ``point_index`` column (same keys and
+    files) while the result gains ``test_quantile_scores`` (and ``test_node_quantile_scores`` with
+    node_scores), written as ``test_quantile_scores.json`` (and ``test_node_quantile_scores.npz``)."""
     config = configparser.ConfigParser()
     config.read(config_path)
     dc, tc = config['Data'], config['Training']
@@ -742,6 +809,14 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
         stream_windows = tc.getboolean('stream_windows', fallback=False)
     cfg_loss, cfg_missing, beta, delta = loss_options(tc)
     missing_value = cfg_missing if missing_value is None else missing_value
+    if quantiles is None:
+        quantiles = quantile_options(tc)
+    elif isinstance(quantiles, str):
+        quantiles = parse_quantiles(quantiles)
+    else:
+        from .loss import check_quantiles
+        quantiles = check_quantiles(quantiles, "quantiles")
+    check_quantile_loss(cfg_loss if loss is None else loss, quantiles)
     cfg_scores, cfg_nodes = scoring_options(tc)
     node_scores = cfg_nodes if node_scores is None else bool(node_scores)
     test_metrics = (cfg_scores if test_metrics is None else bool(test_metrics)) or node_scores
@@ -773,7 +848,7 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
     multi_feature = model_options(tc) if multi_feature is None else bool(multi_feature)
     if multi_feature:
         check_input_features(train_x.shape[2], tc['in_channels'])
-    net = build(config, device, multi_feature)
+    net = build(config, device, multi_feature, quantiles)
     set_direct_grads(net)  # the loop only uses loss.backward() + .grad
     if dropout is not None:
         set_dropout(net, dropout)
@@ -787,7 +862,7 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
     bs = int(tc['batch_size'])
     n_epochs = int(tc['epochs']) if epochs is None else int(epochs)
     cfg_norm, cfg_wd, decoupled = training_options(tc)
-    criterion = make_criterion(cfg_loss if loss is None else loss, missing_value, beta, delta)
+    criterion = make_criterion(cfg_loss if loss is None else loss, missing_value, beta, delta, quantiles)
     best_epoch, best_val, history = fit(net, train_x, train_y, val_x, val_y, epochs=n_epochs,
                                         start_epoch=int(tc['start_epoch']), batch_size=bs,
                                         lr=float(tc['learning_rate']), params_path=params_path,
@@ -803,15 +878,20 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
     result = {"best_epoch": best_epoch, "best_val": best_val, "test_loss": test_loss, "history": history,
               "params_path": params_path, "net": net}
     if test_metrics:
-        result.update(_score_test_split(net, test_x, test_y, bs, missing_value, node_scores, params_path, log))
+        result.update(_score_test_split(net, test_x, test_y, bs, missing_value, node_scores, params_path, log,
+                                        quantiles))
     return result
 
 
-def _score_test_split(net, test_x, test_y, bs, missing_value, per_node, params_path, log):
-    """run()'s test-set scores: score_batches, rank 0's log lines and files, the result keys."""
+def _score_test_split(net, test_x, test_y, bs, missing_value, per_node, params_path, log, quantiles=None):
+    """run()'s test-set scores: score_batches, rank 0's log lines and files, the result keys.  With
+    quantiles the point scores come from the ``point_index`` column and the calibration scores are
+    logged (coverage per level and mean pinball, one line per horizon) and written beside them."""
     import json
     rank, _ = _world()
-    metrics = score_batches(net, test_x, test_y, bs, missing_value, per_node)
+    metrics, qm = score_batches(net, test_x, test_y, bs, missing_value, per_node, quantiles), None
+    if quantiles is not None:
+        metrics, qm = metrics
     excel_list, scores = metrics.compute(), metrics.scores()
     out = {"test_metrics": excel_list, "test_scores": scores}
     if per_node:
@@ -824,6 +904,21 @@ def _score_test_split(net, test_x, test_y, bs, missing_value, per_node, params_p
             json.dump(dict({k: v.tolist() for k, v in scores.items()}, list=excel_list), f, indent=1)
         if per_node:
             np.savez(os.path.join(params_path, 'test_node_scores.npz'), **out["test_node_scores"])
+    if qm is not None:
+        qs = out["test_quantile_scores"] = qm.scores()
+        if per_node:
+            out["test_node_quantile_scores"] = qm.node_scores()
+        if rank == 0:
+            for i in range(qm.P + 1):
+                log('Test quantiles %s: ' % ('overall' if i == qm.P else 'horizon %d' % i)
+                    + ' '.join('coverage[%g] %.4f' % (tau, qs["coverage"][i, q]) for q, tau in enumerate(qm.quantiles))
+                    + ' mean_pinball %.4f' % qs["mean_pinball"][i])
+            with open(os.path.join(params_path, 'test_quantile_scores.json'), 'w') as f:
+                json.dump(dict({k: v.tolist() for k, v in qs.items()}, quantiles=list(qm.quantiles),
+                               point_index=qm.point_index), f, indent=1)
+            if per_node:
+                np.savez(os.path.join(params_path, 'test_node_quantile_scores.npz'),
+                         **out["test_node_quantile_scores"])
     return out
 
 
@@ -885,6 +980,10 @@ def arg_parser():
     ap.add_argument("--multi-feature", action="store_true", default=None,
                     help="the first block takes all in_channels input features (1 <= in_channels <= 8) instead of "
                          "failing for 1 < in_channels < nb_time_filter (overrides [Training] multi_feature)")
+    ap.add_argument("--quantiles", default=None,
+                    help="comma separated quantile levels, e.g. 0.1,0.5,0.9: a quantile head trained with the pinball "
+                         "loss; --test-metrics then also reports coverage, pinball, interval width and crossing rate "
+                         "(overrides [Training] quantiles)")
     return ap
 
 
@@ -901,7 +1000,8 @@ def main(argv=None):
             max_batches=a.max_batches, root=a.out_root, max_grad_norm=a.max_grad_norm,
             weight_decay=a.weight_decay, loss=a.loss, missing_value=a.missing_value,
             stream_windows=a.stream_windows, input_fill=a.input_fill, input_max_gap=a.input_max_gap,
-            test_metrics=a.test_metrics, node_scores=a.node_scores, multi_feature=a.multi_feature)
+            test_metrics=a.test_metrics, node_scores=a.node_scores, multi_feature=a.multi_feature,
+            quantiles=a.quantiles)
     finally:
         if world > 1:
             dist.destroy_process_group()

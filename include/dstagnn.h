@@ -442,6 +442,64 @@ int dstagnn_metrics_accumulate_masked(int64_t B, int64_t N, int P, const float* 
                                       dstagnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Quantile forecasts (loss.hip): the pinball criterion and the calibration sums.
+ *
+ * Levels: tau_0 < tau_1 < ... < tau_{Q-1}, each strictly inside (0, 1), strictly increasing,
+ * 1 <= Q <= DSTAGNN_MAX_QUANTILES; anything else is DSTAGNN_E_ARG.  They are fp32; the kernels
+ * use tau and 1 - tau, the latter formed once on the host in fp32.
+ * Layout: a quantile prediction is (M, Q) floats, q fastest (a (B, N, P, Q) head output with
+ * M = B N P); the target stays (M).
+ * Pinball term of d = y_q - t (the library's sign convention, d in fp32):
+ *   d > 0: (1 - tau_q) d, slope 1 - tau_q      d < 0: tau_q (-d), slope -tau_q
+ *   d = 0: 0, slope 0 (DSTAGNN_LOSS_MAE's sign(0) = 0)      a NaN d stays NaN
+ * (Q = 1, tau = 0.5: half of DSTAGNN_LOSS_MAE.)  An entry is valid by its TARGET under the rule
+ * above (DSTAGNN_MASK_*; selected out, never multiplied by zero).
+ *   loss = sum over valid entries and levels of the term / (count_valid Q)
+ * no valid entry: loss 0, gradient 0; a NaN prediction at a valid entry: a NaN loss.  Terms in
+ * fp32, every add in fp64 in a fixed order: the same bits on every call.
+ *
+ * dstagnn_pinball_forward: y (m, Q), target (m) -> loss (one float), stat (two doubles: the
+ * fp64 sum of the terms and count_valid).  scratch: dstagnn_pinball_scratch_bytes(m, Q) bytes.
+ * dstagnn_pinball_backward: dy[i, q] = slope gout / (count_valid Q) on valid entries, exactly 0
+ * at masked entries and where d = 0; count_valid from the forward's stat and gout (one float on
+ * the device, NULL means 1) are read on the device: no host synchronisation.
+ * A null pointer, a level or mask mode outside the rules -> DSTAGNN_E_ARG; m < 1 or
+ * m Q >= 2^31 -> DSTAGNN_E_SHAPE; a short scratch -> DSTAGNN_E_SPACE.
+ *
+ * dstagnn_metrics_accumulate_quantile: pred (B, N, P, Q), target (B, N, P) -> htable
+ * (P, 2 + 3 Q) and, unless NULL, ntable (N, 2 + 3 Q) doubles on the device, RUNNING tables the
+ * call adds to (zero them to start), over the valid entries:
+ *   0        count of valid entries
+ *   1        count of crossing entries (some y_{q+1} < y_q: the Q predictions are not non-decreasing)
+ *   2 + 3 q  sum of the pinball term of level q (fp32 term, fp64 add)
+ *   3 + 3 q  count of t <= y_q (fp32 compare, exact)
+ *   4 + 3 q  sum of y_q, each cast to double (exact terms)
+ * One launch of ceil(N / (256 / P)) workgroups, fixed order, no atomics on floats.
+ * 1 <= P <= 256, 1 <= Q <= 16, B, N >= 1 and B N P Q < 2^31, else DSTAGNN_E_SHAPE; a null cfg /
+ * pred / target / htable / scratch, an unknown mask mode or a level outside the rule ->
+ * DSTAGNN_E_ARG; scratch smaller than dstagnn_metrics_quantile_scratch_bytes(B, N, P, Q) (0 for
+ * a shape it rejects) -> DSTAGNN_E_SPACE.  All of it is checked before anything touches the device.
+ * ------------------------------------------------------------------------------------- */
+#define DSTAGNN_MAX_QUANTILES 16
+typedef struct {
+  int mask_mode;     /* DSTAGNN_MASK_* */
+  float null_val;    /* DSTAGNN_MASK_NEQ only */
+  int num_quantiles; /* Q */
+  float tau[DSTAGNN_MAX_QUANTILES]; /* the first Q are read */
+} dstagnn_pinball_cfg;
+int64_t dstagnn_pinball_scratch_bytes(int64_t m, int num_quantiles);
+int dstagnn_pinball_forward(const dstagnn_pinball_cfg* cfg, int64_t m, const float* y, const float* target,
+                            float* loss, double* stat, void* scratch, size_t scratch_bytes,
+                            dstagnn_stream_t stream);
+int dstagnn_pinball_backward(const dstagnn_pinball_cfg* cfg, int64_t m, const float* y, const float* target,
+                             const double* stat, const float* gout, float* dy, dstagnn_stream_t stream);
+int64_t dstagnn_metrics_quantile_scratch_bytes(int64_t B, int64_t N, int P, int num_quantiles);
+int dstagnn_metrics_accumulate_quantile(int64_t B, int64_t N, int P, const dstagnn_pinball_cfg* cfg,
+                                        const float* pred, const float* target, double* htable,
+                                        double* ntable /* may be NULL */, void* scratch, size_t scratch_bytes,
+                                        dstagnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Training windows cut from the raw series on the device (windows.hip): what prepareData.py
  * (:63-161) materialises once per label position, per batch instead.
  *

@@ -23,6 +23,15 @@
 
     python tools/bench_loss.py --mode metrics --out profiles/metrics_masked_ab.json
 
+  (4) --mode quantile: the pinball criterion (forward + backward, timed as (1)) and one calibration
+      update (QuantileMetrics.update against the same sums written as torch tensor expressions,
+      --iters updates between two device events) at the head shapes (B, N, P, Q) of PEMS08
+      (32, 170, 12, 3) and GAMBIA (4, 2139, 12, 3), NaN marker on 30 % of the targets.  The torch
+      side is what a user writes today: tensor expressions on the GPU, no host copy.  Also the full
+      training step of the PEMS08-shaped model (nb_block=4, B=32), point head against quantile head.
+
+    python tools/bench_loss.py --mode quantile --out profiles/quantile_ab.json
+
 The JSON carries the library stamp (dstagnn_drought_amd._lib.build_stamp).  There is no fallback:
 without a HIP device the tool fails."""
 import argparse
@@ -160,6 +169,153 @@ def time_metrics(torch, dev, shape, batches, passes, rounds):
             "spread": {k: round((max(r) - min(r)) / med[k], 4) for k, r in runs.items()}}
 
 
+QUANTILES = (0.1, 0.5, 0.9)
+
+
+def _windows(torch, variants, iters, rounds):
+    """--rounds alternating windows of --iters calls between two device events: us per call."""
+    runs = {k: [] for k in variants}
+    for _ in range(rounds):
+        for k, f in variants.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                f()
+            e1.record()
+            e1.synchronize()
+            runs[k].append(round(e0.elapsed_time(e1) / iters * 1e3, 3))
+    med = {k: statistics.median(r) for k, r in runs.items()}
+    return runs, med, {k: round((max(r) - min(r)) / med[k], 4) for k, r in runs.items()}
+
+
+def time_quantile(torch, dev, shape, iters, rounds, warmup):
+    from dstagnn_drought_amd import QuantileLoss, QuantileMetrics
+    B, N, P = shape
+    Q = len(QUANTILES)
+    gen = torch.Generator(device=dev).manual_seed(11)
+    t = 3.0 * torch.randn(shape, device=dev, generator=gen)
+    y = (t[..., None] + torch.randn(B, N, P, Q, device=dev, generator=gen)
+         + torch.linspace(-1.0, 1.0, Q, device=dev)).requires_grad_(True)
+    t[torch.rand(shape, device=dev, generator=gen) < 0.3] = float("nan")
+    tau = torch.tensor(QUANTILES, dtype=torch.float32, device=dev)
+    omt = 1.0 - tau
+    hip = QuantileLoss(QUANTILES, null_val=float("nan"))
+
+    def torch_loss(y, t):  # the masked pinball mean as tensor expressions (no boolean indexing: no sync)
+        valid = ~torch.isnan(t)
+        d = y - torch.where(valid, t, torch.zeros_like(t))[..., None]
+        term = torch.where(d > 0, omt * d, tau * -d)
+        return torch.where(valid[..., None], term, torch.zeros_like(term)).sum() / (valid.sum() * Q).clamp(min=1)
+
+    def step(c):
+        y.grad = None
+        c(y, t).backward()
+
+    for c in (torch_loss, hip):
+        for _ in range(warmup):
+            step(c)
+    torch.cuda.synchronize()
+    runs, med, spread = _windows(torch, {"torch": lambda: step(torch_loss), "hip": lambda: step(hip)}, iters, rounds)
+    with torch.no_grad():
+        agree = abs(float(torch_loss(y, t)) - float(hip(y, t)))
+    out = {"shape": [B, N, P, Q], "fwd_bwd": {"us_per_fwd_bwd_runs": runs, "median_us": med, "spread": spread,
+                                              "hip_over_torch": round(med["hip"] / med["torch"], 4),
+                                              "abs_loss_difference": agree}}
+
+    # one calibration update: the (P, 2 + 3 Q) and (N, 2 + 3 Q) running tables
+    yd = y.detach()
+    qm = QuantileMetrics(P, QUANTILES, missing_value=float("nan"), num_nodes=N, device=dev)
+    ht = torch.zeros(P, 2 + 3 * Q, dtype=torch.float64, device=dev)
+    nt = torch.zeros(N, 2 + 3 * Q, dtype=torch.float64, device=dev)
+
+    def torch_update():
+        valid = ~torch.isnan(t)
+        tz = torch.where(valid, t, torch.zeros_like(t))
+        d = yd - tz[..., None]
+        v3 = valid[..., None]
+        term = torch.where(v3 & (d != 0), torch.where(d > 0, omt * d, tau * -d), torch.zeros_like(d)).double()
+        hit = (v3 & (tz[..., None] <= yd)).double()
+        sy = torch.where(v3, yd, torch.zeros_like(yd)).double()
+        cross = (valid & (yd[..., 1:] < yd[..., :-1]).any(-1)).double()
+        cols = torch.cat([valid.double()[..., None], cross[..., None],
+                          torch.stack([term, hit, sy], -1).reshape(B, N, P, 3 * Q)], -1)
+        ht.add_(cols.sum((0, 1)))
+        nt.add_(cols.sum((0, 2)))
+
+    for _ in range(max(warmup // 10, 10)):
+        torch_update()
+        qm.update(yd, t)
+    torch.cuda.synchronize()
+    qm.reset(), ht.zero_(), nt.zero_()
+    torch_update()
+    qm.update(yd, t)
+    diff = float((qm.table - ht).abs().max() / ht.abs().max())
+    runs, med, spread = _windows(torch, {"torch": torch_update, "hip": lambda: qm.update(yd, t)}, iters, rounds)
+    out["metrics_update"] = {"us_per_update_runs": runs, "median_us": med, "spread": spread,
+                             "hip_over_torch": round(med["hip"] / med["torch"], 4),
+                             "worst_table_difference_relative_to_its_largest_entry": diff}
+    return out
+
+
+def time_model_step(torch, dev, rounds, steps=40, warmup=10):
+    """The full training step (forward, criterion, backward, HipAdam) of the PEMS08-shaped model
+    (make_model nb_block=4, B=32): the point model with the driver's default nn.SmoothL1Loss
+    against the quantile model (final_fc 12 -> 36 columns) with QuantileLoss."""
+    import bench
+    import dstagnn_drought_amd as D
+    from dstagnn_drought_amd import train as TR
+    c = bench.CFG
+    B, N, T, K, h, Dm, dk, C = c["B"], c["N"], c["T"], c["K"], c["n_heads"], c["d_model"], c["d_k"], c["C"]
+    tmd, pa = bench.synth_graph(N)
+    gen = torch.Generator(device=dev).manual_seed(5)
+    x = torch.randn(B, N, 1, T, device=dev, generator=gen)
+    t = torch.randn(B, N, T, device=dev, generator=gen)
+    variants = {}
+    for name, q in (("point", None), ("quantile", QUANTILES)):
+        torch.manual_seed(1)
+        net = D.set_direct_grads(D.make_model(dev, 1, 4, 1, K, C, C, 1, tmd, pa, tmd, T, T, N, Dm, dk, dk, h,
+                                              quantiles=q).train())
+        crit = torch.nn.SmoothL1Loss().to(dev) if q is None else D.QuantileLoss(q)
+        opt = TR.make_adam(net.parameters(), 1e-3)
+
+        def step(net=net, crit=crit, opt=opt):
+            opt.zero_grad()
+            crit(net(x), t).backward()
+            opt.step()
+        variants[name] = step
+    for f in variants.values():
+        for _ in range(warmup):
+            f()
+    torch.cuda.synchronize()
+    runs, med, spread = _windows(torch, variants, steps, rounds)
+    return {"model": "make_model nb_block=4, PEMS08 shape, B=32, train mode, HipAdam", "steps_per_window": steps,
+            "us_per_step_runs": runs, "median_us": med, "spread": spread,
+            "quantile_over_point": round(med["quantile"] / med["point"], 4)}
+
+
+def main_quantile(a):
+    import torch
+    from dstagnn_drought_amd import _lib
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_loss.py measures on the GPU only: no HIP device")
+    dev = torch.device("cuda:0")
+    rec = {"what": f"pinball criterion forward + backward and one calibration update at Q = {len(QUANTILES)}, NaN marker "
+                   f"on 30 % of the targets, us per call between device events, {a.rounds} alternating windows x "
+                   f"{a.iters} calls (tools/bench_loss.py --mode quantile)",
+           "variants": {"torch": "the same quantities as torch tensor expressions on the GPU",
+                        "hip": "QuantileLoss (pinball_fwd_kernel + pinball_bwd_kernel) / QuantileMetrics.update with the "
+                               "node table (metrics_quantile_kernel)"},
+           "quantiles": list(QUANTILES), "stamp": _lib.build_stamp(),
+           "quantile": {name: time_quantile(torch, dev, SHAPES[name], a.iters, a.rounds, a.warmup)
+                        for name in ("PEMS08", "GAMBIA")},
+           "model_step": time_model_step(torch, dev, a.rounds)}
+    print(json.dumps(rec))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(rec, f, indent=1)
+
+
 def main_metrics(a):
     import torch
     from dstagnn_drought_amd import _lib
@@ -184,18 +340,25 @@ def main_metrics(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("loss", "metrics"), default="loss",
-                    help="loss: (1) and (2) above; metrics: (3), the masked scoring pass")
+    ap.add_argument("--mode", choices=("loss", "metrics", "quantile"), default="loss",
+                    help="loss: (1) and (2) above; metrics: (3), the masked scoring pass; quantile: (4), the pinball "
+                         "criterion and one calibration update")
     ap.add_argument("--passes", type=int, default=300, help="--mode metrics: passes per window")
     ap.add_argument("--iters", type=int, default=2000, help="iterations per window (>= 200)")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=500)
     ap.add_argument("--batches", type=int, default=64)
     ap.add_argument("--out", default=None,
-                    help="default: profiles/loss_ab.json (profiles/metrics_masked_ab.json with --mode metrics)")
+                    help="default: profiles/loss_ab.json (profiles/metrics_masked_ab.json with --mode metrics, "
+                         "profiles/quantile_ab.json with --mode quantile)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "metrics_masked_ab.json" if a.mode == "metrics" else "loss_ab.json")
+        a.out = os.path.join(ROOT, "profiles", {"metrics": "metrics_masked_ab.json",
+                                                "quantile": "quantile_ab.json"}.get(a.mode, "loss_ab.json"))
+    if a.mode == "quantile":
+        if a.iters < 200:
+            ap.error("--iters must be at least 200")
+        return main_quantile(a)
     if a.mode == "metrics":
         if a.passes < 1 or a.rounds < 3:
             ap.error("--mode metrics needs --passes >= 1 and --rounds >= 3")
