@@ -1056,7 +1056,17 @@ struct Bwd {
     } else {
       DS_TRY(colsum_on(ks.side(), w.dtc, m.BN * m.C, m.T, 1, gd.fcmy_b));
     }
-    {
+    // the fused backward's compact rows with all six gradients wanted: one sliding-window kernel
+    // and its fold (gtu_dw.hip) — a gradient the caller does not ask for, the padded
+    // rows, T != 12 or C != 32 keep the grouped GEMM below
+    bool all6 = compact && m.gbfused && gtu_dw_ok(m.C, m.T);
+    for (int q = 0; q < 3; ++q) all6 = all6 && gd.gtu_w[q] && gd.gtu_b[q];
+    if (all6) {
+      GtuDwArgs g;
+      g.BN = m.BN; g.C = m.C; g.T = m.T; g.X = s.X;
+      for (int q = 0; q < 3; ++q) { g.dconv[q] = w.dconv[q]; g.dw[q] = gd.gtu_w[q]; g.db[q] = gd.gtu_b[q]; }
+      DS_TRY(op_gtu_dw(g, ks.split() ? w.gemm_ws_side : w.gemm_ws, kGemmWs, ks.side()));
+    } else {
       Gemm dws[3];
       int nw = 0;
       for (int q = 0; q < 3; ++q) {

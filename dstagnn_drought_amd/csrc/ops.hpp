@@ -266,6 +266,22 @@ struct TconvArgs {
 };
 bool gtu_tconv_ok(int C, const int* ks, int n);
 int op_gtu_tconv(const TconvArgs& a, hipStream_t st, ForkSig* sig = nullptr);
+// the three GTU convolution weight / bias gradients as one sliding-window kernel and a fixed-order
+// fold (gtu_dw.hip); C = 32, T = 12
+struct GtuDwArgs {
+  const float* dconv[3] = {};  // compact gate-gradient rows (BN Tg_q, 2C) per GTU
+  const float* X = nullptr;    // (BN, T, C) the GTU stage input
+  int64_t BN = 0;
+  int C = 0, T = 0;
+  float* dw[3] = {};           // (2C, C, kw) the parameters' own layout
+  float* db[3] = {};           // (2C)
+  int chunks = 0;              // 0: the planner's partition; > 0: that many chunks per GTU (tests)
+};
+bool gtu_dw_ok(int C, int T);
+int gtu_dw_stage_nodes();                        // nodes per LDS stage
+void gtu_dw_plan(int64_t BN, int chunks[3]);     // chunks per GTU: a function of BN and the CU count
+// ws: the workgroups' partials (sum_q chunks_q (2C (C kw + 1)) floats)
+int op_gtu_dw(const GtuDwArgs& a, float* ws, size_t ws_floats, hipStream_t st);
 // the temporal-attention stage as one kernel (tat_fused.hip): Q|K|V projection, attention, fc,
 // residual and the LayerNorm over N; E(R, n) = src[(R % FT) s0 + (R / FT) s1 + n sN]
 struct TatFusedArgs {

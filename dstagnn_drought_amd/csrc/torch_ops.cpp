@@ -25,6 +25,8 @@
 //                           with gaps: statistics of the observed values, forward fill, in-gather imputation
 //   dstagnn::gemm_f32      the strided f32-MFMA GEMM (tests / tools)
 //   dstagnn::colsum         the fixed-order column-sum reduction (bias / LayerNorm affine grads; tests)
+//   dstagnn::gtu_dw / gtu_dw_plan   the GTU convolution weight / bias gradients through gtu_dw_kernel and
+//                           its fold, and the planner's chunk counts and stage size (tests)
 //   dstagnn::stag_* / emd_dense / fast_stag_distances / graph_topk[_masked]   the graph builders
 //                           (stag_prep_masked / stag_emd_pairs_masked: a series with gaps)
 //                           (data/STAG_gen.py:17-129, data/fast_STAG_gen.py:16-74)
@@ -711,6 +713,42 @@ Tensor colsum(const Tensor& in, int64_t O, int64_t I) {
                           ws.data_ptr(), (size_t)ws.numel(), stream_of(in)),
            "dstagnn_colsum");
   return out;
+}
+
+// the GTU convolution weight / bias gradients through gtu_dw_kernel and its fold (tests): dconv_q
+// (BN Tg_q, 64) compact gate-gradient rows, X (BN, 12, 32) -> dW3, dW5, dW7 (64, 32, kw), db3, db5, db7
+std::vector<Tensor> gtu_dw(const Tensor& d3, const Tensor& d5, const Tensor& d7, const Tensor& X, int64_t chunks) {
+  const Tensor* dc[3] = {&d3, &d5, &d7};
+  check_dev(X, at::kFloat, "X");
+  TORCH_CHECK(X.dim() == 3 && X.size(0) > 0 && X.size(1) == 12 && X.size(2) == 32, "gtu_dw: X must be (BN, 12, 32)");
+  TORCH_CHECK(chunks >= 0, "gtu_dw: chunks >= 0");
+  const int64_t BN = X.size(0);
+  c10::DeviceGuard guard(X.device());
+  std::vector<Tensor> out(6);
+  const float* dp[3];
+  float *wp[3], *bp[3];
+  for (int q = 0; q < 3; ++q) {
+    const int64_t kw = 3 + 2 * q;
+    check_dev(*dc[q], at::kFloat, "dconv");
+    TORCH_CHECK(dc[q]->dim() == 2 && dc[q]->size(0) == BN * (12 - kw + 1) && dc[q]->size(1) == 64,
+                "gtu_dw: dconv_q must be (BN (12 - kw + 1), 64)");
+    out[q] = at::empty({64, 32, kw}, X.options());
+    out[3 + q] = at::empty({64}, X.options());
+    dp[q] = dc[q]->data_ptr<float>(); wp[q] = out[q].data_ptr<float>(); bp[q] = out[3 + q].data_ptr<float>();
+  }
+  // NaN-filled: a partial no workgroup wrote would show in the result
+  Tensor ws = at::full({(kGemmWsBytes + 256) / 4}, std::nanf(""), X.options());
+  check_rc(dstagnn_gtu_dw(dp, X.data_ptr<float>(), BN, wp, bp, (int)chunks, ws.data_ptr(), (size_t)ws.numel() * 4,
+                          stream_of(X)),
+           "dstagnn_gtu_dw");
+  return out;
+}
+
+// the planner's chunk counts per GTU for BN nodes on the current device, then the nodes per stage
+std::vector<int64_t> gtu_dw_plan(int64_t BN) {
+  int ch[3] = {0, 0, 0}, stage = 0;
+  check_rc(dstagnn_gtu_dw_plan(BN, ch, &stage), "dstagnn_gtu_dw_plan");
+  return {ch[0], ch[1], ch[2], stage};
 }
 
 // -------------------------------------------------------------------------------------
@@ -1452,6 +1490,8 @@ TORCH_LIBRARY(dstagnn, m) {
   m.def("gemm_f32(Tensor A, Tensor B, Tensor(a!) C, int[] mnkb, int[] maps, int[] offs, float alpha, float beta, "
         "Tensor? bias, int bias_stride, bool relu) -> ()");
   m.def("colsum(Tensor x, int O, int I) -> Tensor");
+  m.def("gtu_dw(Tensor dconv3, Tensor dconv5, Tensor dconv7, Tensor X, int chunks) -> Tensor[]");
+  m.def("gtu_dw_plan(int BN) -> int[]", gtu_dw_plan);
   m.def("head_fwd(Tensor[] outs, Tensor w1, Tensor b1, Tensor w2, Tensor b2) -> (Tensor, Tensor)");
   m.def("head_bwd(Tensor[] outs, Tensor w1, Tensor w2, Tensor h, Tensor dy, int[] need) -> Tensor[]");
   m.def("adam_step(Tensor(a!)[] params, Tensor[] grads, Tensor(b!)[] exp_avgs, Tensor(c!)[] exp_avg_sqs, "
@@ -1518,6 +1558,7 @@ TORCH_LIBRARY_IMPL(dstagnn, CUDA, m) {
   m.impl("cheb_sat_bwd", cheb_sat_bwd);
   m.impl("gemm_f32", gemm_f32);
   m.impl("colsum", colsum);
+  m.impl("gtu_dw", gtu_dw);
   m.impl("head_fwd", head_fwd);
   m.impl("head_bwd", head_bwd);
   m.impl("adam_step", adam_step);

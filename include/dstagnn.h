@@ -271,6 +271,18 @@ int dstagnn_gemm_f32(const dstagnn_gemm_desc* g, void* scratch, size_t scratch_b
 int dstagnn_colsum(const float* in, int64_t A, int O, int I, float* out, int64_t ostride, float beta,
                    void* scratch, size_t scratch_bytes, dstagnn_stream_t stream);
 
+/* The three GTU convolution weight and bias gradients of a block with C = 32, T = 12 as the
+ * block's backward computes them where the fused GTU backward runs (gtu_dw_kernel + its fold):
+ *   dw[q][o][c][j] = sum_{bn, t'} dconv[q][(bn Tg + t')][o] X[bn][t' + j][c],  db[q][o] = sum dconv[q][.][o]
+ * for kernel widths kw = 3, 5, 7 (q = 0, 1, 2; Tg = 12 - kw + 1); dconv[q]: (BN Tg, 64), X: (BN, 12, 32),
+ * all 16-B aligned.  chunks = 0: the planner's node partition; chunks > 0: that many chunks per
+ * GTU (empty chunks allowed).  Fixed summation order: bit-identical from run to run.
+ * scratch >= 32 MB + 256.  dstagnn_gtu_dw_plan: the planner's chunk counts per GTU for BN nodes on
+ * the current device and the nodes per LDS stage. */
+int dstagnn_gtu_dw(const float* const dconv[3], const float* X, int64_t BN, float* const dw[3], float* const db[3],
+                   int chunks, void* scratch, size_t scratch_bytes, dstagnn_stream_t stream);
+int dstagnn_gtu_dw_plan(int64_t BN, int chunks[3], int* stage_nodes);
+
 /* Time `iters` back-to-back launches of one block stage with HIP events on
  * `stream`; writes the mean per-launch milliseconds.  stage: 0 = whole forward,
  * 2 = cheb_sat forward stage, 3 = pre_conv stage, 10 = the single kernel the
@@ -690,7 +702,8 @@ enum {
   DSTAGNN_PROF_GTU_FUSED_FWD = 4,  /* gtu_fwd_fused_kernel                                      */
   DSTAGNN_PROF_GTU_FUSED_BWD = 5,  /* gtu_bwd_fused_kernel                                      */
   DSTAGNN_PROF_GTU_TCONV = 6,      /* gtu_tconv sliding-window convolution gradient             */
-  DSTAGNN_PROF_SAT_FUSED = 7       /* retired (that kernel is gone): never reported             */
+  DSTAGNN_PROF_SAT_FUSED = 7,      /* retired (that kernel is gone): never reported             */
+  DSTAGNN_PROF_GTU_DW = 8          /* gtu_dw_kernel + its fold (GTU convolution weight gradients) */
 };
 typedef struct dstagnn_prof_record {
   double flops;  /* algorithmic FLOP of the call   */

@@ -11,6 +11,8 @@ for r in $(seq 1 $REPS); do
   for lib in "$@"; do
     tag=$(echo "$lib" | tr '/' '_')
     if [ "$lib" = "-" ]; then E=(); else E=(LD_LIBRARY_PATH=$lib); fi
+    # a library of another C ABI (a parent without this tree's entries) brings its own _C.so
+    [ "$lib" != "-" ] && [ -f "$lib/_C.so" ] && E+=(DSTAGNN_EXT=$PWD/$lib/_C.so)
     env "${E[@]}" timeout -k 10 120 python bench.py --steps $STEPS --warmup 20 --no-cpu-baseline --no-extras ${AB_ARGS:-} \
       > gpurun_out/ab/${tag}_$r.log 2>&1 || { echo "FATAL $lib rep $r"; tail -5 gpurun_out/ab/${tag}_$r.log; exit 9; }
     echo "rep $r [$lib]: $(grep -h 'timed' gpurun_out/ab/${tag}_$r.log)"
