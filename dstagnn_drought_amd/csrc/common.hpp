@@ -185,6 +185,11 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {  // fp64: the same butterfly, the same order
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 // NV independent full-wave sums at once (NV = 2^L <= 64): L halving exchange steps (offsets
 // 32, 16, ...: each lane keeps the half of its values its offset bit selects and adds the
 // partner's copy of that half), then plain butterflies; NV - 1 + 6 - L shuffles instead of 6 NV.
@@ -213,6 +218,11 @@ __device__ __forceinline__ float wave_sum_many(float (&v)[NV]) {
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
   return v;
 }
 // max / sum over each aligned group of 16 lanes (xor butterfly), every lane ending with the result

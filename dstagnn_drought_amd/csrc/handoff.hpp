@@ -75,13 +75,13 @@ __device__ __forceinline__ bool last_arrival(int* cnt, int n, int* flag) {
 // sum of the n partials src[k * row_stride] in index order (step 6): chunks of G sc1 loads issued
 // before the chunk's first add (one memory round trip per chunk: sc1 loads are served beyond the
 // XCD's L2), chunk after chunk into one accumulator
-template <int G>
-__device__ __forceinline__ float sum_rows_agent(const float* src, int64_t row_stride, int n) {
-  float v = 0.f;
+template <int G, typename T>
+__device__ __forceinline__ T sum_rows_agent(const T* src, int64_t row_stride, int n) {
+  T v = T(0);
   for (int k0 = 0; k0 < n; k0 += G) {
-    float u[G];
+    T u[G];
 #pragma unroll
-    for (int k = 0; k < G; ++k) u[k] = k0 + k < n ? ld_agent(src + (k0 + k) * row_stride) : 0.f;
+    for (int k = 0; k < G; ++k) u[k] = k0 + k < n ? ld_agent(src + (k0 + k) * row_stride) : T(0);
 #pragma unroll
     for (int k = 0; k < G; ++k) v += u[k];
   }

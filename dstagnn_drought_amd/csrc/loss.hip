@@ -1,47 +1,57 @@
 // loss.hip — the two ends of a training step on the GPU (gfx950): the criterion
 // (train_DSTAGNN_my.py:132 `nn.SmoothL1Loss()`, :156-157 loss + backward) with the masked
-// variants the model family uses for series with gaps, and the test-set scores
-// (lib/utils1.py:418-431: per-horizon MAE / RMSE / MAPE; lib/metrics.py:6-17 masked MAPE).
+// variants the model family uses for series with gaps, its quantile (pinball) form, and the
+// test-set scores (lib/utils1.py:418-431: per-horizon MAE / RMSE / MAPE; lib/metrics.py:6-17 masked
+// MAPE).  On a (B, N, P) head output of ~65 k floats all of this is launch latency, so each is ONE
+// launch.
 //
-// On a (B, N, P) head output of ~65 k floats all of this is launch latency, so each is ONE launch:
-//   loss_fwd_kernel      d = y - t in fp32, the per-element term in fp32, every add from the first
-//                        one in fp64 (sum and valid count per thread; the wave butterfly; the four
-//                        wave sums ((w0 + w1) + (w2 + w3))).  A workgroup's {sum, count} goes out
-//                        sc1 and the workgroup whose ticket came last (handoff.hpp) adds all
-//                        partials in one fixed order: lane l of its first wave takes partials l,
-//                        l + 64, ... in index order, then the butterfly.  stat = {sum, count},
-//                        loss = sum / count (0 when nothing is valid).  Same bits on every launch.
+// The numeric contract, the same in every kernel: a masked entry is selected out (never multiplied
+// by zero: a NaN target under the NaN mask leaves the loss finite and its gradient entry exactly
+// 0; a NaN prediction at a valid entry makes the loss NaN, which HipAdam's non-finite skip then
+// sees), every term is fp32, every add from the first one is fp64 in a fixed order, no
+// floating-point atomics: a launch gives the same bits every time.
+//
+// The shared pieces, each written once:
+//   sum_count_handoff   a workgroup's {sum, count} out sc1, the hand-off of handoff.hpp, the last
+//                       arrival's grid fold in lane order (the two criterion forwards).
+//   fold_into_table     the last arrival of a score kernel: sum_rows_agent<8> over the workgroups,
+//                       in order, added to the running table (metrics_accum_kernel,
+//                       metrics_quantile_kernel).
+//   lds_levels          tau and 1 - tau of the quantile levels into LDS (the pinball kernels).
+//   mask_arg, horizon_arg, strip_arg, scratch_arg, ticket_arg   the entry points' common checks.
+//
+// The kernels:
+//   loss_fwd_kernel      d = y - t, loss_term; tiles w, w + grid, ...; sum_count_handoff; stat =
+//                        {sum, count}, loss = sum / count (0 when nothing is valid).
 //   loss_bwd_kernel      dy = l'(d) * (gout / count) on valid entries, 0 elsewhere; count from the
 //                        forward's stat and gout from device memory: no host sync.  Recomputes d.
-//   metrics_accum_kernel (rows, P) predictions / targets -> a running (P, 4) fp64 table of
-//                        sum |e|, sum e^2, sum |e / t| over t != null, count of t != null.  Thread
-//                        rl P + p of the first (256 / P) P reads element row0 P + rl P + p
-//                        (coalesced; its p never changes), keeps four fp64 sums, LDS folds them
-//                        over rl in order, workgroups hand off as above and the last one adds the
-//                        folded sums into the table.  No floating-point atomics anywhere.
-//   metrics_masked_kernel (B, N, P) predictions / targets -> a running (P, 8) horizon table and an
-//                        optional running (N, 8) node table of fp64 sums over the VALID entries
-//                        (the criterion's is_valid): count, sum e, sum |e|, sum e^2, sum |e / t|
-//                        over t != mape_null, its count, sum t, sum t^2.  A workgroup owns a strip
-//                        of 256 / P nodes: thread nl P + p walks the samples of element (n0 + nl,
-//                        p), LDS folds the strip over nl (per horizon: a partial handed off as
-//                        above) and over p (per node: added straight into the node table, whose
-//                        rows have one owning workgroup each).
-//   pinball_fwd_kernel / pinball_bwd_kernel   the quantile (pinball) criterion of an (M, Q)
-//                        prediction, q fastest, against an (M) target: loss_fwd / loss_bwd's plan
-//                        over the M Q stream (element i: target i / Q, level i mod Q).
-//   metrics_quantile_kernel (B, N, P, Q) predictions -> running (P, 2 + 3 Q) and optional
-//                        (N, 2 + 3 Q) tables of the calibration sums (valid and crossing counts;
-//                        per level the pinball sum, the count of t <= y_q, the sum of y_q), on
-//                        metrics_masked_kernel's plan.
+//   pinball_fwd_kernel / pinball_bwd_kernel   the same two over the (M, Q) prediction stream, q
+//                        fastest: element i belongs to target i / Q (read through the cache: Q
+//                        neighbouring lanes share one) and level i mod Q (pinball_walk), the levels
+//                        from LDS; stat = {sum, count / Q}; a slope of exactly 0 gives +0.
+//   metrics_accum_kernel (rows, P) -> the running (P, 4) table of sum |e|, sum e^2, sum |e / t| over
+//                        t != null, its count.  Thread rl P + p of the first (256 / P) P reads
+//                        element row0 P + rl P + p (coalesced; its p never changes), LDS folds over
+//                        rl in order; fold_into_table.
+//   metrics_masked_kernel (B, N, P) -> the running (P, 8) and optional (N, 8) tables over the VALID
+//                        entries (count, sum e, sum |e|, sum e^2, sum |e / t| over t != mape_null,
+//                        its count, sum t, sum t^2).  A workgroup owns a strip of 256 / P nodes:
+//                        thread nl P + p walks the samples of element (n0 + nl, p), LDS folds the
+//                        strip over nl (per horizon: the sc1 partial) and over p (per node: straight
+//                        into the node table, whose rows have one owning workgroup each).
+//   metrics_quantile_kernel (B, N, P, Q) -> running (P, 2 + 3 Q) and optional (N, 2 + 3 Q) tables
+//                        of the calibration sums (valid and crossing counts; per level the pinball
+//                        sum, the count of t <= y_q, the sum of y_q): the masked kernel's strip
+//                        plan, kQmChunk columns through LDS at a time; fold_into_table.
 //
-// A masked entry is selected out (never multiplied by zero): a NaN target under the NaN mask
-// leaves the loss finite and its gradient entry exactly 0.  A NaN prediction at a valid entry makes
-// the loss NaN (HipAdam's non-finite skip then sees a NaN gradient norm).
+// In all four criterion kernels: 16-byte loads where every pointer of the launch is 16-byte aligned
+// and the tile is whole; scalar loads otherwise (a batch slice y[b:b+bs] of a contiguous tensor is
+// often not aligned; the last tile is usually partial).
 //
-// Vector (16-byte) loads where every pointer of the launch is 16-byte aligned and the tile is
-// whole; scalar loads otherwise (a batch slice y[b:b+bs] of a contiguous tensor is often not
-// aligned; the last tile is usually partial).
+// Copies kept on purpose: the tile walk of the four criterion kernels, the strip
+// fold of the two (B, N, P) score kernels and metrics_masked_kernel's last-arrival fold.  Each shared
+// form that was tried changed the code of kernels on the training or scoring path, and where it
+// was measured it was slower or spilled SGPRs.
 #include <cmath>
 
 #include "handoff.hpp"
@@ -52,12 +62,8 @@ namespace {
 constexpr int kLossThreads = 256, kLossPer = 16, kLossTile = kLossThreads * kLossPer;
 constexpr int kLossMaxWg = 1024;  // beyond it a workgroup walks tiles w, w + grid, ...
 constexpr int kMetThreads = 256, kMetPasses = 8, kMetMaxWg = 256, kMetMaxP = 256;
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+constexpr int kFold = 8;  // sc1 loads in flight in a last arrival's fold (sum_rows_agent)
+constexpr int kMaxQ = DSTAGNN_MAX_QUANTILES;
 
 __device__ __forceinline__ bool is_valid(int mask, float null_val, float t) {
   return mask == DSTAGNN_MASK_NONE ? true : mask == DSTAGNN_MASK_NAN ? !(t != t) : t != null_val;
@@ -86,13 +92,82 @@ __device__ __forceinline__ float loss_slope(int kind, float b, float d) {
   }
 }
 
+// term and slope of the pinball criterion at d = y_q - t: d > 0: (1 - tau) d, slope 1 - tau; d < 0:
+// tau (-d), slope -tau; d = 0: 0 and 0 (DSTAGNN_LOSS_MAE's sign(0) = 0); a NaN d stays NaN
+__device__ __forceinline__ float pinball_term(float tau, float omt, float d) {
+  return d > 0.f ? omt * d : d < 0.f ? tau * -d : d == 0.f ? 0.f : d;
+}
+__device__ __forceinline__ float pinball_slope(float tau, float omt, float d) {
+  return d > 0.f ? omt : d < 0.f ? -tau : d == 0.f ? 0.f : d;
+}
+
+// (target index, level) of the four stream elements i0 .. i0 + 3 of an (M, Q) prediction
+__device__ __forceinline__ void pinball_walk(unsigned i0, unsigned Q, unsigned (&m)[4], unsigned (&q)[4]) {
+  m[0] = i0 / Q;
+  q[0] = i0 - m[0] * Q;
+#pragma unroll
+  for (int j = 1; j < 4; ++j) {
+    const bool wrap = q[j - 1] + 1 == Q;
+    q[j] = wrap ? 0u : q[j - 1] + 1;
+    m[j] = m[j - 1] + (wrap ? 1u : 0u);
+  }
+}
+
+// A checked dstagnn_pinball_cfg and the 1 - tau of its levels (both formed on the host).
+struct PinballArgs {
+  int mask_mode;
+  float null_val;
+  int num_quantiles;
+  float tau[kMaxQ], one_minus_tau[kMaxQ];
+};
+
+// all threads of a pinball criterion kernel, first thing: the levels tau and 1 - tau into LDS
+struct Levels {
+  const float *tau, *omt;
+};
+__device__ __forceinline__ Levels lds_levels(const PinballArgs& cfg) {
+  __shared__ float tau[kMaxQ], omt[kMaxQ];
+  const int t = threadIdx.x;
+  if (t < kMaxQ) tau[t] = cfg.tau[t], omt[t] = cfg.one_minus_tau[t];
+  __syncthreads();
+  return {tau, omt};
+}
+
+// ---- the {sum, count} hand-off ----------------------------------------------------------------
+// Every thread of every workgroup of a kLossThreads launch calls it with its own fp64 sum and
+// count.  The wave butterfly, the four wave sums as ((w0 + w1) + (w2 + w3)), the workgroup's pair
+// out as two 8-byte sc1 stores, the hand-off of handoff.hpp; in the last arrival lane l of the first
+// wave takes partials l, l + 64, ... in index order, then the butterfly.  True on thread 0 of the
+// last arrival alone, where sum and cnt are then the launch's totals: the same bits every time.
+__device__ __forceinline__ bool sum_count_handoff(double& sum, double& cnt, double* __restrict__ part, int* ticket) {
+  __shared__ double ws[kLossThreads / 64], wc[kLossThreads / 64];
+  __shared__ int last;
+  const int t = threadIdx.x;
+  sum = wave_sum(sum);
+  cnt = wave_sum(cnt);
+  if ((t & 63) == 0) ws[t >> 6] = sum, wc[t >> 6] = cnt;
+  __syncthreads();
+  if (t == 0) {
+    st_agent(part + 2 * (int64_t)blockIdx.x, (ws[0] + ws[1]) + (ws[2] + ws[3]));
+    st_agent(part + 2 * (int64_t)blockIdx.x + 1, (wc[0] + wc[1]) + (wc[2] + wc[3]));
+  }
+  if (!last_arrival(ticket, (int)gridDim.x, &last)) return false;
+  if (t >= 64) return false;
+  double a = 0.0, c = 0.0;
+  for (int64_t k = t; k < (int64_t)gridDim.x; k += 64) {
+    a += ld_agent(part + 2 * k);
+    c += ld_agent(part + 2 * k + 1);
+  }
+  sum = wave_sum(a);
+  cnt = wave_sum(c);
+  return t == 0;
+}
+
 __global__ __launch_bounds__(kLossThreads) void loss_fwd_kernel(dstagnn_loss_cfg cfg, int64_t n,
                                                                const float* __restrict__ y,
                                                                const float* __restrict__ tg, int vec,
                                                                double* __restrict__ part, int* ticket,
                                                                double* __restrict__ stat, float* __restrict__ loss) {
-  __shared__ double ws[kLossThreads / 64], wc[kLossThreads / 64];
-  __shared__ int last;
   const int t = threadIdx.x;
   double sum = 0.0, cnt = 0.0;
   for (int64_t base = (int64_t)blockIdx.x * kLossTile; base < n; base += (int64_t)gridDim.x * kLossTile) {
@@ -130,29 +205,10 @@ __global__ __launch_bounds__(kLossThreads) void loss_fwd_kernel(dstagnn_loss_cfg
       }
     }
   }
-  sum = wave_sum_f64(sum);
-  cnt = wave_sum_f64(cnt);
-  if ((t & 63) == 0) ws[t >> 6] = sum, wc[t >> 6] = cnt;
-  __syncthreads();
-  // the hand-off of handoff.hpp: {sum, count} per workgroup, every partial an 8-byte sc1 store
-  if (t == 0) {
-    st_agent(part + 2 * (int64_t)blockIdx.x, (ws[0] + ws[1]) + (ws[2] + ws[3]));
-    st_agent(part + 2 * (int64_t)blockIdx.x + 1, (wc[0] + wc[1]) + (wc[2] + wc[3]));
-  }
-  if (!last_arrival(ticket, (int)gridDim.x, &last)) return;
-  if (t >= 64) return;
-  double a = 0.0, c = 0.0;
-  for (int64_t k = t; k < (int64_t)gridDim.x; k += 64) {
-    a += ld_agent(part + 2 * k);
-    c += ld_agent(part + 2 * k + 1);
-  }
-  a = wave_sum_f64(a);
-  c = wave_sum_f64(c);
-  if (t == 0) {
-    stat[0] = a;
-    stat[1] = c;
-    loss[0] = c > 0.0 ? (float)(a / c) : 0.f;
-  }
+  if (!sum_count_handoff(sum, cnt, part, ticket)) return;
+  stat[0] = sum;
+  stat[1] = cnt;
+  loss[0] = cnt > 0.0 ? (float)(sum / cnt) : 0.f;
 }
 
 __global__ __launch_bounds__(kLossThreads) void loss_bwd_kernel(dstagnn_loss_cfg cfg, int64_t n,
@@ -199,6 +255,135 @@ __global__ __launch_bounds__(kLossThreads) void loss_bwd_kernel(dstagnn_loss_cfg
   }
 }
 
+__global__ __launch_bounds__(kLossThreads) void pinball_fwd_kernel(PinballArgs cfg, int64_t n,
+                                                                  const float* __restrict__ y,
+                                                                  const float* __restrict__ tg, int vec,
+                                                                  double* __restrict__ part, int* ticket,
+                                                                  double* __restrict__ stat,
+                                                                  float* __restrict__ loss) {
+  const int t = threadIdx.x;
+  const unsigned Q = (unsigned)cfg.num_quantiles;
+  const Levels lv = lds_levels(cfg);
+  double sum = 0.0, cnt = 0.0;  // cnt counts stream elements: Q per valid target entry
+  for (int64_t base = (int64_t)blockIdx.x * kLossTile; base < n; base += (int64_t)gridDim.x * kLossTile) {
+    if (vec && base + kLossTile <= n) {  // (uniform) a whole tile: four 16-byte loads of y
+      const float4* __restrict__ y4 = reinterpret_cast<const float4*>(y + base);
+      float4 a[kLossPer / 4];
+#pragma unroll
+      for (int u = 0; u < kLossPer / 4; ++u) a[u] = y4[u * kLossThreads + t];
+#pragma unroll
+      for (int u = 0; u < kLossPer / 4; ++u) {
+        unsigned m[4], q[4];
+        pinball_walk((unsigned)base + 4u * (unsigned)(u * kLossThreads + t), Q, m, q);
+        const float yv[4] = {a[u].x, a[u].y, a[u].z, a[u].w};
+        float tv[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) tv[j] = tg[m[j]];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (is_valid(cfg.mask_mode, cfg.null_val, tv[j])) {
+            sum += (double)pinball_term(lv.tau[q[j]], lv.omt[q[j]], yv[j] - tv[j]);
+            cnt += 1.0;
+          }
+      }
+    } else {
+      float yv[kLossPer], tv[kLossPer];
+      unsigned qv[kLossPer];
+#pragma unroll
+      for (int u = 0; u < kLossPer; ++u) {
+        const int64_t i = base + t + (int64_t)kLossThreads * u;
+        const bool ok = i < n;
+        const unsigned m = ok ? (unsigned)i / Q : 0u;
+        qv[u] = ok ? (unsigned)i - m * Q : 0u;
+        yv[u] = ok ? y[i] : 0.f;
+        tv[u] = ok ? tg[m] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < kLossPer; ++u) {
+        const int64_t i = base + t + (int64_t)kLossThreads * u;
+        if (i < n && is_valid(cfg.mask_mode, cfg.null_val, tv[u])) {
+          sum += (double)pinball_term(lv.tau[qv[u]], lv.omt[qv[u]], yv[u] - tv[u]);
+          cnt += 1.0;
+        }
+      }
+    }
+  }
+  if (!sum_count_handoff(sum, cnt, part, ticket)) return;
+  stat[0] = sum;
+  stat[1] = cnt / (double)Q;  // the valid target entries (cnt is a multiple of Q: exact)
+  loss[0] = cnt > 0.0 ? (float)(sum / cnt) : 0.f;
+}
+
+__global__ __launch_bounds__(kLossThreads) void pinball_bwd_kernel(PinballArgs cfg, int64_t n,
+                                                                  const float* __restrict__ y,
+                                                                  const float* __restrict__ tg, int vec,
+                                                                  const double* __restrict__ stat,
+                                                                  const float* __restrict__ gout,
+                                                                  float* __restrict__ dy) {
+  const int t = threadIdx.x;
+  const unsigned Q = (unsigned)cfg.num_quantiles;
+  const Levels lv = lds_levels(cfg);
+  const double cnt = stat[1] * (double)Q;
+  const float g = gout != nullptr ? gout[0] : 1.f;
+  const float scale = cnt > 0.0 ? (float)((double)g / cnt) : 0.f;
+  const int64_t base = (int64_t)blockIdx.x * kLossTile;
+  if (vec && base + kLossTile <= n) {
+    const float4* __restrict__ y4 = reinterpret_cast<const float4*>(y + base);
+    float4* __restrict__ d4 = reinterpret_cast<float4*>(dy + base);
+    float4 a[kLossPer / 4];
+#pragma unroll
+    for (int u = 0; u < kLossPer / 4; ++u) a[u] = y4[u * kLossThreads + t];
+#pragma unroll
+    for (int u = 0; u < kLossPer / 4; ++u) {
+      unsigned m[4], q[4];
+      pinball_walk((unsigned)base + 4u * (unsigned)(u * kLossThreads + t), Q, m, q);
+      const float yv[4] = {a[u].x, a[u].y, a[u].z, a[u].w};
+      float tv[4], r[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) tv[j] = tg[m[j]];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float s = pinball_slope(lv.tau[q[j]], lv.omt[q[j]], yv[j] - tv[j]);
+        r[j] = is_valid(cfg.mask_mode, cfg.null_val, tv[j]) && s != 0.f ? s * scale : 0.f;
+      }
+      d4[u * kLossThreads + t] = make_float4(r[0], r[1], r[2], r[3]);
+    }
+    return;
+  }
+  float yv[kLossPer], tv[kLossPer];
+  unsigned qv[kLossPer];
+#pragma unroll
+  for (int u = 0; u < kLossPer; ++u) {
+    const int64_t i = base + t + (int64_t)kLossThreads * u;
+    const bool ok = i < n;
+    const unsigned m = ok ? (unsigned)i / Q : 0u;
+    qv[u] = ok ? (unsigned)i - m * Q : 0u;
+    yv[u] = ok ? y[i] : 0.f;
+    tv[u] = ok ? tg[m] : 0.f;
+  }
+#pragma unroll
+  for (int u = 0; u < kLossPer; ++u) {
+    const int64_t i = base + t + (int64_t)kLossThreads * u;
+    if (i < n) {
+      const float s = pinball_slope(lv.tau[qv[u]], lv.omt[qv[u]], yv[u] - tv[u]);
+      dy[i] = is_valid(cfg.mask_mode, cfg.null_val, tv[u]) && s != 0.f ? s * scale : 0.f;
+    }
+  }
+}
+
+// ---- the score tables --------------------------------------------------------------------------
+// The last arrival of a score kernel: workgroup k's partial is part[k cols P + c P + p]; they are
+// added in workgroup order (kFold sc1 loads issued before their adds) and the total joins the
+// running table[p cols + c].  Launches on one stream are ordered: the table needs no atomics.
+__device__ __forceinline__ void fold_into_table(const double* __restrict__ part, int P, int cols,
+                                                double* __restrict__ table) {
+  const int items = cols * P;
+  for (int item = (int)threadIdx.x; item < items; item += kMetThreads) {  // (every score kernel: 256 threads)
+    const int c = item / P, p = item - c * P;
+    table[p * cols + c] += sum_rows_agent<kFold>(part + item, items, (int)gridDim.x);
+  }
+}
+
 __global__ __launch_bounds__(kMetThreads) void metrics_accum_kernel(int64_t n, int P, const float* __restrict__ pred,
                                                                    const float* __restrict__ tg, float null_val,
                                                                    int nan_mode, double* __restrict__ part,
@@ -237,15 +422,10 @@ __global__ __launch_bounds__(kMetThreads) void metrics_accum_kernel(int64_t n, i
     st_agent(part + (int64_t)blockIdx.x * items + item, a);
   }
   if (!last_arrival(ticket, (int)gridDim.x, &last)) return;
-  for (int item = t; item < items; item += kMetThreads) {
-    const int c = item / P, p = item - c * P;
-    double a = 0.0;
-    for (int64_t k = 0; k < (int64_t)gridDim.x; ++k) a += ld_agent(part + k * items + item);
-    table[p * 4 + c] += a;  // launches on one stream are ordered: the running table needs no atomics
-  }
+  fold_into_table(part, P, 4, table);
 }
 
-constexpr int kMmThreads = 256, kMmCols = 8, kMmUnroll = 4, kMmFold = 8;
+constexpr int kMmCols = 8, kMmUnroll = 4;
 
 // one entry into a thread's eight sums: e, e * e and e / t in fp32, every add in fp64; t and t * t
 // as doubles (the product of two floats is exact there)
@@ -265,19 +445,19 @@ __device__ __forceinline__ void masked_entry(double (&s)[kMmCols], int mask, flo
   s[7] += (double)tv * (double)tv;
 }
 
-__global__ __launch_bounds__(kMmThreads) void metrics_masked_kernel(int B, int N, int P,
+__global__ __launch_bounds__(kMetThreads) void metrics_masked_kernel(int B, int N, int P,
                                                                    const float* __restrict__ pred,
                                                                    const float* __restrict__ tg, int mask,
                                                                    float null_val, float mape_null,
                                                                    double* __restrict__ part, int* ticket,
                                                                    double* __restrict__ htable,
                                                                    double* __restrict__ ntable) {
-  __shared__ double red[kMmCols][kMmThreads];
+  __shared__ double red[kMmCols][kMetThreads];
   __shared__ int last;
   const int t = threadIdx.x;
-  const int TN = kMmThreads / P;                   // nodes of a whole strip
-  const int n0 = (int)blockIdx.x * TN;             // (the grid is ceil(N / TN): n0 < N)
-  const int tn = N - n0 < TN ? N - n0 : TN;        // nodes of this strip (the last one is partial)
+  const int TN = kMetThreads / P;            // nodes of a whole strip
+  const int n0 = (int)blockIdx.x * TN;       // (the grid is ceil(N / TN): n0 < N)
+  const int tn = N - n0 < TN ? N - n0 : TN;  // nodes of this strip (the last one is partial)
   double s[kMmCols] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   if (t < tn * P) {
     // element (b, n0 + nl, p) with t = nl P + p sits at b N P + n0 P + t: for a fixed b the strip
@@ -301,7 +481,7 @@ __global__ __launch_bounds__(kMmThreads) void metrics_masked_kernel(int B, int N
   // per node, over p in order: item = nl 8 + c lands on ntable[(n0 + nl) 8 + c].  This workgroup is
   // the only one that ever touches these rows and launches on a stream are ordered: plain adds.
   if (ntable != nullptr) {
-    for (int item = t; item < kMmCols * tn; item += kMmThreads) {
+    for (int item = t; item < kMmCols * tn; item += kMetThreads) {
       const int nl = item / kMmCols, c = item - nl * kMmCols;
       double a = 0.0;
       for (int p = 0; p < P; ++p) a += red[c][nl * P + p];
@@ -310,223 +490,47 @@ __global__ __launch_bounds__(kMmThreads) void metrics_masked_kernel(int B, int N
   }
   // per horizon, over nl in order (the idle rows of a partial strip hold zeros); item = c P + p
   const int items = kMmCols * P;
-  for (int item = t; item < items; item += kMmThreads) {
+  for (int item = t; item < items; item += kMetThreads) {
     const int c = item / P, p = item - c * P;
     double a = 0.0;
     for (int nl = 0; nl < TN; ++nl) a += red[c][nl * P + p];
     st_agent(part + (int64_t)blockIdx.x * items + item, a);
   }
   if (!last_arrival(ticket, (int)gridDim.x, &last)) return;
-  // the last arrival: the partials in workgroup order, kMmFold sc1 loads issued before their adds
+  // the last arrival: the partials in workgroup order, kFold sc1 loads issued before their adds
   const int G = (int)gridDim.x;
-  for (int item = t; item < items; item += kMmThreads) {
+  for (int item = t; item < items; item += kMetThreads) {
     const int c = item / P, p = item - c * P;
     double a = 0.0;
-    for (int k0 = 0; k0 < G; k0 += kMmFold) {
-      double u[kMmFold];
+    for (int k0 = 0; k0 < G; k0 += kFold) {
+      double u[kFold];
 #pragma unroll
-      for (int k = 0; k < kMmFold; ++k) u[k] = k0 + k < G ? ld_agent(part + (int64_t)(k0 + k) * items + item) : 0.0;
+      for (int k = 0; k < kFold; ++k) u[k] = k0 + k < G ? ld_agent(part + (int64_t)(k0 + k) * items + item) : 0.0;
 #pragma unroll
-      for (int k = 0; k < kMmFold; ++k) a += u[k];
+      for (int k = 0; k < kFold; ++k) a += u[k];
     }
     htable[p * kMmCols + c] += a;
   }
 }
 
-// ---- quantile forecasts: the pinball criterion and the calibration sums -----------------------
-// Prediction (M, Q), q fastest; target (M).  Element i of the prediction stream belongs to target
-// i / Q and level i mod Q: the stream itself is read as loss_fwd_kernel reads y (consecutive lanes,
-// consecutive floats; 16-byte loads on whole aligned tiles), the target through the cache (Q
-// neighbouring lanes share one).  The levels sit in LDS: tau and 1 - tau, both formed on the host.
-constexpr int kMaxQ = DSTAGNN_MAX_QUANTILES;
-struct PinballArgs {  // a checked dstagnn_pinball_cfg and the 1 - tau of its levels
-  int mask_mode;
-  float null_val;
-  int num_quantiles;
-  float tau[kMaxQ], one_minus_tau[kMaxQ];
-};
+// The calibration sums of (B, N, P, Q) predictions against (B, N, P) targets: 2 + 3 Q sums per
+// thread: valid count, crossing count and, per level, the pinball sum (fp32 term), the count of
+// t <= y_q (fp32 compare) and the sum of y_q (exact as doubles).  A thread reads the Q floats of its
+// entry (the wave: 64 Q contiguous floats, every byte used) and keeps its sums in registers; the
+// loops over q are unrolled to kMaxQ under the uniform q < Q so every index is a constant.
+constexpr int kQmCols = 2 + 3 * kMaxQ, kQmChunk = 8;
 
-// term and slope of d = y_q - t: d > 0: (1 - tau) d, slope 1 - tau; d < 0: tau (-d), slope -tau;
-// d = 0: 0 and 0 (DSTAGNN_LOSS_MAE's sign(0) = 0); a NaN d stays NaN
-__device__ __forceinline__ float pinball_term(float tau, float omt, float d) {
-  return d > 0.f ? omt * d : d < 0.f ? tau * -d : d == 0.f ? 0.f : d;
-}
-__device__ __forceinline__ float pinball_slope(float tau, float omt, float d) {
-  return d > 0.f ? omt : d < 0.f ? -tau : d == 0.f ? 0.f : d;
-}
-
-// (target index, level) of the four stream elements i0 .. i0 + 3
-__device__ __forceinline__ void pinball_walk(unsigned i0, unsigned Q, unsigned (&m)[4], unsigned (&q)[4]) {
-  m[0] = i0 / Q;
-  q[0] = i0 - m[0] * Q;
-#pragma unroll
-  for (int j = 1; j < 4; ++j) {
-    const bool wrap = q[j - 1] + 1 == Q;
-    q[j] = wrap ? 0u : q[j - 1] + 1;
-    m[j] = m[j - 1] + (wrap ? 1u : 0u);
-  }
-}
-
-__global__ __launch_bounds__(kLossThreads) void pinball_fwd_kernel(PinballArgs cfg, int64_t n,
-                                                                  const float* __restrict__ y,
-                                                                  const float* __restrict__ tg, int vec,
-                                                                  double* __restrict__ part, int* ticket,
-                                                                  double* __restrict__ stat,
-                                                                  float* __restrict__ loss) {
-  __shared__ double ws[kLossThreads / 64], wc[kLossThreads / 64];
-  __shared__ float tau[kMaxQ], omt[kMaxQ];
-  __shared__ int last;
-  const int t = threadIdx.x;
-  const unsigned Q = (unsigned)cfg.num_quantiles;
-  if (t < kMaxQ) tau[t] = cfg.tau[t], omt[t] = cfg.one_minus_tau[t];
-  __syncthreads();
-  double sum = 0.0, cnt = 0.0;  // cnt counts stream elements: Q per valid target entry
-  for (int64_t base = (int64_t)blockIdx.x * kLossTile; base < n; base += (int64_t)gridDim.x * kLossTile) {
-    if (vec && base + kLossTile <= n) {  // (uniform) a whole tile: four 16-byte loads of y
-      const float4* __restrict__ y4 = reinterpret_cast<const float4*>(y + base);
-      float4 a[kLossPer / 4];
-#pragma unroll
-      for (int u = 0; u < kLossPer / 4; ++u) a[u] = y4[u * kLossThreads + t];
-#pragma unroll
-      for (int u = 0; u < kLossPer / 4; ++u) {
-        unsigned m[4], q[4];
-        pinball_walk((unsigned)base + 4u * (unsigned)(u * kLossThreads + t), Q, m, q);
-        const float yv[4] = {a[u].x, a[u].y, a[u].z, a[u].w};
-        float tv[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) tv[j] = tg[m[j]];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (is_valid(cfg.mask_mode, cfg.null_val, tv[j])) {
-            sum += (double)pinball_term(tau[q[j]], omt[q[j]], yv[j] - tv[j]);
-            cnt += 1.0;
-          }
-      }
-    } else {
-      float yv[kLossPer], tv[kLossPer];
-      unsigned qv[kLossPer];
-#pragma unroll
-      for (int u = 0; u < kLossPer; ++u) {
-        const int64_t i = base + t + (int64_t)kLossThreads * u;
-        const bool ok = i < n;
-        const unsigned m = ok ? (unsigned)i / Q : 0u;
-        qv[u] = ok ? (unsigned)i - m * Q : 0u;
-        yv[u] = ok ? y[i] : 0.f;
-        tv[u] = ok ? tg[m] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < kLossPer; ++u) {
-        const int64_t i = base + t + (int64_t)kLossThreads * u;
-        if (i < n && is_valid(cfg.mask_mode, cfg.null_val, tv[u])) {
-          sum += (double)pinball_term(tau[qv[u]], omt[qv[u]], yv[u] - tv[u]);
-          cnt += 1.0;
-        }
-      }
-    }
-  }
-  sum = wave_sum_f64(sum);
-  cnt = wave_sum_f64(cnt);
-  if ((t & 63) == 0) ws[t >> 6] = sum, wc[t >> 6] = cnt;
-  __syncthreads();
-  if (t == 0) {  // the hand-off of handoff.hpp, as loss_fwd_kernel
-    st_agent(part + 2 * (int64_t)blockIdx.x, (ws[0] + ws[1]) + (ws[2] + ws[3]));
-    st_agent(part + 2 * (int64_t)blockIdx.x + 1, (wc[0] + wc[1]) + (wc[2] + wc[3]));
-  }
-  if (!last_arrival(ticket, (int)gridDim.x, &last)) return;
-  if (t >= 64) return;
-  double a = 0.0, c = 0.0;
-  for (int64_t k = t; k < (int64_t)gridDim.x; k += 64) {
-    a += ld_agent(part + 2 * k);
-    c += ld_agent(part + 2 * k + 1);
-  }
-  a = wave_sum_f64(a);
-  c = wave_sum_f64(c);
-  if (t == 0) {
-    stat[0] = a;
-    stat[1] = c / (double)Q;  // the valid target entries (c is a multiple of Q: exact)
-    loss[0] = c > 0.0 ? (float)(a / c) : 0.f;
-  }
-}
-
-__global__ __launch_bounds__(kLossThreads) void pinball_bwd_kernel(PinballArgs cfg, int64_t n,
-                                                                  const float* __restrict__ y,
-                                                                  const float* __restrict__ tg, int vec,
-                                                                  const double* __restrict__ stat,
-                                                                  const float* __restrict__ gout,
-                                                                  float* __restrict__ dy) {
-  __shared__ float tau[kMaxQ], omt[kMaxQ];
-  const int t = threadIdx.x;
-  const unsigned Q = (unsigned)cfg.num_quantiles;
-  if (t < kMaxQ) tau[t] = cfg.tau[t], omt[t] = cfg.one_minus_tau[t];
-  __syncthreads();
-  const double cnt = stat[1] * (double)Q;
-  const float g = gout != nullptr ? gout[0] : 1.f;
-  const float scale = cnt > 0.0 ? (float)((double)g / cnt) : 0.f;
-  const int64_t base = (int64_t)blockIdx.x * kLossTile;
-  if (vec && base + kLossTile <= n) {
-    const float4* __restrict__ y4 = reinterpret_cast<const float4*>(y + base);
-    float4* __restrict__ d4 = reinterpret_cast<float4*>(dy + base);
-    float4 a[kLossPer / 4];
-#pragma unroll
-    for (int u = 0; u < kLossPer / 4; ++u) a[u] = y4[u * kLossThreads + t];
-#pragma unroll
-    for (int u = 0; u < kLossPer / 4; ++u) {
-      unsigned m[4], q[4];
-      pinball_walk((unsigned)base + 4u * (unsigned)(u * kLossThreads + t), Q, m, q);
-      const float yv[4] = {a[u].x, a[u].y, a[u].z, a[u].w};
-      float tv[4], r[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) tv[j] = tg[m[j]];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float s = pinball_slope(tau[q[j]], omt[q[j]], yv[j] - tv[j]);
-        r[j] = is_valid(cfg.mask_mode, cfg.null_val, tv[j]) && s != 0.f ? s * scale : 0.f;
-      }
-      d4[u * kLossThreads + t] = make_float4(r[0], r[1], r[2], r[3]);
-    }
-    return;
-  }
-  float yv[kLossPer], tv[kLossPer];
-  unsigned qv[kLossPer];
-#pragma unroll
-  for (int u = 0; u < kLossPer; ++u) {
-    const int64_t i = base + t + (int64_t)kLossThreads * u;
-    const bool ok = i < n;
-    const unsigned m = ok ? (unsigned)i / Q : 0u;
-    qv[u] = ok ? (unsigned)i - m * Q : 0u;
-    yv[u] = ok ? y[i] : 0.f;
-    tv[u] = ok ? tg[m] : 0.f;
-  }
-#pragma unroll
-  for (int u = 0; u < kLossPer; ++u) {
-    const int64_t i = base + t + (int64_t)kLossThreads * u;
-    if (i < n) {
-      const float s = pinball_slope(tau[qv[u]], omt[qv[u]], yv[u] - tv[u]);
-      dy[i] = is_valid(cfg.mask_mode, cfg.null_val, tv[u]) && s != 0.f ? s * scale : 0.f;
-    }
-  }
-}
-
-// The calibration sums of (B, N, P, Q) predictions against (B, N, P) targets: metrics_masked_kernel's
-// shape (a workgroup owns a strip of 256 / P nodes, thread nl P + p walks the samples of element
-// (n0 + nl, p)) with 2 + 3 Q sums per thread: valid count, crossing count and, per level, the pinball
-// sum (fp32 term), the count of t <= y_q (fp32 compare) and the sum of y_q (exact as doubles).
-// A thread reads the Q floats of its entry (the wave: 64 Q contiguous floats, every byte used) and
-// keeps its sums in registers; the loops over q are unrolled to kMaxQ under the uniform q < Q so
-// every index is a constant.  The LDS folds go kQmChunk columns at a time.
-constexpr int kQmThreads = 256, kQmCols = 2 + 3 * kMaxQ, kQmChunk = 8, kQmFold = 8;
-
-__global__ __launch_bounds__(kQmThreads) void metrics_quantile_kernel(int B, int N, int P, PinballArgs cfg,
+__global__ __launch_bounds__(kMetThreads) void metrics_quantile_kernel(int B, int N, int P, PinballArgs cfg,
                                                                      const float* __restrict__ pred,
                                                                      const float* __restrict__ tg,
                                                                      double* __restrict__ part, int* ticket,
                                                                      double* __restrict__ htable,
                                                                      double* __restrict__ ntable) {
-  __shared__ double red[kQmChunk][kQmThreads];
+  __shared__ double red[kQmChunk][kMetThreads];
   __shared__ int last;
   const int t = threadIdx.x;
   const int Q = cfg.num_quantiles, cols = 2 + 3 * Q;
-  const int TN = kQmThreads / P;
+  const int TN = kMetThreads / P;
   const int n0 = (int)blockIdx.x * TN;       // (the grid is ceil(N / TN): n0 < N)
   const int tn = N - n0 < TN ? N - n0 : TN;  // nodes of this strip
   double s[kQmCols];
@@ -569,7 +573,7 @@ __global__ __launch_bounds__(kQmThreads) void metrics_quantile_kernel(int B, int
     const int cw = cols - c0 < kQmChunk ? cols - c0 : kQmChunk;  // columns of this chunk
     // per node, over p in order; this workgroup is the only one that ever touches these rows
     if (ntable != nullptr) {
-      for (int item = t; item < cw * tn; item += kQmThreads) {
+      for (int item = t; item < cw * tn; item += kMetThreads) {
         const int nl = item / cw, j = item - nl * cw;
         double a = 0.0;
         for (int p = 0; p < P; ++p) a += red[j][nl * P + p];
@@ -577,7 +581,7 @@ __global__ __launch_bounds__(kQmThreads) void metrics_quantile_kernel(int B, int
       }
     }
     // per horizon, over nl in order (the idle rows of a partial strip hold zeros)
-    for (int item = t; item < cw * P; item += kQmThreads) {
+    for (int item = t; item < cw * P; item += kMetThreads) {
       const int j = item / P, p = item - j * P;
       double a = 0.0;
       for (int nl = 0; nl < TN; ++nl) a += red[j][nl * P + p];
@@ -585,19 +589,7 @@ __global__ __launch_bounds__(kQmThreads) void metrics_quantile_kernel(int B, int
     }
   }
   if (!last_arrival(ticket, (int)gridDim.x, &last)) return;
-  const int G = (int)gridDim.x;
-  for (int item = t; item < items; item += kQmThreads) {
-    const int c = item / P, p = item - c * P;
-    double a = 0.0;
-    for (int k0 = 0; k0 < G; k0 += kQmFold) {
-      double u[kQmFold];
-#pragma unroll
-      for (int k = 0; k < kQmFold; ++k) u[k] = k0 + k < G ? ld_agent(part + (int64_t)(k0 + k) * items + item) : 0.0;
-#pragma unroll
-      for (int k = 0; k < kQmFold; ++k) a += u[k];
-    }
-    htable[p * cols + c] += a;
-  }
+  fold_into_table(part, P, cols, htable);
 }
 
 int64_t loss_grid(int64_t n) {
@@ -611,46 +603,112 @@ int64_t metrics_grid(int64_t rows, int P) {
   return g < 1 ? 1 : g > kMetMaxWg ? kMetMaxWg : g;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// the checks shared by forward and backward (nothing here touches the device); cfg normalised:
-// smooth_l1 at beta = 0 is mae, and a NaN null value selects the NaN mask
-int loss_args(const char* who, const dstagnn_loss_cfg* cfg, int64_t n, const void* y, const void* target,
-              dstagnn_loss_cfg* out) {
-  const std::string w(who);
-  if (!cfg || !y || !target) {
-    set_last_error(w + ": null cfg / y / target");
-    return DSTAGNN_E_ARG;
-  }
-  if (n <= 0 || n >= (1ll << 31)) {
-    set_last_error(w + ": n must be in [1, 2^31)");
-    return DSTAGNN_E_ARG;
-  }
-  if (cfg->kind < DSTAGNN_LOSS_SMOOTH_L1 || cfg->kind > DSTAGNN_LOSS_MSE) {
-    set_last_error(w + ": unknown loss kind " + std::to_string(cfg->kind));
-    return DSTAGNN_E_ARG;
-  }
-  if (cfg->mask_mode < DSTAGNN_MASK_NONE || cfg->mask_mode > DSTAGNN_MASK_NAN) {
-    set_last_error(w + ": unknown mask mode " + std::to_string(cfg->mask_mode));
-    return DSTAGNN_E_ARG;
-  }
-  if (!(cfg->param >= 0.f)) {  // (a NaN fails too)
-    set_last_error(w + ": negative or NaN param (beta / delta)");
-    return DSTAGNN_E_ARG;
-  }
-  *out = *cfg;
-  if (out->kind == DSTAGNN_LOSS_SMOOTH_L1 && out->param == 0.f) out->kind = DSTAGNN_LOSS_MAE;
-  if (out->mask_mode == DSTAGNN_MASK_NEQ && std::isnan(out->null_val)) out->mask_mode = DSTAGNN_MASK_NAN;
-  return 0;
-}
-
-// ceil(N / (256 / P)) workgroups, or 0 for a shape the masked metrics reject
+// ceil(N / (256 / P)) workgroups, or 0 for a shape the strip kernels reject
 int64_t masked_grid(int64_t B, int64_t N, int P) {
   if (P < 1 || P > kMetMaxP || B <= 0 || N <= 0) return 0;
   const int64_t lim = (1ll << 31) - 1;
   if (N > lim / P || B > lim / (N * P)) return 0;  // B N P >= 2^31
-  const int64_t TN = kMmThreads / P;
+  const int64_t TN = kMetThreads / P;
   return (N + TN - 1) / TN;
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// ---- the checks every entry point shares (nothing here touches the device); w: the entry's name ----
+int fail(const std::string& text, int rc) {
+  set_last_error(text);
+  return rc;
+}
+
+// the mask-mode range, and the rule that a NaN null value under the != mode selects the NaN mask
+int mask_arg(const std::string& w, int* mask_mode, float null_val) {
+  if (*mask_mode < DSTAGNN_MASK_NONE || *mask_mode > DSTAGNN_MASK_NAN)
+    return fail(w + ": unknown mask mode " + std::to_string(*mask_mode), DSTAGNN_E_ARG);
+  if (*mask_mode == DSTAGNN_MASK_NEQ && std::isnan(null_val)) *mask_mode = DSTAGNN_MASK_NAN;
+  return 0;
+}
+
+// P of a score table; axis: what the entry calls it
+int horizon_arg(const std::string& w, int P, const char* axis) {
+  if (P < 1 || P > kMetMaxP)
+    return fail(w + ": P (the " + axis + " axis) must be in [1, 256], got " + std::to_string(P), DSTAGNN_E_SHAPE);
+  return 0;
+}
+
+// the (B, N, P) extent of a strip kernel, times Q values per entry; extent: its text; -> the grid
+int strip_arg(const std::string& w, int64_t B, int64_t N, int P, int Q, const char* extent, int64_t* grid) {
+  *grid = masked_grid(B, N, P);
+  if (*grid == 0 || B * N * P > ((1ll << 31) - 1) / Q)
+    return fail(w + ": B and N must be >= 1 and " + extent + " in [1, 2^31)", DSTAGNN_E_SHAPE);
+  return 0;
+}
+
+// need: the entry's scratch-size function applied to its shape; call: that function as the header writes it
+int scratch_arg(const std::string& w, size_t scratch_bytes, int64_t need, const char* call) {
+  if (scratch_bytes < (size_t)need) return fail(w + ": scratch smaller than " + call, DSTAGNN_E_SPACE);
+  return 0;
+}
+
+// the stream's ticket counter for one hand-off (zero between launches), or null with the error set
+int* ticket_arg(const std::string& w, hipStream_t st) {
+  int* ticket = stream_counters(st, 1);
+  if (!ticket) set_last_error(w + ": no ticket counter for this stream");
+  return ticket;
+}
+
+// the checks shared by the criterion's forward and backward; cfg normalised: smooth_l1 at beta = 0
+// is mae, the mask as mask_arg leaves it
+int loss_args(const std::string& w, const dstagnn_loss_cfg* cfg, int64_t n, const void* y, const void* target,
+              dstagnn_loss_cfg* out) {
+  if (!cfg || !y || !target) return fail(w + ": null cfg / y / target", DSTAGNN_E_ARG);
+  if (n <= 0 || n >= (1ll << 31)) return fail(w + ": n must be in [1, 2^31)", DSTAGNN_E_ARG);
+  if (cfg->kind < DSTAGNN_LOSS_SMOOTH_L1 || cfg->kind > DSTAGNN_LOSS_MSE)
+    return fail(w + ": unknown loss kind " + std::to_string(cfg->kind), DSTAGNN_E_ARG);
+  *out = *cfg;
+  if (int rc = mask_arg(w, &out->mask_mode, out->null_val)) return rc;
+  if (!(cfg->param >= 0.f))  // (a NaN fails too)
+    return fail(w + ": negative or NaN param (beta / delta)", DSTAGNN_E_ARG);
+  if (out->kind == DSTAGNN_LOSS_SMOOTH_L1 && out->param == 0.f) out->kind = DSTAGNN_LOSS_MAE;
+  return 0;
+}
+
+// the level rule (include/dstagnn.h): 1 <= Q <= 16 levels, each strictly inside (0, 1), strictly
+// increasing; the mask as mask_arg leaves it.  Fills the kernels' argument block.
+int pinball_args(const std::string& w, const dstagnn_pinball_cfg* cfg, PinballArgs* out) {
+  if (!cfg) return fail(w + ": null cfg", DSTAGNN_E_ARG);
+  const int Q = cfg->num_quantiles;
+  if (Q < 1 || Q > kMaxQ)
+    return fail(w + ": num_quantiles must be in [1, " + std::to_string(kMaxQ) + "], got " + std::to_string(Q),
+                DSTAGNN_E_ARG);
+  for (int q = 0; q < Q; ++q) {
+    const float v = cfg->tau[q];
+    if (!(v > 0.f && v < 1.f))  // (a NaN fails too)
+      return fail(w + ": every quantile level must be strictly inside (0, 1), got " + std::to_string(v),
+                  DSTAGNN_E_ARG);
+    if (q > 0 && !(cfg->tau[q - 1] < v))
+      return fail(w + ": the quantile levels must be strictly increasing", DSTAGNN_E_ARG);
+  }
+  out->mask_mode = cfg->mask_mode;
+  out->null_val = cfg->null_val;
+  out->num_quantiles = Q;
+  if (int rc = mask_arg(w, &out->mask_mode, out->null_val)) return rc;
+  for (int q = 0; q < kMaxQ; ++q) {
+    out->tau[q] = q < Q ? cfg->tau[q] : 0.5f;
+    out->one_minus_tau[q] = 1.0f - out->tau[q];  // fp32, once
+  }
+  return 0;
+}
+
+// the checks shared by the pinball criterion's forward and backward; *n = m * Q, the length of the
+// prediction stream
+int pinball_pair(const std::string& w, const dstagnn_pinball_cfg* cfg, int64_t m, const void* y, const void* target,
+                 PinballArgs* out, int64_t* n) {
+  if (int rc = pinball_args(w, cfg, out)) return rc;
+  if (m <= 0 || m > ((1ll << 31) - 1) / out->num_quantiles)
+    return fail(w + ": m must be >= 1 and m * num_quantiles < 2^31", DSTAGNN_E_SHAPE);
+  if (!y || !target) return fail(w + ": null y / target", DSTAGNN_E_ARG);
+  *n = m * out->num_quantiles;
+  return 0;
 }
 
 }  // namespace
@@ -663,22 +721,14 @@ int64_t dstagnn_loss_scratch_bytes(int64_t n) {
 
 int dstagnn_loss_forward(const dstagnn_loss_cfg* cfg, int64_t n, const float* y, const float* target, float* loss,
                          double* stat, void* scratch, size_t scratch_bytes, dstagnn_stream_t stream) {
+  const std::string w("loss_forward");
   dstagnn_loss_cfg c;
-  if (int rc = loss_args("loss_forward", cfg, n, y, target, &c)) return rc;
-  if (!loss || !stat || !scratch) {
-    set_last_error("loss_forward: null loss / stat / scratch");
-    return DSTAGNN_E_ARG;
-  }
-  if (scratch_bytes < (size_t)dstagnn_loss_scratch_bytes(n)) {
-    set_last_error("loss_forward: scratch smaller than dstagnn_loss_scratch_bytes(n)");
-    return DSTAGNN_E_SPACE;
-  }
+  if (int rc = loss_args(w, cfg, n, y, target, &c)) return rc;
+  if (!loss || !stat || !scratch) return fail(w + ": null loss / stat / scratch", DSTAGNN_E_ARG);
+  if (int rc = scratch_arg(w, scratch_bytes, dstagnn_loss_scratch_bytes(n), "dstagnn_loss_scratch_bytes(n)")) return rc;
   hipStream_t st = (hipStream_t)stream;
-  int* ticket = stream_counters(st, 1);
-  if (!ticket) {
-    set_last_error("loss_forward: no ticket counter for this stream");
-    return DSTAGNN_E_ARG;
-  }
+  int* ticket = ticket_arg(w, st);
+  if (!ticket) return DSTAGNN_E_ARG;
   const int vec = aligned16(y) && aligned16(target);
   hipLaunchKernelGGL(loss_fwd_kernel, dim3((unsigned)loss_grid(n)), dim3(kLossThreads), 0, st, c, n, y, target, vec,
                      static_cast<double*>(scratch), ticket, stat, loss);
@@ -688,12 +738,10 @@ int dstagnn_loss_forward(const dstagnn_loss_cfg* cfg, int64_t n, const float* y,
 
 int dstagnn_loss_backward(const dstagnn_loss_cfg* cfg, int64_t n, const float* y, const float* target,
                           const double* stat, const float* gout, float* dy, dstagnn_stream_t stream) {
+  const std::string w("loss_backward");
   dstagnn_loss_cfg c;
-  if (int rc = loss_args("loss_backward", cfg, n, y, target, &c)) return rc;
-  if (!stat || !dy) {
-    set_last_error("loss_backward: null stat / dy");
-    return DSTAGNN_E_ARG;
-  }
+  if (int rc = loss_args(w, cfg, n, y, target, &c)) return rc;
+  if (!stat || !dy) return fail(w + ": null stat / dy", DSTAGNN_E_ARG);
   const int vec = aligned16(y) && aligned16(target) && aligned16(dy);
   const int64_t tiles = (n + kLossTile - 1) / kLossTile;
   hipLaunchKernelGGL(loss_bwd_kernel, dim3((unsigned)tiles), dim3(kLossThreads), 0, (hipStream_t)stream, c, n, y,
@@ -709,28 +757,17 @@ int64_t dstagnn_metrics_scratch_bytes(int64_t rows, int P) {
 
 int dstagnn_metrics_accumulate(int64_t rows, int P, const float* pred, const float* target, float null_val,
                                double* table, void* scratch, size_t scratch_bytes, dstagnn_stream_t stream) {
-  if (P < 1 || P > kMetMaxP) {
-    set_last_error("metrics_accumulate: P (the last axis) must be in [1, 256], got " + std::to_string(P));
-    return DSTAGNN_E_SHAPE;
-  }
-  if (rows <= 0 || rows * (int64_t)P >= (1ll << 31)) {
-    set_last_error("metrics_accumulate: rows * P must be in [1, 2^31)");
-    return DSTAGNN_E_SHAPE;
-  }
-  if (!pred || !target || !table || !scratch) {
-    set_last_error("metrics_accumulate: null pred / target / table / scratch");
-    return DSTAGNN_E_ARG;
-  }
-  if (scratch_bytes < (size_t)dstagnn_metrics_scratch_bytes(rows, P)) {
-    set_last_error("metrics_accumulate: scratch smaller than dstagnn_metrics_scratch_bytes(rows, P)");
-    return DSTAGNN_E_SPACE;
-  }
+  const std::string w("metrics_accumulate");
+  if (int rc = horizon_arg(w, P, "last")) return rc;
+  if (rows <= 0 || rows * (int64_t)P >= (1ll << 31))
+    return fail(w + ": rows * P must be in [1, 2^31)", DSTAGNN_E_SHAPE);
+  if (!pred || !target || !table || !scratch) return fail(w + ": null pred / target / table / scratch", DSTAGNN_E_ARG);
+  if (int rc = scratch_arg(w, scratch_bytes, dstagnn_metrics_scratch_bytes(rows, P),
+                           "dstagnn_metrics_scratch_bytes(rows, P)"))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
-  int* ticket = stream_counters(st, 1);
-  if (!ticket) {
-    set_last_error("metrics_accumulate: no ticket counter for this stream");
-    return DSTAGNN_E_ARG;
-  }
+  int* ticket = ticket_arg(w, st);
+  if (!ticket) return DSTAGNN_E_ARG;
   hipLaunchKernelGGL(metrics_accum_kernel, dim3((unsigned)metrics_grid(rows, P)), dim3(kMetThreads), 0, st,
                      rows * (int64_t)P, P, pred, target, null_val, std::isnan(null_val) ? 1 : 0,
                      static_cast<double*>(scratch), ticket, table);
@@ -745,98 +782,23 @@ int64_t dstagnn_metrics_masked_scratch_bytes(int64_t B, int64_t N, int P) {
 int dstagnn_metrics_accumulate_masked(int64_t B, int64_t N, int P, const float* pred, const float* target,
                                       int mask_mode, float null_val, float mape_null, double* htable,
                                       double* ntable, void* scratch, size_t scratch_bytes, dstagnn_stream_t stream) {
-  if (P < 1 || P > kMetMaxP) {
-    set_last_error("metrics_accumulate_masked: P (the last axis) must be in [1, 256], got " + std::to_string(P));
-    return DSTAGNN_E_SHAPE;
-  }
-  const int64_t grid = masked_grid(B, N, P);
-  if (grid == 0) {
-    set_last_error("metrics_accumulate_masked: B and N must be >= 1 and B * N * P in [1, 2^31)");
-    return DSTAGNN_E_SHAPE;
-  }
-  if (!pred || !target || !htable || !scratch) {
-    set_last_error("metrics_accumulate_masked: null pred / target / htable / scratch");
-    return DSTAGNN_E_ARG;
-  }
-  if (mask_mode < DSTAGNN_MASK_NONE || mask_mode > DSTAGNN_MASK_NAN) {
-    set_last_error("metrics_accumulate_masked: unknown mask mode " + std::to_string(mask_mode));
-    return DSTAGNN_E_ARG;
-  }
-  if (scratch_bytes < (size_t)dstagnn_metrics_masked_scratch_bytes(B, N, P)) {
-    set_last_error("metrics_accumulate_masked: scratch smaller than dstagnn_metrics_masked_scratch_bytes(B, N, P)");
-    return DSTAGNN_E_SPACE;
-  }
-  if (mask_mode == DSTAGNN_MASK_NEQ && std::isnan(null_val)) mask_mode = DSTAGNN_MASK_NAN;  // as loss_args
+  const std::string w("metrics_accumulate_masked");
+  int64_t grid = 0;
+  if (int rc = horizon_arg(w, P, "last")) return rc;
+  if (int rc = strip_arg(w, B, N, P, 1, "B * N * P", &grid)) return rc;
+  if (!pred || !target || !htable || !scratch) return fail(w + ": null pred / target / htable / scratch", DSTAGNN_E_ARG);
+  if (int rc = mask_arg(w, &mask_mode, null_val)) return rc;
+  if (int rc = scratch_arg(w, scratch_bytes, dstagnn_metrics_masked_scratch_bytes(B, N, P),
+                           "dstagnn_metrics_masked_scratch_bytes(B, N, P)"))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
-  int* ticket = stream_counters(st, 1);
-  if (!ticket) {
-    set_last_error("metrics_accumulate_masked: no ticket counter for this stream");
-    return DSTAGNN_E_ARG;
-  }
-  hipLaunchKernelGGL(metrics_masked_kernel, dim3((unsigned)grid), dim3(kMmThreads), 0, st, (int)B, (int)N, P, pred,
+  int* ticket = ticket_arg(w, st);
+  if (!ticket) return DSTAGNN_E_ARG;
+  hipLaunchKernelGGL(metrics_masked_kernel, dim3((unsigned)grid), dim3(kMetThreads), 0, st, (int)B, (int)N, P, pred,
                      target, mask_mode, null_val, mape_null, static_cast<double*>(scratch), ticket, htable, ntable);
   DS_CHECK_LAUNCH();
   return 0;
 }
-
-// ---- quantile forecasts -----------------------------------------------------------------------
-namespace {
-
-// the level rule (include/dstagnn.h): 1 <= Q <= 16 levels, each strictly inside (0, 1), strictly
-// increasing; the mask mode as loss_args reads it.  Fills the kernels' argument block.
-int pinball_args(const std::string& w, const dstagnn_pinball_cfg* cfg, PinballArgs* out) {
-  if (!cfg) {
-    set_last_error(w + ": null cfg");
-    return DSTAGNN_E_ARG;
-  }
-  const int Q = cfg->num_quantiles;
-  if (Q < 1 || Q > kMaxQ) {
-    set_last_error(w + ": num_quantiles must be in [1, " + std::to_string(kMaxQ) + "], got " + std::to_string(Q));
-    return DSTAGNN_E_ARG;
-  }
-  for (int q = 0; q < Q; ++q) {
-    const float v = cfg->tau[q];
-    if (!(v > 0.f && v < 1.f)) {  // (a NaN fails too)
-      set_last_error(w + ": every quantile level must be strictly inside (0, 1), got " + std::to_string(v));
-      return DSTAGNN_E_ARG;
-    }
-    if (q > 0 && !(cfg->tau[q - 1] < v)) {
-      set_last_error(w + ": the quantile levels must be strictly increasing");
-      return DSTAGNN_E_ARG;
-    }
-  }
-  if (cfg->mask_mode < DSTAGNN_MASK_NONE || cfg->mask_mode > DSTAGNN_MASK_NAN) {
-    set_last_error(w + ": unknown mask mode " + std::to_string(cfg->mask_mode));
-    return DSTAGNN_E_ARG;
-  }
-  out->mask_mode = cfg->mask_mode;
-  out->null_val = cfg->null_val;
-  out->num_quantiles = Q;
-  if (out->mask_mode == DSTAGNN_MASK_NEQ && std::isnan(out->null_val)) out->mask_mode = DSTAGNN_MASK_NAN;
-  for (int q = 0; q < kMaxQ; ++q) {
-    out->tau[q] = q < Q ? cfg->tau[q] : 0.5f;
-    out->one_minus_tau[q] = 1.0f - out->tau[q];  // fp32, once
-  }
-  return 0;
-}
-
-// the checks shared by forward and backward; *n = m * Q, the length of the prediction stream
-int pinball_pair(const std::string& w, const dstagnn_pinball_cfg* cfg, int64_t m, const void* y, const void* target,
-                 PinballArgs* out, int64_t* n) {
-  if (int rc = pinball_args(w, cfg, out)) return rc;
-  if (m <= 0 || m > ((1ll << 31) - 1) / out->num_quantiles) {
-    set_last_error(w + ": m must be >= 1 and m * num_quantiles < 2^31");
-    return DSTAGNN_E_SHAPE;
-  }
-  if (!y || !target) {
-    set_last_error(w + ": null y / target");
-    return DSTAGNN_E_ARG;
-  }
-  *n = m * out->num_quantiles;
-  return 0;
-}
-
-}  // namespace
 
 int64_t dstagnn_pinball_scratch_bytes(int64_t m, int num_quantiles) {
   if (m <= 0 || num_quantiles < 1 || num_quantiles > kMaxQ || m > ((1ll << 31) - 1) / num_quantiles) return 0;
@@ -846,23 +808,17 @@ int64_t dstagnn_pinball_scratch_bytes(int64_t m, int num_quantiles) {
 int dstagnn_pinball_forward(const dstagnn_pinball_cfg* cfg, int64_t m, const float* y, const float* target,
                             float* loss, double* stat, void* scratch, size_t scratch_bytes,
                             dstagnn_stream_t stream) {
+  const std::string w("pinball_forward");
   PinballArgs a;
   int64_t n = 0;
-  if (int rc = pinball_pair("pinball_forward", cfg, m, y, target, &a, &n)) return rc;
-  if (!loss || !stat || !scratch) {
-    set_last_error("pinball_forward: null loss / stat / scratch");
-    return DSTAGNN_E_ARG;
-  }
-  if (scratch_bytes < (size_t)dstagnn_pinball_scratch_bytes(m, a.num_quantiles)) {
-    set_last_error("pinball_forward: scratch smaller than dstagnn_pinball_scratch_bytes(m, num_quantiles)");
-    return DSTAGNN_E_SPACE;
-  }
+  if (int rc = pinball_pair(w, cfg, m, y, target, &a, &n)) return rc;
+  if (!loss || !stat || !scratch) return fail(w + ": null loss / stat / scratch", DSTAGNN_E_ARG);
+  if (int rc = scratch_arg(w, scratch_bytes, dstagnn_pinball_scratch_bytes(m, a.num_quantiles),
+                           "dstagnn_pinball_scratch_bytes(m, num_quantiles)"))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
-  int* ticket = stream_counters(st, 1);
-  if (!ticket) {
-    set_last_error("pinball_forward: no ticket counter for this stream");
-    return DSTAGNN_E_ARG;
-  }
+  int* ticket = ticket_arg(w, st);
+  if (!ticket) return DSTAGNN_E_ARG;
   const int vec = aligned16(y);  // (the target is read through the cache, one float at a time)
   hipLaunchKernelGGL(pinball_fwd_kernel, dim3((unsigned)loss_grid(n)), dim3(kLossThreads), 0, st, a, n, y, target, vec,
                      static_cast<double*>(scratch), ticket, stat, loss);
@@ -872,13 +828,11 @@ int dstagnn_pinball_forward(const dstagnn_pinball_cfg* cfg, int64_t m, const flo
 
 int dstagnn_pinball_backward(const dstagnn_pinball_cfg* cfg, int64_t m, const float* y, const float* target,
                              const double* stat, const float* gout, float* dy, dstagnn_stream_t stream) {
+  const std::string w("pinball_backward");
   PinballArgs a;
   int64_t n = 0;
-  if (int rc = pinball_pair("pinball_backward", cfg, m, y, target, &a, &n)) return rc;
-  if (!stat || !dy) {
-    set_last_error("pinball_backward: null stat / dy");
-    return DSTAGNN_E_ARG;
-  }
+  if (int rc = pinball_pair(w, cfg, m, y, target, &a, &n)) return rc;
+  if (!stat || !dy) return fail(w + ": null stat / dy", DSTAGNN_E_ARG);
   const int vec = aligned16(y) && aligned16(dy);
   const int64_t tiles = (n + kLossTile - 1) / kLossTile;
   hipLaunchKernelGGL(pinball_bwd_kernel, dim3((unsigned)tiles), dim3(kLossThreads), 0, (hipStream_t)stream, a, n, y,
@@ -898,41 +852,24 @@ int dstagnn_metrics_accumulate_quantile(int64_t B, int64_t N, int P, const dstag
                                         const float* pred, const float* target, double* htable, double* ntable,
                                         void* scratch, size_t scratch_bytes, dstagnn_stream_t stream) {
   const std::string w("metrics_accumulate_quantile");
-  if (!cfg) {
-    set_last_error(w + ": null cfg");
-    return DSTAGNN_E_ARG;
-  }
-  if (P < 1 || P > kMetMaxP) {
-    set_last_error(w + ": P (the horizon axis) must be in [1, 256], got " + std::to_string(P));
-    return DSTAGNN_E_SHAPE;
-  }
+  if (!cfg) return fail(w + ": null cfg", DSTAGNN_E_ARG);
+  if (int rc = horizon_arg(w, P, "horizon")) return rc;
   const int Q = cfg->num_quantiles;
-  if (Q < 1 || Q > kMaxQ) {
-    set_last_error(w + ": Q (the last axis) must be in [1, " + std::to_string(kMaxQ) + "], got " + std::to_string(Q));
-    return DSTAGNN_E_SHAPE;
-  }
-  const int64_t grid = masked_grid(B, N, P);
-  if (grid == 0 || B * N * P > ((1ll << 31) - 1) / Q) {
-    set_last_error(w + ": B and N must be >= 1 and B * N * P * Q in [1, 2^31)");
-    return DSTAGNN_E_SHAPE;
-  }
-  if (!pred || !target || !htable || !scratch) {
-    set_last_error(w + ": null pred / target / htable / scratch");
-    return DSTAGNN_E_ARG;
-  }
+  if (Q < 1 || Q > kMaxQ)
+    return fail(w + ": Q (the last axis) must be in [1, " + std::to_string(kMaxQ) + "], got " + std::to_string(Q),
+                DSTAGNN_E_SHAPE);
+  int64_t grid = 0;
+  if (int rc = strip_arg(w, B, N, P, Q, "B * N * P * Q", &grid)) return rc;
+  if (!pred || !target || !htable || !scratch) return fail(w + ": null pred / target / htable / scratch", DSTAGNN_E_ARG);
   PinballArgs a;
   if (int rc = pinball_args(w, cfg, &a)) return rc;
-  if (scratch_bytes < (size_t)dstagnn_metrics_quantile_scratch_bytes(B, N, P, Q)) {
-    set_last_error(w + ": scratch smaller than dstagnn_metrics_quantile_scratch_bytes(B, N, P, Q)");
-    return DSTAGNN_E_SPACE;
-  }
+  if (int rc = scratch_arg(w, scratch_bytes, dstagnn_metrics_quantile_scratch_bytes(B, N, P, Q),
+                           "dstagnn_metrics_quantile_scratch_bytes(B, N, P, Q)"))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
-  int* ticket = stream_counters(st, 1);
-  if (!ticket) {
-    set_last_error(w + ": no ticket counter for this stream");
-    return DSTAGNN_E_ARG;
-  }
-  hipLaunchKernelGGL(metrics_quantile_kernel, dim3((unsigned)grid), dim3(kQmThreads), 0, st, (int)B, (int)N, P, a,
+  int* ticket = ticket_arg(w, st);
+  if (!ticket) return DSTAGNN_E_ARG;
+  hipLaunchKernelGGL(metrics_quantile_kernel, dim3((unsigned)grid), dim3(kMetThreads), 0, st, (int)B, (int)N, P, a,
                      pred, target, static_cast<double*>(scratch), ticket, htable, ntable);
   DS_CHECK_LAUNCH();
   return 0;

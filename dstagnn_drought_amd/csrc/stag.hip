@@ -24,17 +24,6 @@ namespace {
 constexpr int kPrepThreads = 256;
 constexpr int kLdsMax = 160 * 1024;
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 struct WaveMin {
   __device__ emd::Cand operator()(emd::Cand c) const {
 #pragma unroll
@@ -54,7 +43,7 @@ struct WaveSync {
 
 // block reduction over kPrepThreads threads (double)
 __device__ double block_sum(double v, double* red) {
-  v = wave_sum_d(v);
+  v = wave_sum(v);
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   __syncthreads();
   if (l == 0) red[w] = v;
@@ -194,7 +183,7 @@ __global__ __launch_bounds__(64) void stag_emd_kernel(const double* __restrict__
     int st = 0;
     int64_t piv = 0;
     double obj = emd::solve<64>(w, lane, WaveMin(), WaveSync(), 1.0, &st, &piv);
-    obj = wave_sum_d(obj);
+    obj = wave_sum(obj);
     if (lane == 0) { out[k] = obj; status[k] = st; if (pivots) pivots[k] = piv; }
     __syncthreads();
   }
@@ -238,7 +227,7 @@ __global__ __launch_bounds__(64) void stag_emd_masked_kernel(
     int st = 0;
     int64_t piv = 0;
     double obj = emd::solve<64>(w, lane, WaveMin(), WaveSync(), 1.0, &st, &piv);
-    obj = wave_sum_d(obj);
+    obj = wave_sum(obj);
     if (lane == 0) { out[k] = obj; status[k] = st; if (pivots) pivots[k] = piv; }
     __syncthreads();
   }
@@ -261,7 +250,7 @@ __global__ __launch_bounds__(64) void emd_dense_kernel(const double* __restrict_
       sp += a; sq += b;
       if (a < 0.0 || b < 0.0) neg = 1.0;
     }
-    sp = wave_sum_d(sp); sq = wave_sum_d(sq); neg = wave_max_d(neg);
+    sp = wave_sum(sp); sq = wave_sum(sq); neg = wave_max(neg);
     if (neg > 0.0 || !emd::balanced(sp, sq)) {
       if (lane == 0) { out[k] = 1.0; status[k] = 1; }
       continue;
@@ -269,12 +258,12 @@ __global__ __launch_bounds__(64) void emd_dense_kernel(const double* __restrict_
     w.Dm = D + k * (int64_t)T * T;
     double cm = 0.0;
     for (int64_t e = lane; e < (int64_t)T * T; e += 64) cm = fmax(cm, fabs(emd::clean_cost(w.Dm[e])));
-    cm = wave_max_d(cm);
+    cm = wave_max(cm);
     __syncthreads();
     int st = 0;
     int64_t piv = 0;
     double obj = emd::solve<64>(w, lane, WaveMin(), WaveSync(), cm, &st, &piv);
-    obj = wave_sum_d(obj);
+    obj = wave_sum(obj);
     if (lane == 0) { out[k] = obj; status[k] = st; }
     __syncthreads();
   }

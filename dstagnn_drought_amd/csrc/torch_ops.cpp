@@ -974,6 +974,17 @@ void check_loss_pair(const Tensor& y, const Tensor& target, const char* who) {
   TORCH_CHECK(y.device() == target.device(), who, ": y and target on different devices");
 }
 
+// the backward's saved state: the forward's two doubles and the optional one-float upstream gradient
+void check_stat_gout(const Tensor& y, const Tensor& stat, const c10::optional<Tensor>& gout, const char* who,
+                     const char* fwd) {
+  check_dev(stat, at::kDouble, "stat");
+  TORCH_CHECK(stat.numel() == 2 && stat.device() == y.device(), who, ": stat must be ", fwd, "'s two doubles");
+  if (gout.has_value() && gout->defined()) {
+    check_dev(*gout, at::kFloat, "gout");
+    TORCH_CHECK(gout->numel() == 1 && gout->device() == y.device(), who, ": gout must be one float on y's device");
+  }
+}
+
 // -> (loss: 0-dim fp32, stat: {fp64 sum of the terms, valid count}); no host sync
 std::tuple<Tensor, Tensor> loss_fwd(const Tensor& y, const Tensor& target, int64_t kind, double param,
                                     int64_t mask_mode, double null_val) {
@@ -995,12 +1006,7 @@ std::tuple<Tensor, Tensor> loss_fwd(const Tensor& y, const Tensor& target, int64
 Tensor loss_bwd(const Tensor& y, const Tensor& target, const Tensor& stat, const c10::optional<Tensor>& gout,
                 int64_t kind, double param, int64_t mask_mode, double null_val) {
   check_loss_pair(y, target, "loss_bwd");
-  check_dev(stat, at::kDouble, "stat");
-  TORCH_CHECK(stat.numel() == 2 && stat.device() == y.device(), "loss_bwd: stat must be loss_fwd's two doubles");
-  if (gout.has_value() && gout->defined()) {
-    check_dev(*gout, at::kFloat, "gout");
-    TORCH_CHECK(gout->numel() == 1 && gout->device() == y.device(), "loss_bwd: gout must be one float on y's device");
-  }
+  check_stat_gout(y, stat, gout, "loss_bwd", "loss_fwd");
   c10::DeviceGuard guard(y.device());
   const dstagnn_loss_cfg cfg = loss_cfg(kind, param, mask_mode, null_val);
   Tensor dy = at::empty(y.sizes(), f32(y));
@@ -1100,13 +1106,7 @@ std::tuple<Tensor, Tensor> pinball_fwd(const Tensor& y, const Tensor& target, c1
 Tensor pinball_bwd(const Tensor& y, const Tensor& target, const Tensor& stat, const c10::optional<Tensor>& gout,
                    c10::ArrayRef<double> quantiles, int64_t mask_mode, double null_val) {
   check_pinball_pair(y, target, quantiles.size(), "pinball_bwd");
-  check_dev(stat, at::kDouble, "stat");
-  TORCH_CHECK(stat.numel() == 2 && stat.device() == y.device(), "pinball_bwd: stat must be pinball_fwd's two doubles");
-  if (gout.has_value() && gout->defined()) {
-    check_dev(*gout, at::kFloat, "gout");
-    TORCH_CHECK(gout->numel() == 1 && gout->device() == y.device(),
-                "pinball_bwd: gout must be one float on y's device");
-  }
+  check_stat_gout(y, stat, gout, "pinball_bwd", "pinball_fwd");
   c10::DeviceGuard guard(y.device());
   const dstagnn_pinball_cfg cfg = pinball_cfg(quantiles, mask_mode, null_val);
   Tensor dy = at::empty(y.sizes(), f32(y));

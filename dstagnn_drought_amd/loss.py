@@ -110,7 +110,65 @@ class HipLoss(nn.Module):
         return _lib.load().loss_fwd(input, target, *self._cfg)[0]  # nothing saved
 
 
-class ForecastMetrics:
+class _RunningTables:
+    """What ``ForecastMetrics`` and ``QuantileMetrics`` share: the checked horizon and node counts,
+    the device, the mask of ``missing_value``, the running fp64 tables (``table`` (P, cols) and
+    ``node_table`` (num_nodes, cols) or None) and their reset / merge / all-reduce.  A subclass
+    supplies ``scores_of_table`` and ``_config()``."""
+
+    def _check_horizon(self, num_for_predict):
+        self.P = int(num_for_predict)
+        if not 1 <= self.P <= 256:
+            raise ValueError(f"{type(self).__name__}: num_for_predict must be in [1, 256], got {num_for_predict!r}")
+
+    def _init_tables(self, cols, device, missing_value, num_nodes):
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(HIP_ONLY)
+        self.missing_value = None if missing_value is None else float(missing_value)
+        self.num_nodes = None if num_nodes is None else int(num_nodes)
+        if self.num_nodes is not None and self.num_nodes < 1:
+            raise ValueError(f"{type(self).__name__}: num_nodes must be >= 1, got {num_nodes!r}")
+        self._mask = mask_of(missing_value)
+        self.table = torch.zeros(self.P, cols, dtype=torch.float64, device=device)
+        self.node_table = (None if self.num_nodes is None else
+                           torch.zeros(self.num_nodes, cols, dtype=torch.float64, device=device))
+
+    def _check_nodes(self, pred, axis):
+        if self.num_nodes is not None and pred.shape[axis] != self.num_nodes:
+            raise ValueError(f"{type(self).__name__}: pred {tuple(pred.shape)} has {pred.shape[axis]} nodes, "
+                             f"num_nodes is {self.num_nodes}")
+
+    def reset(self):
+        self.table.zero_()
+        if self.node_table is not None:
+            self.node_table.zero_()
+
+    def node_scores(self):
+        if self.node_table is None:
+            raise ValueError(f"{type(self).__name__}: node_scores() needs num_nodes")
+        return self.scores_of_table(self.node_table.cpu().numpy(), overall=False)
+
+    def merge(self, other):
+        """Adds ``other``'s tables into this object's (the sums are additive)."""
+        if not isinstance(other, type(self)) or other._config() != self._config():
+            raise ValueError(f"{type(self).__name__}.merge: the other object has a different configuration")
+        self.table += other.table.to(self.table.device)
+        if self.node_table is not None:
+            self.node_table += other.node_table.to(self.node_table.device)
+        return self
+
+    def all_reduce(self):
+        """One SUM all-reduce per table when a process group is up; nothing otherwise."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(self.table)
+            if self.node_table is not None:
+                dist.all_reduce(self.node_table)
+        return self
+
+
+class ForecastMetrics(_RunningTables):
     """Running per-horizon scores of (S, N, P) predictions against their targets.
 
     ``update(pred, target)``: one launch, no sync.  ``compute()``: one device-to-host copy; the
@@ -136,28 +194,14 @@ class ForecastMetrics:
     object's tables; ``all_reduce()`` sums them over the ranks of the process group."""
 
     def __init__(self, num_for_predict, null_val=0.0, device=None, *, missing_value=None, num_nodes=None):
-        self.P = int(num_for_predict)
-        if not 1 <= self.P <= 256:
-            raise ValueError(f"ForecastMetrics: num_for_predict must be in [1, 256], got {num_for_predict!r}")
+        self._check_horizon(num_for_predict)
         self.null_val = float(null_val)
-        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError(HIP_ONLY)
-        self.missing_value = None if missing_value is None else float(missing_value)
-        self.num_nodes = None if num_nodes is None else int(num_nodes)
-        if self.num_nodes is not None and self.num_nodes < 1:
-            raise ValueError(f"ForecastMetrics: num_nodes must be >= 1, got {num_nodes!r}")
         self.masked = missing_value is not None or num_nodes is not None
-        self._mask = mask_of(missing_value)
-        self.table = torch.zeros(self.P, 8 if self.masked else 4, dtype=torch.float64, device=device)
-        self.node_table = (None if self.num_nodes is None else
-                           torch.zeros(self.num_nodes, 8, dtype=torch.float64, device=device))
+        self._init_tables(8 if self.masked else 4, device, missing_value, num_nodes)
         self.rows = 0
 
     def reset(self):
-        self.table.zero_()
-        if self.node_table is not None:
-            self.node_table.zero_()
+        super().reset()
         self.rows = 0
 
     def update(self, pred, target):
@@ -178,9 +222,7 @@ class ForecastMetrics:
         if pred.shape != target.shape or pred.dim() < 2 or pred.shape[-1] != self.P:
             raise ValueError(f"ForecastMetrics: pred {tuple(pred.shape)} / target {tuple(target.shape)} must be "
                              f"equal (..., N, {self.P}) shapes")
-        if self.num_nodes is not None and pred.shape[-2] != self.num_nodes:
-            raise ValueError(f"ForecastMetrics: pred {tuple(pred.shape)} has {pred.shape[-2]} nodes, "
-                             f"num_nodes is {self.num_nodes}")
+        self._check_nodes(pred, -2)
         if not (pred.is_cuda and target.is_cuda):
             raise RuntimeError(HIP_ONLY)
         if pred.numel() == 0:
@@ -253,21 +295,12 @@ class ForecastMetrics:
     def scores(self):
         return self.scores_of_table(self.table.cpu().numpy(), self.rows)
 
-    def node_scores(self):
-        if self.node_table is None:
-            raise ValueError("ForecastMetrics: node_scores() needs num_nodes")
-        return self.scores_of_table(self.node_table.cpu().numpy(), overall=False)
-
     def _config(self):
         return (self.P, repr(self.null_val), self.masked, self._mask[0], repr(self._mask[1]), self.num_nodes)
 
     def merge(self, other):
         """Adds ``other``'s tables and row count into this object's (the sums are additive)."""
-        if not isinstance(other, ForecastMetrics) or other._config() != self._config():
-            raise ValueError("ForecastMetrics.merge: the other object has a different configuration")
-        self.table += other.table.to(self.table.device)
-        if self.node_table is not None:
-            self.node_table += other.node_table.to(self.node_table.device)
+        super().merge(other)
         self.rows += other.rows
         return self
 
@@ -275,14 +308,11 @@ class ForecastMetrics:
         """One SUM all-reduce per table (and one of the row count) when a process group is up;
         nothing otherwise."""
         import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized()):
-            return self
-        dist.all_reduce(self.table)
-        if self.node_table is not None:
-            dist.all_reduce(self.node_table)
-        rows = torch.tensor([self.rows], dtype=torch.int64, device=self.table.device)
-        dist.all_reduce(rows)
-        self.rows = int(rows.item())
+        if dist.is_available() and dist.is_initialized():
+            super().all_reduce()
+            rows = torch.tensor([self.rows], dtype=torch.int64, device=self.table.device)
+            dist.all_reduce(rows)
+            self.rows = int(rows.item())
         return self
 
 
@@ -382,7 +412,7 @@ class QuantileLoss(nn.Module):
         return _lib.load().pinball_fwd(input, target, *self._cfg)[0]  # nothing saved
 
 
-class QuantileMetrics:
+class QuantileMetrics(_RunningTables):
     """Running calibration scores of (S, N, P, Q) quantile predictions against (S, N, P) targets,
     in the mould of ``ForecastMetrics``: ``update(pred, target)`` is one launch of
     ``metrics_quantile_kernel`` and no sync, no prediction is copied to the host.
@@ -404,38 +434,18 @@ class QuantileMetrics:
     ``merge(other)`` adds another object's tables; ``all_reduce()`` sums them over the ranks."""
 
     def __init__(self, num_for_predict, quantiles, *, missing_value=None, num_nodes=None, device=None):
-        self.P = int(num_for_predict)
-        if not 1 <= self.P <= 256:
-            raise ValueError(f"QuantileMetrics: num_for_predict must be in [1, 256], got {num_for_predict!r}")
+        self._check_horizon(num_for_predict)
         self.quantiles = check_quantiles(quantiles, "QuantileMetrics")
         self.point_index = point_index_of(self.quantiles)
         self.Q = len(self.quantiles)
-        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError(HIP_ONLY)
-        self.missing_value = None if missing_value is None else float(missing_value)
-        self.num_nodes = None if num_nodes is None else int(num_nodes)
-        if self.num_nodes is not None and self.num_nodes < 1:
-            raise ValueError(f"QuantileMetrics: num_nodes must be >= 1, got {num_nodes!r}")
-        self._mask = mask_of(missing_value)
-        cols = 2 + 3 * self.Q
-        self.table = torch.zeros(self.P, cols, dtype=torch.float64, device=device)
-        self.node_table = (None if self.num_nodes is None else
-                           torch.zeros(self.num_nodes, cols, dtype=torch.float64, device=device))
-
-    def reset(self):
-        self.table.zero_()
-        if self.node_table is not None:
-            self.node_table.zero_()
+        self._init_tables(2 + 3 * self.Q, device, missing_value, num_nodes)
 
     def update(self, pred, target):
         if (pred.dim() < 3 or tuple(pred.shape[:-1]) != tuple(target.shape) or pred.shape[-1] != self.Q
                 or pred.shape[-2] != self.P):
             raise ValueError(f"QuantileMetrics: pred {tuple(pred.shape)} / target {tuple(target.shape)} must be "
                              f"(..., N, {self.P}, {self.Q}) and (..., N, {self.P})")
-        if self.num_nodes is not None and pred.shape[-3] != self.num_nodes:
-            raise ValueError(f"QuantileMetrics: pred {tuple(pred.shape)} has {pred.shape[-3]} nodes, "
-                             f"num_nodes is {self.num_nodes}")
+        self._check_nodes(pred, -3)
         if not (pred.is_cuda and target.is_cuda):
             raise RuntimeError(HIP_ONLY)
         if pred.numel() == 0:
@@ -470,29 +480,5 @@ class QuantileMetrics:
     def scores(self):
         return self.scores_of_table(self.table.cpu().numpy())
 
-    def node_scores(self):
-        if self.node_table is None:
-            raise ValueError("QuantileMetrics: node_scores() needs num_nodes")
-        return self.scores_of_table(self.node_table.cpu().numpy(), overall=False)
-
     def _config(self):
         return (self.P, self.quantiles, self._mask[0], repr(self._mask[1]), self.num_nodes)
-
-    def merge(self, other):
-        """Adds ``other``'s tables into this object's (the sums are additive)."""
-        if not isinstance(other, QuantileMetrics) or other._config() != self._config():
-            raise ValueError("QuantileMetrics.merge: the other object has a different configuration")
-        self.table += other.table.to(self.table.device)
-        if self.node_table is not None:
-            self.node_table += other.node_table.to(self.node_table.device)
-        return self
-
-    def all_reduce(self):
-        """One SUM all-reduce per table when a process group is up; nothing otherwise."""
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized()):
-            return self
-        dist.all_reduce(self.table)
-        if self.node_table is not None:
-            dist.all_reduce(self.node_table)
-        return self
