@@ -12,7 +12,9 @@ none per subset) and are added to that module's CONFIGS table at import.
 
 Paths: one child process with DSTAGNN_GEMM_LOG=1 runs every geometry once; a case on the new path
 logs no GEMM of the dTheta shape (M = K F, N = C, K = B N T), a Chebyshev order the predicate
-refuses (K = 6: the KM = 8 template) still logs it.
+refuses (K = 6: the KM = 8 template) still logs it — and so does a batch whose fold rows pass the
+scratch (WS_CASES: the last batch admitted and the first refused at <4, 5>, and the plain forms
+<8, 5>, <6, 5>, <4, 3> just past the bound, which nothing else runs).
 """
 import os
 import subprocess
@@ -37,6 +39,14 @@ GEOM = {  # name: (N, T, K, h, D, dk, C)
     "dth_c16": (40, 12, 3, 3, 64, 32, 16),   # the narrow channel count (<4, 3>)
     "dth_n64": (64, 12, 3, 3, 64, 32, 32),   # with hub = 40: a support row past one 32-entry chunk
     "dth_k6": (40, 12, 6, 3, 64, 32, 32),    # refused (KM = 8): agg_k and the GEMM stay
+    # both sides of the fold-scratch bound (cheb_agg_dtheta_ws_floats <= kGemmWs = 8 388 608 floats), K = 5,
+    # F = C = 32, N = 40: B = 325 is 163 pairs, 1632 workgroup rows of 5120 floats = 8 355 840 (in-kernel);
+    # B = 327 is 1640 rows, 8 396 800 floats (refused: the plain spmm_t2 form, agg_k and the GEMM)
+    "dth_ws_t8": (40, 8, 5, 3, 64, 32, 32),   # <4, 5>
+    "dth_ws_t16": (40, 16, 5, 3, 64, 32, 32),  # <8, 5>
+    "dth_ws_t9": (40, 9, 5, 3, 64, 32, 32),    # <6, 5>, refused at B = 327 like the two above
+    # K = 3: rows of 3072 floats, so the first refused batch is larger; B = 545 is 273 pairs (the last a lone sample), 2736 rows, 8 404 992 floats
+    "dth_ws_k3t7": (40, 7, 3, 3, 64, 32, 32),  # <4, 3>
 }
 P.CONFIGS.update(GEOM)
 
@@ -47,6 +57,10 @@ BASE_CASES = [("dth_base", False, 3, False, 0), ("dth_base", False, 3, True, 0),
 SHAPE_CASES = [("dth_k1", False, 3, False, 0), ("dth_k5", False, 3, False, 0), ("dth_t8", False, 3, False, 0),
                ("dth_t16", False, 3, False, 0), ("dth_c16", False, 3, False, 0), ("dth_n64", False, 3, False, 40)]
 REFUSED = ("dth_k6", False, 3, False, 0)
+# (name, first, B, train, hub) -> whether the dTheta scratch admits the batch
+WS_CASES = {("dth_ws_t8", False, 325, False, 0): True, ("dth_ws_t8", False, 327, False, 0): False,
+            ("dth_ws_t16", False, 327, False, 0): False, ("dth_ws_t9", False, 327, False, 0): False,
+            ("dth_ws_k3t7", False, 545, False, 0): False}
 
 
 def _id(c):
@@ -60,10 +74,30 @@ def test_block_vs_oracle(case):
     _run_config_vs_oracle(name, first, B, train=train, hub=hub, paths={"sparse", "cheb_agg"})
 
 
+@pytest.mark.parametrize("case", list(WS_CASES), ids=_id)
+def test_scratch_bound_sides_vs_oracle(case):
+    """The last batch the fold scratch admits and the first it refuses, at the suite's bound, with
+    test_gpu_parity.FLIP_CAP on the ReLU decisions that differ (these rows compare 5e6 of them).
+    FLIP_CAP's condition, checked on the CPU (seed 3): the fp32 oracle against the fp64 oracle flips
+    0 of 9 984 000 (B = 325, T = 8), 2 of 10 045 440 (B = 327, T = 8), 1 of 20 090 880 (B = 327, T = 16),
+    0 of 11 301 120 (B = 327, T = 9) and 1 of 14 649 600 (B = 545, T = 7) decisions, at most 2e-7 against the 1e-5 the cap
+    presumes.  The rows' time is the
+    fp64 oracle's on the host."""
+    name, first, B, train, hub = case
+    errs, stats, owns = {}, {}, {}
+    flips = _run_config_vs_oracle(name, first, B, train=train, hub=hub, paths={"sparse", "cheb_agg"}, errs=errs,
+                                  stats=stats, owns=owns)
+    worst = max(errs, key=errs.get)
+    own_arm = {k: f"{owns[k]:.1e}" for k in errs if errs[k] > P.TOL}
+    print(f"DTH_WS {_id(case)}: flips {flips} / {stats['mask_elems']}, worst err/scale {errs[worst]:.3e} on {worst}"
+          + (f"; 2 x own arm: {own_arm}" if own_arm else ""))
+    assert flips <= P.FLIP_CAP * stats["mask_elems"], f"{name}: {flips} ReLU decisions of {stats['mask_elems']} differ"
+
+
 # ---------------------------------------------------------------------------------------
 # which path ran: the library's own GEMM log
 # ---------------------------------------------------------------------------------------
-PATH_RUNS = [c for c in BASE_CASES if not c[3]] + SHAPE_CASES + [REFUSED]
+PATH_RUNS = [c for c in BASE_CASES if not c[3]] + SHAPE_CASES + [REFUSED] + list(WS_CASES)
 
 PATH_CHILD = """
 import sys
@@ -115,8 +149,8 @@ def test_dtheta_gemm_only_where_refused():
         assert lines, (name, "the block logged no GEMM")
         shape = "M=%d N=%d K=%d " % (K * (1 if first else C), C, B * N * T)  # dTheta[(k,f), c] over (b, j, t)
         hit = [ln for ln in lines if shape in ln]
-        if (name, first, B) == REFUSED[:3]:
-            assert len(hit) == 1, (name, shape, "the refused order lost its dTheta GEMM", lines)
+        if (name, first, B) == REFUSED[:3] or WS_CASES.get((name, first, B, False, 0)) is False:
+            assert len(hit) == 1, (name, shape, "the refused order / batch lost its dTheta GEMM", lines)
         else:
             assert not hit, (name, shape, "dTheta still runs as a GEMM", hit)
 

@@ -24,8 +24,13 @@ SAVE = false instantiations the build contains, and the bit-identity rows that r
   cheb_agg_fwd_kernel (named there)
 Not reached by a row: gtu_tail_fwd_ct_kernel<32,12,256,*,false> (runs only with the fused GTU
 forward switched off by its knob), the 4-wave tat_fused forms (DSTAGNN_TF_WAVES=4), the fused TAt
-at T = 8 / 16 with NTW > 1, and the (NQ, KM) pairs no geometry of test_gpu_parity.CONFIGS reaches
-— the same kernel text at another loop bound.
+at T = 8 / 16 with NTW > 1, and of the (NQ, KM) pairs an F = 1 or F = C geometry admits
+(tests/test_parity_coverage_cpu.py enumerates them) only cheb_agg_fwd_kernel<12, 5, false> (C = 32 at
+T in 17..24 with K = 4 or 5: no geometry of test_gpu_parity.CONFIGS).  The last rows reach
+cheb_agg_fwd_kernel<8, KM> and <6, KM> and cheb_agg_fwd2_kernel<2, KM> at every KM (C = 16 inner blocks
+at T = 25, 17 | 24 and 8), then <1, 2 | 5 | 8> and <16, 2> of cheb_agg_fwd_kernel and fwd2<4, 5>.  The forms
+only a multi-feature first block admits (cheb_agg_fwd_kernel<4, KM>, <2, 5>, <2, 8>) have their
+bit-identity rows in test_gpu_multifeature (test_no_grad_forward_has_the_training_forward_bits).
 """
 import json
 
@@ -79,7 +84,15 @@ CASES = [
     # cheb_agg_fwd (NQ, KM): (12,8) (12,2) (16,5) (16,8); k4t48 and k8t40 also the split tail
     ("k8t24", False, 2, {}, {"cheb_agg"}, set()), ("k2t24", False, 2, {}, {"cheb_agg"}, set()),
     ("k4t48", False, 2, {}, {"cheb_agg"}, set()), ("k8t40", False, 2, {}, {"cheb_agg"}, set()),
-]
+    # C = 16 inner: cheb_agg_fwd (8, KM) at T = 25 and (6, KM) at T = 17 / 24, cheb_agg_fwd2 (2, KM) at T = 8
+    # (KM = 8: c16k8t8 above), every order template; T >= 20 also the split tail at C = 16
+] + [(n, False, 2, {}, {"cheb_agg"}, {"gtu_fused_fwd"}) for n in (
+    "c16k2t25", "c16t25", "c16k5t25", "c16k8t25", "c16k2t17", "c16t24", "c16k5t17", "c16k8t17", "c16k2t8", "c16t8",
+    "c16k5t8")] + [
+    # cheb_agg_fwd (1, 2) (1, 5) (1, 8): first blocks at T > 16; (16, 2); cheb_agg_fwd2 (4, 5)
+    ("k2t24", True, 1, {}, {"cheb_agg"}, set()), ("k4t48", True, 1, {}, {"cheb_agg"}, set()),
+    ("k8t24", True, 1, {}, {"cheb_agg"}, set()), ("t63", False, 2, {}, {"cheb_agg"}, set()),
+    ("k5t8", False, 2, {}, {"cheb_agg"}, set())]
 
 
 def _case_id(c):

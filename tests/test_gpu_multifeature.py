@@ -14,6 +14,10 @@ Shapes (the smallest that reach each first-block path at F > 1):
   B  C=8 T=9 h=2 d_k=8 D=16 K=2 N=20 B=2 F=4     generic MF tail, unfused TAt, Theta-first, odd T
   C  C=32 T=24 N=16 B=2 F=4                        T = 24: the split path instead of the ct24 template
   D  C=32 T=144 h=2 D=64 K=2 N=12 B=1 F=4          the split long-series path (GAMBIA in small)
+and the rows of MF_DISPATCH below: the aggregate-first templates only a multi-feature first block
+admits, the MF = true tail forms off "generic c32 / cx" and "split c32", and EmbedT's LayerNorm over
+B F T rows past one value a lane (tests/kernel_coverage.py names each row's templates;
+tests/test_parity_coverage_cpu.py holds BLOCK_CASES to what the gates admit).
 """
 import functools
 import os
@@ -47,6 +51,29 @@ def _no_arpack_draws(monkeypatch):
 #        N,  T,  K, h, D,  dk, C,  B
 SHAPES = {"A": (37, 12, 3, 3, 64, 32, 32, 3), "B": (20, 9, 2, 2, 16, 8, 8, 2), "C": (16, 24, 3, 3, 64, 32, 32, 2),
           "D": (12, 144, 2, 2, 64, 32, 32, 1)}
+# name: (shape row, F, what only this row reaches).  N = 40, D = 64, d_k = 32, B = 2 unless the comment says otherwise.
+MF_DISPATCH = {
+    # C = 16, T = 17, F = 8: rows of 8 * 17 = 136 floats on the single-sample kernels, cheb_agg_fwd_kernel<4, KM>
+    # and cheb_agg_sddmm_kernel<4, KM> at every order template (no F = 1 or F = C geometry gives NQ = 4
+    # there); the generic MF tail at C = 16
+    "c16t17k2": ((40, 17, 2, 2, 64, 32, 16, 2), 8), "c16t17k3": ((40, 17, 3, 2, 64, 32, 16, 2), 8),
+    "c16t17k5": ((40, 17, 5, 2, 64, 32, 16, 2), 8), "c16t17k8": ((40, 17, 8, 2, 64, 32, 16, 2), 8),
+    # C = 32, T = 24, F = 4: rows of 96 floats, fwd / sddmm <2, 5> (K = 4 < KM) and <2, 8> (K = 6 < KM)
+    "t24k4": ((40, 24, 4, 2, 64, 32, 32, 2), 4), "t24k6": ((40, 24, 6, 2, 64, 32, 32, 2), 4),
+    # the split MF tail at C = 16 (T >= 20) and at a C off {16, 32} (Theta-first Chebyshev, K-concatenated dx)
+    "c16t24": ((40, 24, 3, 2, 64, 32, 16, 2), 8), "c8t20": ((40, 20, 3, 2, 64, 32, 8, 2), 4),
+    # the two tail gates disagree (F = 1 layout: forward 28 172 B, backward 33 236 B > 32 KB): the generic
+    # MF forward's saved state feeds the split MF backward
+    "c72t19": ((40, 19, 3, 2, 64, 32, 72, 2), 4),
+    # F T = 21: rows no multiple of 4 floats at the minimum T, an odd F, h = 3 (T = 7: the G = 64 VALU TAt)
+    "t7f3": ((40, 7, 3, 3, 64, 32, 32, 2), 3),
+    # EmbedT / TAt LayerNorm over B F T rows of N floats read with element stride F T (h = 2: the fused TAt
+    # refuses, the matrix-core TAt runs B F problems): VPT<2>; the float4 backward (EmbedT) and both float4
+    # directions (TAt); B = 1, N = 1030: the workgroup-per-row kernels with the contribution-form backward
+    "n100": ((100, 12, 3, 2, 64, 32, 32, 2), 4), "n256": ((256, 12, 3, 2, 64, 32, 32, 2), 4),
+    "n1030": ((1030, 12, 3, 2, 64, 32, 32, 1), 4),
+}
+SHAPES.update({k: v[0] for k, v in MF_DISPATCH.items()})
 
 
 def d64(t):
@@ -102,15 +129,22 @@ def hip_relu_masks(blk, x, res, train=False, seed=0):
             (r > 0).permute(0, 2, 1, 3).contiguous().cpu())
 
 
-def expected_paths(shape, F, sparse=True):
-    """(must, must_not): the multi-feature tail always; the rest from the dispatch mirrors."""
+def predicted(shape, F, sparse=True, train=False):
+    """The dispatch mirror's tokens for a multi-feature first block of this shape (res_att = 0)."""
     N, T, K, h, D, dk, C, B = SHAPES[shape]
+    return kc.kernels(N, T, K, F, C, B, sparse=sparse, d_k=dk, h=h, D=D, first=True, res_kind=0, train=train)
+
+
+def expected_paths(shape, F, sparse=True):
+    """(must, must_not): the multi-feature tail always; the rest from the dispatch mirror's tokens."""
+    fam = {f for f, _ in predicted(shape, F, sparse)}
+    assert not fam & {"gtu_fused_fwd", "gtu_fused_bwd", "tat_fused_fwd", "tat_fused_bwd"}, sorted(fam)  # the F = 1 | C names
     must, must_not = {"first_multi"}, {"gtu_fused_fwd", "gtu_fused_bwd"}
-    (must if sparse and kc.cheb_agg_ok(F, C, K, T) else must_not).add("cheb_agg")
-    fused = kc.tat_fused_fwd_ok(N, T, h, dk, dk)
-    (must if fused else must_not).add("tat_fused_fwd")
-    (must if fused and kc.tat_fused_bwd_ok(N, T, h, dk, dk, F, 0) else must_not).add("tat_fused_bwd")
+    (must if fam & {"fwd", "fwd2"} else must_not).add("cheb_agg")
+    (must if "tat_fused_fwd_mf" in fam else must_not).add("tat_fused_fwd")
+    (must if "tat_fused_bwd_mf" in fam else must_not).add("tat_fused_bwd")
     (must if sparse else must_not).add("sparse")
+    assert sparse == bool(fam & {"fwd", "fwd2", "theta_first"})
     return must, must_not
 
 
@@ -130,7 +164,7 @@ def _close(case, key, got, want64, want32, tol=tp.TOL):
         f"{case} {key}: max err {err:.3e} > {tol:.0e} * {scale:.3e} and > 2 x fp32 own {own:.3e}"
 
 
-def _run_block_case(shape, F, sparse=True, train=False):
+def _run_block_case(shape, F, sparse=True, train=False, flip_cap=False):
     from dstagnn_drought_amd.block_fn import block_paths, dropout_masks
     case = f"{shape}/F{F}" + ("" if sparse else "/dense") + ("/train" if train else "")
     p, x, g_out, g_re, cheb, apa, dims = _case(shape, F)
@@ -149,6 +183,7 @@ def _run_block_case(shape, F, sparse=True, train=False):
         dm = (m0.cpu(), m1.cpu().permute(0, 2, 1, 3).contiguous())
     masks = hip_relu_masks(blk, xg, 0, train=train, seed=dseed)
     flips = tp.relu_aware_mask(mfr, p, x, 0, cheb, apa, dims, masks, case, eps=tp.RELU_EPS, drop_masks=dm)
+    elems = sum(int(m.numel()) for m in masks)
     kw = dict(relu_mask=masks[0], tail_masks=masks[1:], train=train)
     r64 = mfr.block_forward_backward({k: d64(v) for k, v in p.items()}, d64(x), 0, [d64(c) for c in cheb], d64(apa),
                                      dims, d64(g_out), d64(g_re), drop_masks=None if dm is None else tuple(map(d64, dm)),
@@ -167,7 +202,10 @@ def _run_block_case(shape, F, sparse=True, train=False):
         assert r64[4][n] is not None and prm.grad is not None, f"{case}: {n} has no gradient"
         assert prm.grad.shape == prm.shape
         _close(case, n, prm.grad, r64[4][n], r32[4][n])
-    print(f"{case}: {flips} ReLU decisions within rounding of 0; fp32 arm so far: {NEEDED_FP32_ARM}")
+    print(f"{case}: {flips} / {elems} ReLU decisions within rounding of 0; fp32 arm so far: {NEEDED_FP32_ARM}")
+    if flip_cap:  # test_gpu_parity.test_pinned_templates_vs_oracle's cap, for the MF_DISPATCH rows
+        print(f"{case}: kernels {sorted(kc.dispatch_only(predicted(shape, F, sparse, train)))}")
+        assert flips <= tp.FLIP_CAP * elems, f"{case}: {flips} ReLU decisions of {elems} differ"
     return out.detach()
 
 
@@ -178,6 +216,27 @@ BLOCK_CASES = [("A", 4), ("A", 2), ("A", 3), ("A", 8), ("B", 4), ("C", 4), ("D",
 def test_block_vs_fp64_helper(shape, F):
     tp._need_gpu()
     _run_block_case(shape, F)
+
+
+# (shape, F, train): every MF_DISPATCH row in eval mode; train where the dropout rides in a tail form no
+# other row runs it in — the (generic forward, split backward) pairing and the split form.
+#
+# FLIP_CAP's condition, checked on the CPU for every row (seed 3): the fp32 restatement against the fp64 one
+# flips 0 of the 38 400 .. 1 186 560 ReLU decisions of each row.
+# Measured on the MI355X (worst err / scale over all tensors; every row 0 flips, none on the fp32 arm):
+#   c16t17 K = 2 6.0e-7  K = 3 6.6e-7  K = 5 7.2e-7  K = 8 9.4e-7    t24k4 7.5e-7  t24k6 6.8e-7
+#   c16t24 6.5e-7  c8t20 7.4e-7  c72t19 8.7e-7 (train 6.5e-7)  C train 8.6e-7  t7f3 2.3e-6
+#   n100 7.2e-7  n256 8.4e-7  n1030 5.7e-7
+MF_DISPATCH_CASES = [(n, MF_DISPATCH[n][1], False) for n in MF_DISPATCH] + [("c72t19", 4, True), ("C", 4, True)]
+
+
+@pytest.mark.parametrize("shape,F,train", MF_DISPATCH_CASES,
+                         ids=[f"{s}-F{f}" + ("-train" if t else "") for s, f, t in MF_DISPATCH_CASES])
+def test_block_dispatch_rows_vs_fp64_helper(shape, F, train):
+    """The rows of MF_DISPATCH at the bound and procedure of test_block_vs_fp64_helper, path bits (from the
+    extended mirror) asserted first, and test_gpu_parity.FLIP_CAP on the decisions that differ."""
+    tp._need_gpu()
+    _run_block_case(shape, F, train=train, flip_cap=True)
 
 
 def test_block_dense_cheb_vs_fp64_helper():
@@ -191,13 +250,15 @@ def test_block_train_mode_vs_fp64_helper():
     _run_block_case("A", 4, train=True)
 
 
-@pytest.mark.parametrize("shape", ["A", "D"])
+@pytest.mark.parametrize("shape", ["A", "D", "c16t17k2", "c16t17k3", "c16t17k5", "c16t17k8", "t24k4", "t24k6"])
 def test_no_grad_forward_has_the_training_forward_bits(shape):
-    """torch.no_grad() takes dstagnn_block_forward_only (lean plan, SAVE = false kernel forms)."""
+    """torch.no_grad() takes dstagnn_block_forward_only (lean plan, SAVE = false kernel forms; the
+    MF_DISPATCH rows: cheb_agg_fwd_kernel<4, KM, false> and <2, 5 | 8, false>, which no other block admits)."""
     tp._need_gpu()
     from dstagnn_drought_amd import _lib, block_fn as bf
-    p, x, *_ = _case(shape, 4)
-    blk = _block(shape, 4, p)
+    F = MF_DISPATCH[shape][1] if shape in MF_DISPATCH else 4
+    p, x, *_ = _case(shape, F)
+    blk = _block(shape, F, p)
     xg = x.cuda().requires_grad_(True)
     out, re_at = blk(xg, 0)
     assert out.grad_fn is not None
