@@ -43,6 +43,11 @@
 //                        of the calibration sums (valid and crossing counts; per level the pinball
 //                        sum, the count of t <= y_q, the sum of y_q): the masked kernel's strip
 //                        plan, kQmChunk columns through LDS at a time; fold_into_table.
+//   skill_kernel<S>      (B, N, P) and the series (type S) -> running (P, 13) and optional (N, 13)
+//                        tables of the sums behind the skill over persistence, the skill over the
+//                        seasonal climatology and the anomaly correlation: the masked kernel's strip
+//                        plan, both baselines read out of the series by each sample's label position
+//                        (a device array); fold_into_table.
 //
 // In all four criterion kernels: 16-byte loads where every pointer of the launch is 16-byte aligned
 // and the tile is whole; scalar loads otherwise (a batch slice y[b:b+bs] of a contiguous tensor is
@@ -592,6 +597,140 @@ __global__ __launch_bounds__(kMetThreads) void metrics_quantile_kernel(int B, in
   fold_into_table(part, P, cols, htable);
 }
 
+// ---- skill against persistence and the seasonal climatology --------------------------------------
+// The 13 sums of include/dstagnn.h's skill section.  Both baselines are read out of the series
+// inside this launch: the persistence value of (b, n) is src[pos[b] - 1, n, F - 1] (src: the series,
+// or its unlimited forward fill), the climatology of (b, n, p) is clim[(pos[b] + p) mod period, n].
+constexpr int kSkCols = DSTAGNN_SKILL_COLS, kSkUnroll = 4;
+
+struct SkillArgs {
+  int B, N, P, F, period;
+  int mask, src_masked, src_nan;
+  float null_val;
+  double src_null;
+  int64_t L;
+  const float *pred, *tg;
+  const void* src;
+  const int64_t* pos;
+  const double* clim;
+  const int32_t* cnt;
+};
+
+// the windows section's rule for a series element (windows.hip win_missing)
+template <typename S>
+__device__ __forceinline__ bool series_missing(S v, S null, int nan_mode) {
+  return nan_mode ? v != v : v == null;
+}
+
+// one entry into a thread's 13 sums: the differences and the squares of columns 1, 2, 6, 7 in fp32,
+// the anomaly products as doubles (exact), every add in fp64; pers / clim: that baseline is defined
+__device__ __forceinline__ void skill_entry(double (&s)[kSkCols], int mask, float null_val, float pv, float tv,
+                                            bool pers, float q, bool clim, float c) {
+  if (!is_valid(mask, null_val, tv)) return;  // selected out: a NaN target never reaches a sum
+  const float em = pv - tv;
+  const float em2 = em * em, ema = fabsf(em);
+  if (pers) {
+    const float ep = q - tv;
+    s[0] += 1.0;
+    s[1] += (double)em2;
+    s[2] += (double)(ep * ep);
+    s[3] += (double)ema;
+    s[4] += (double)fabsf(ep);
+  }
+  if (clim) {
+    const float ec = c - tv, af = pv - c, ao = tv - c;
+    s[5] += 1.0;
+    s[6] += (double)em2;
+    s[7] += (double)(ec * ec);
+    s[8] += (double)ema;
+    s[9] += (double)fabsf(ec);
+    s[10] += (double)af * (double)ao;
+    s[11] += (double)af * (double)af;
+    s[12] += (double)ao * (double)ao;
+  }
+}
+
+// metrics_masked_kernel's strip plan: a workgroup owns 256 / P nodes, thread nl P + p walks the
+// samples of element (n0 + nl, p) with the loads of kSkUnroll samples in flight (each sample's label
+// position first: it is uniform, and the two baseline addresses hang on it).  A sample whose targets
+// would leave the series is skipped unread.  LDS folds over nl (per horizon: the sc1 partial) and
+// over p (per node: straight into the node table, whose rows have one owning workgroup each).
+template <typename S>
+__global__ __launch_bounds__(kMetThreads) void skill_kernel(SkillArgs a, double* __restrict__ part, int* ticket,
+                                                          double* __restrict__ htable, double* __restrict__ ntable) {
+  __shared__ double red[kSkCols][kMetThreads];
+  __shared__ int last;
+  const int t = threadIdx.x;
+  const int P = a.P, N = a.N;
+  const int TN = kMetThreads / P;            // nodes of a whole strip
+  const int n0 = (int)blockIdx.x * TN;       // (the grid is ceil(N / TN): n0 < N)
+  const int tn = N - n0 < TN ? N - n0 : TN;  // nodes of this strip (the last one is partial)
+  double s[kSkCols];
+#pragma unroll
+  for (int c = 0; c < kSkCols; ++c) s[c] = 0.0;
+  if (t < tn * P) {
+    const int nl = t / P, p = t - nl * P, n = n0 + nl;
+    const int pm = p % a.period;  // this thread's phase is (pos mod period + pm) mod period
+    const int64_t step = (int64_t)N * P, NF = (int64_t)N * a.F;
+    const float* __restrict__ pp = a.pred + (int64_t)n0 * P + t;
+    const float* __restrict__ tp = a.tg + (int64_t)n0 * P + t;
+    const S* __restrict__ sp = static_cast<const S*>(a.src) + (int64_t)n * a.F + (a.F - 1);
+    const double* __restrict__ cl = a.clim + n;
+    const int32_t* __restrict__ cn = a.cnt + n;
+    const S snull = (S)a.src_null;
+    for (int b0 = 0; b0 < a.B; b0 += kSkUnroll) {
+      float pv[kSkUnroll], tv[kSkUnroll];
+      double cv[kSkUnroll];
+      S qv[kSkUnroll];
+      int cc[kSkUnroll];
+      bool in[kSkUnroll], prev[kSkUnroll];
+#pragma unroll
+      for (int u = 0; u < kSkUnroll; ++u) {
+        const int b = b0 + u;
+        const int64_t l = b < a.B ? a.pos[b] : -1;
+        in[u] = l >= 0 && l + P <= a.L;  // (uniform; b >= B fails it)
+        prev[u] = in[u] && l >= 1;
+        int64_t ph = in[u] ? l % a.period + pm : 0;  // (both terms below period)
+        if (ph >= a.period) ph -= a.period;
+        pv[u] = in[u] ? pp[b * step] : 0.f;
+        tv[u] = in[u] ? tp[b * step] : 0.f;
+        qv[u] = prev[u] ? sp[(l - 1) * NF] : snull;
+        cv[u] = in[u] ? cl[ph * N] : 0.0;
+        cc[u] = in[u] ? cn[ph * N] : 0;
+      }
+#pragma unroll
+      for (int u = 0; u < kSkUnroll; ++u) {
+        if (!in[u]) continue;
+        const bool pers = prev[u] && !(a.src_masked && series_missing(qv[u], snull, a.src_nan));
+        skill_entry(s, a.mask, a.null_val, pv[u], tv[u], pers, (float)qv[u], cc[u] > 0, (float)cv[u]);
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < kSkCols; ++c) red[c][t] = s[c];
+  __syncthreads();
+  // per node, over p in order: item = nl 13 + c lands on ntable[(n0 + nl) 13 + c].  This workgroup is
+  // the only one that ever touches these rows and launches on a stream are ordered: plain adds.
+  if (ntable != nullptr) {
+    for (int item = t; item < kSkCols * tn; item += kMetThreads) {
+      const int nl = item / kSkCols, c = item - nl * kSkCols;
+      double acc = 0.0;
+      for (int p = 0; p < P; ++p) acc += red[c][nl * P + p];
+      ntable[(int64_t)n0 * kSkCols + item] += acc;
+    }
+  }
+  // per horizon, over nl in order (the idle rows of a partial strip hold zeros); item = c P + p
+  const int items = kSkCols * P;
+  for (int item = t; item < items; item += kMetThreads) {
+    const int c = item / P, p = item - c * P;
+    double acc = 0.0;
+    for (int nl = 0; nl < TN; ++nl) acc += red[c][nl * P + p];
+    st_agent(part + (int64_t)blockIdx.x * items + item, acc);
+  }
+  if (!last_arrival(ticket, (int)gridDim.x, &last)) return;
+  fold_into_table(part, P, kSkCols, htable);
+}
+
 int64_t loss_grid(int64_t n) {
   const int64_t tiles = (n + kLossTile - 1) / kLossTile;
   return tiles < 1 ? 1 : tiles > kLossMaxWg ? kLossMaxWg : tiles;
@@ -871,6 +1010,49 @@ int dstagnn_metrics_accumulate_quantile(int64_t B, int64_t N, int P, const dstag
   if (!ticket) return DSTAGNN_E_ARG;
   hipLaunchKernelGGL(metrics_quantile_kernel, dim3((unsigned)grid), dim3(kMetThreads), 0, st, (int)B, (int)N, P, a,
                      pred, target, static_cast<double*>(scratch), ticket, htable, ntable);
+  DS_CHECK_LAUNCH();
+  return 0;
+}
+
+int64_t dstagnn_skill_scratch_bytes(int64_t B, int64_t N, int P) {
+  return masked_grid(B, N, P) * kSkCols * (int64_t)P * (int64_t)sizeof(double);
+}
+
+int dstagnn_skill_accumulate(int64_t B, int64_t N, int P, const float* pred, const float* target, int mask_mode,
+                             float null_val, int series_f64, const void* pers_src, int64_t L, int64_t F,
+                             int src_masked, double src_null, const int64_t* pos, const double* clim,
+                             const int32_t* cnt, int64_t period, double* htable, double* ntable, void* scratch,
+                             size_t scratch_bytes, dstagnn_stream_t stream) {
+  const std::string w("skill_accumulate");
+  int64_t grid = 0;
+  if (int rc = horizon_arg(w, P, "last")) return rc;
+  if (int rc = strip_arg(w, B, N, P, 1, "B * N * P", &grid)) return rc;
+  const int64_t lim = (1ll << 31) - 1;
+  if (L < 1 || F < 1 || N > lim / L || F > lim / (L * N))
+    return fail(w + ": L and F must be >= 1 and L * N * F below 2^31", DSTAGNN_E_SHAPE);
+  if (period < 1 || period > L || period > lim / N)
+    return fail(w + ": period must be in [1, L] and period * N below 2^31, got " + std::to_string(period),
+                DSTAGNN_E_SHAPE);
+  if (!pred || !target || !pers_src || !pos || !clim || !cnt || !htable || !scratch)
+    return fail(w + ": null pred / target / pers_src / pos / clim / cnt / htable / scratch", DSTAGNN_E_ARG);
+  if (int rc = mask_arg(w, &mask_mode, null_val)) return rc;
+  if (!src_masked && std::isnan(src_null)) return fail(w + ": a NaN src_null needs src_masked = 1", DSTAGNN_E_ARG);
+  if (int rc = scratch_arg(w, scratch_bytes, dstagnn_skill_scratch_bytes(B, N, P), "dstagnn_skill_scratch_bytes(B, N, P)"))
+    return rc;
+  hipStream_t st = (hipStream_t)stream;
+  int* ticket = ticket_arg(w, st);
+  if (!ticket) return DSTAGNN_E_ARG;
+  SkillArgs a{};
+  a.B = (int)B, a.N = (int)N, a.P = P, a.F = (int)F, a.period = (int)period;
+  a.mask = mask_mode, a.null_val = null_val;
+  a.src_masked = src_masked ? 1 : 0, a.src_nan = std::isnan(src_null) ? 1 : 0, a.src_null = src_masked ? src_null : 0.0;
+  a.L = L, a.pred = pred, a.tg = target, a.src = pers_src, a.pos = pos, a.clim = clim, a.cnt = cnt;
+  if (series_f64)
+    hipLaunchKernelGGL(skill_kernel<double>, dim3((unsigned)grid), dim3(kMetThreads), 0, st, a,
+                       static_cast<double*>(scratch), ticket, htable, ntable);
+  else
+    hipLaunchKernelGGL(skill_kernel<float>, dim3((unsigned)grid), dim3(kMetThreads), 0, st, a,
+                       static_cast<double*>(scratch), ticket, htable, ntable);
   DS_CHECK_LAUNCH();
   return 0;
 }

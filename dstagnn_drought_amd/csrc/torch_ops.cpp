@@ -23,6 +23,8 @@
 //   dstagnn::window_stats   the training windows' mean / std from the raw series (prepareData.py:149-161)
 //   dstagnn::window_stats_masked / window_fill_forward / window_gather_masked   the same for a series
 //                           with gaps: statistics of the observed values, forward fill, in-gather imputation
+//   dstagnn::climatology / skill_update   the seasonal climatology table of the training steps, and the
+//                           sums of the skill over persistence / climatology and the anomaly correlation
 //   dstagnn::gemm_f32      the strided f32-MFMA GEMM (tests / tools)
 //   dstagnn::colsum         the fixed-order column-sum reduction (bias / LayerNorm affine grads; tests)
 //   dstagnn::gtu_dw / gtu_dw_plan   the GTU convolution weight / bias gradients through gtu_dw_kernel and
@@ -1253,6 +1255,66 @@ std::tuple<Tensor, Tensor> window_fill_forward(const Tensor& series, double null
   return {filled, counts};
 }
 
+// the seasonal climatology of the target feature over the steps [0, t_end) -> (clim (period, N) fp64,
+// cnt (period, N) int32); masked: the elements equal to null_val (NaN: the NaN ones) are left out
+std::tuple<Tensor, Tensor> climatology(const Tensor& series, int64_t period, int64_t t_end, bool masked,
+                                       double null_val) {
+  const bool f64 = series_f64(series, "climatology");
+  const int64_t L = series.size(0), N = series.size(1), F = series.size(2);
+  TORCH_CHECK(period >= 1 && period <= L, "climatology: period must be in [1, ", L, "], got ", period);
+  c10::DeviceGuard guard(series.device());
+  Tensor clim = at::empty({period, N}, series.options().dtype(at::kDouble));
+  Tensor cnt = at::empty({period, N}, series.options().dtype(at::kInt));
+  check_rc(dstagnn_climatology(f64, series.data_ptr(), L, N, F, period, t_end, masked ? 1 : 0, null_val,
+                               clim.data_ptr<double>(), cnt.data_ptr<int32_t>(), stream_of(series)),
+           "dstagnn_climatology");
+  return {clim, cnt};
+}
+
+// pred, target (..., N, P) taken as (B, N, P), pos (B) int64 label positions, src (L, N, F) the series
+// or its forward fill, clim / cnt (period, N): the 13 skill sums added into the running (P, 13)
+// horizon table and, where given, the running (N, 13) node table; one launch, no host sync
+void skill_update(const Tensor& pred, const Tensor& target, int64_t mask_mode, double null_val, const Tensor& src,
+                  bool src_masked, double src_null, const Tensor& pos, const Tensor& clim, const Tensor& cnt,
+                  Tensor htable, const c10::optional<Tensor>& ntable) {
+  check_loss_pair(pred, target, "skill_update");
+  const bool f64 = series_f64(src, "skill_update");
+  check_dev(pos, at::kLong, "pos");
+  check_dev(clim, at::kDouble, "clim");
+  check_dev(cnt, at::kInt, "cnt");
+  check_dev(htable, at::kDouble, "htable");
+  TORCH_CHECK(pred.dim() >= 2, "skill_update: pred must have a node and a horizon axis");
+  const int64_t P = pred.size(-1), N = pred.size(-2), B = P > 0 && N > 0 ? pred.numel() / (N * P) : 0;
+  const int64_t L = src.size(0), F = src.size(2), period = clim.dim() == 2 ? clim.size(0) : 0;
+  TORCH_CHECK(src.size(1) == N, "skill_update: the series has ", src.size(1), " nodes, pred ", N);
+  TORCH_CHECK(pos.dim() == 1 && pos.numel() == B, "skill_update: pos must hold one label position per sample (", B,
+              "), got ", pos.sizes());
+  TORCH_CHECK(clim.dim() == 2 && clim.size(1) == N && cnt.sizes() == clim.sizes(),
+              "skill_update: clim and cnt must be (period, ", N, "), got ", clim.sizes(), " and ", cnt.sizes());
+  // (a P outside [1, 256] is the library's DSTAGNN_E_SHAPE below)
+  TORCH_CHECK(P < 1 || P > 256 || (htable.dim() == 2 && htable.size(0) == P && htable.size(1) == DSTAGNN_SKILL_COLS),
+              "skill_update: htable must be (", P, ", ", DSTAGNN_SKILL_COLS, "), got ", htable.sizes());
+  const bool nodes = ntable.has_value() && ntable->defined();
+  if (nodes) {
+    check_dev(*ntable, at::kDouble, "ntable");
+    TORCH_CHECK(ntable->dim() == 2 && ntable->size(0) == N && ntable->size(1) == DSTAGNN_SKILL_COLS,
+                "skill_update: ntable must be (", N, ", ", DSTAGNN_SKILL_COLS, "), got ", ntable->sizes());
+  }
+  for (const Tensor* t : {&src, &pos, &clim, &cnt, static_cast<const Tensor*>(&htable)})
+    TORCH_CHECK(t->device() == pred.device(), "skill_update: every tensor must be on pred's device");
+  TORCH_CHECK(!nodes || ntable->device() == pred.device(), "skill_update: ntable on another device");
+  c10::DeviceGuard guard(pred.device());
+  const int Pi = (int)std::min<int64_t>(P, INT32_MAX);
+  const int64_t sb = std::max<int64_t>(dstagnn_skill_scratch_bytes(B, N, Pi), 16);
+  Tensor scratch = at::empty({sb / 8}, pred.options().dtype(at::kDouble));
+  check_rc(dstagnn_skill_accumulate(B, N, Pi, pred.data_ptr<float>(), target.data_ptr<float>(), (int)mask_mode,
+                                    (float)null_val, f64, src.data_ptr(), L, F, src_masked ? 1 : 0, src_null,
+                                    pos.data_ptr<int64_t>(), clim.data_ptr<double>(), cnt.data_ptr<int32_t>(), period,
+                                    htable.data_ptr<double>(), nodes ? ntable->data_ptr<double>() : nullptr,
+                                    scratch.data_ptr<double>(), (size_t)sb, stream_of(pred)),
+           "dstagnn_skill_accumulate");
+}
+
 int64_t window_fill_chunk() { return dstagnn_window_fill_chunk(); }
 int64_t window_fill_cols() { return dstagnn_window_fill_cols(); }
 
@@ -1518,6 +1580,9 @@ TORCH_LIBRARY(dstagnn, m) {
   m.def("window_tile_nodes(int F, int Tin) -> int", window_tile_nodes);
   m.def("window_stats_masked(Tensor series, Tensor w, float null_val) -> (Tensor, Tensor)");
   m.def("window_fill_forward(Tensor series, float null_val, int max_gap) -> (Tensor, Tensor)");
+  m.def("climatology(Tensor series, int period, int t_end, bool masked, float null_val) -> (Tensor, Tensor)");
+  m.def("skill_update(Tensor pred, Tensor target, int mask_mode, float null_val, Tensor src, bool src_masked, "
+        "float src_null, Tensor pos, Tensor clim, Tensor cnt, Tensor(a!) htable, Tensor(b!)? ntable) -> ()");
   m.def("window_fill_chunk() -> int", window_fill_chunk);
   m.def("window_fill_cols() -> int", window_fill_cols);
   m.def("window_gather_masked(Tensor xsrc, Tensor ysrc, Tensor rel, Tensor labels, Tensor idx, Tensor mean, "
@@ -1577,6 +1642,8 @@ TORCH_LIBRARY_IMPL(dstagnn, CUDA, m) {
   m.impl("window_stats_masked", window_stats_masked);
   m.impl("window_fill_forward", window_fill_forward);
   m.impl("window_gather_masked", window_gather_masked);
+  m.impl("climatology", climatology);
+  m.impl("skill_update", skill_update);
   m.impl("stag_prep", stag_prep);
   m.impl("stag_emd_pairs", stag_emd_pairs);
   m.impl("stag_prep_masked", stag_prep_masked);

@@ -52,6 +52,11 @@
 //     longer reach), loads that one value, then walks its chunk forward and stores.  Nothing later
 //     than s is ever read for step s.  Missing / filled counts per feature: LDS integer atomics,
 //     then one global atomic per feature and workgroup (integers: exact in any order).
+//
+// The seasonal baseline of the skill scores (loss.hip skill_kernel):
+//   climatology_kernel<S, MASKED>  clim (period, N) fp64 and cnt (period, N) int32: the mean of the
+//     observed target feature over the training steps of each phase t mod period, one thread per
+//     (phase, node), sequential in t: the same bits on every call.
 #include <cmath>
 
 #include "handoff.hpp"
@@ -340,7 +345,88 @@ __global__ __launch_bounds__(kFillCols) void window_fill_kernel(const S* __restr
 
 int64_t stats_grid(int64_t L) { return L < 1 ? 1 : L > kStatMaxWg ? kStatMaxWg : L; }
 
+// The seasonal climatology of the target feature over the training steps [0, t_end): one thread per
+// (phase, node), n fastest (for a fixed t the lanes of a wave read elements F apart in one row),
+// walking t = phase, phase + period, ... in order with kClimUnroll loads in flight.  Each value is
+// converted to double and added in increasing t; one division.  MASKED: the missing elements are
+// skipped.  A (phase, node) with no observed value: clim = NaN, cnt = 0.
+constexpr int kClimThreads = 256, kClimUnroll = 4;
+
+template <typename S, bool MASKED>
+__global__ __launch_bounds__(kClimThreads) void climatology_kernel(const S* __restrict__ series, int64_t NF, int N,
+                                                                  int F, int period, int64_t t_end, double null_val,
+                                                                  int null_nan, double* __restrict__ clim,
+                                                                  int32_t* __restrict__ cnt) {
+  const int64_t i = (int64_t)blockIdx.x * kClimThreads + threadIdx.x;
+  if (i >= (int64_t)period * N) return;
+  const int phase = (int)(i / N), n = (int)(i - (int64_t)phase * N);
+  const S nullv = MASKED ? (S)null_val : S(0);
+  const S* __restrict__ col = series + (int64_t)n * F + (F - 1);
+  double sum = 0.0;
+  int c = 0;
+  for (int64_t t = phase; t < t_end; t += (int64_t)period * kClimUnroll) {
+    S v[kClimUnroll];
+#pragma unroll
+    for (int u = 0; u < kClimUnroll; ++u) {
+      const int64_t tu = t + (int64_t)u * period;
+      v[u] = tu < t_end ? col[tu * NF] : nullv;
+    }
+#pragma unroll
+    for (int u = 0; u < kClimUnroll; ++u) {
+      const int64_t tu = t + (int64_t)u * period;
+      if (tu < t_end && !(MASKED && win_missing(v[u], nullv, null_nan))) sum += (double)v[u], ++c;
+    }
+  }
+  clim[i] = c > 0 ? sum / (double)c : __builtin_nan("");
+  cnt[i] = c;
+}
+
+template <typename S>
+void launch_climatology(const void* series, int64_t N, int64_t F, int64_t period, int64_t t_end, int masked,
+                        double null_val, double* clim, int32_t* cnt, hipStream_t st) {
+  const dim3 grid((unsigned)((period * N + kClimThreads - 1) / kClimThreads)), block(kClimThreads);
+  const int null_nan = std::isnan(null_val) ? 1 : 0;
+  if (masked)
+    hipLaunchKernelGGL((climatology_kernel<S, true>), grid, block, 0, st, static_cast<const S*>(series), N * F, (int)N,
+                       (int)F, (int)period, t_end, null_val, null_nan, clim, cnt);
+  else
+    hipLaunchKernelGGL((climatology_kernel<S, false>), grid, block, 0, st, static_cast<const S*>(series), N * F, (int)N,
+                       (int)F, (int)period, t_end, 0.0, 0, clim, cnt);
+}
+
 }  // namespace
+
+int dstagnn_climatology(int series_f64, const void* series, int64_t L, int64_t N, int64_t F, int64_t period,
+                        int64_t t_end, int masked, double null_val, double* clim, int32_t* cnt,
+                        dstagnn_stream_t stream) {
+  const int64_t lim = (1ll << 31) - 1;
+  if (L < 1 || N < 1 || F < 1 || N > lim / L || F > lim / (L * N)) {
+    set_last_error("climatology: L, N and F must be >= 1 and L * N * F below 2^31");
+    return DSTAGNN_E_SHAPE;
+  }
+  if (period < 1 || period > L || period > lim / N) {
+    set_last_error("climatology: period must be in [1, L] and period * N below 2^31, got " + std::to_string(period));
+    return DSTAGNN_E_SHAPE;
+  }
+  if (t_end < 1 || t_end > L) {
+    set_last_error("climatology: t_end (the end of the training steps) must be in [1, L], got " +
+                   std::to_string(t_end));
+    return DSTAGNN_E_SHAPE;
+  }
+  if (!series || !clim || !cnt) {
+    set_last_error("climatology: null series / clim / cnt");
+    return DSTAGNN_E_ARG;
+  }
+  if (!masked && std::isnan(null_val)) {
+    set_last_error("climatology: a NaN null_val needs masked = 1");
+    return DSTAGNN_E_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (series_f64) launch_climatology<double>(series, N, F, period, t_end, masked, null_val, clim, cnt, st);
+  else launch_climatology<float>(series, N, F, period, t_end, masked, null_val, clim, cnt, st);
+  DS_CHECK_LAUNCH();
+  return 0;
+}
 
 int dstagnn_window_tile_nodes(int F, int Tin) { return F < 1 || Tin < 1 ? 0 : win_tile_nodes(F, Tin); }
 

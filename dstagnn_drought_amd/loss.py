@@ -14,6 +14,10 @@ With a missing value and / or a node count: the masked (P, 8) and (N, 8) tables 
 ``QuantileLoss`` / ``QuantileMetrics``: the pinball criterion of a (..., P, Q) quantile forecast and
 its calibration scores (coverage, pinball, interval width, crossing rate), on the same kernels' plan.
 
+``BaselineSkill``: the skill of a forecast over persistence and over the seasonal climatology, and
+the anomaly correlation, both baselines read out of a ``WindowedSeries``' raw series inside the
+scoring launch (``skill_kernel``, csrc/windows.hip ``climatology_kernel``).
+
 HIP tensors only: there is no CPU fallback.
 """
 import math
@@ -482,3 +486,153 @@ class QuantileMetrics(_RunningTables):
 
     def _config(self):
         return (self.P, self.quantiles, self._mask[0], repr(self._mask[1]), self.num_nodes)
+
+
+# ---- skill against the forecasts that cost nothing -----------------------------------------------
+SKILL_COLS = 13  # include/dstagnn.h DSTAGNN_SKILL_COLS
+BASELINES = (("persistence", 0), ("climatology", 5))  # (name, first column of its five sums)
+
+
+def check_period(period, L, who="BaselineSkill"):
+    """The climatology period as an int in [1, L]; ValueError for a missing or any other one."""
+    if period is None or isinstance(period, bool):
+        raise ValueError(f"{who}: a climatology period is needed (an int in [1, {int(L)}]), got {period!r}")
+    try:
+        p = int(period)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: the climatology period must be an int in [1, {int(L)}], got {period!r}") from None
+    if p != period or not 1 <= p <= int(L):
+        raise ValueError(f"{who}: the climatology period must be an int in [1, {int(L)}] (the series' length), "
+                         f"got {period!r}")
+    return p
+
+
+class BaselineSkill(_RunningTables):
+    """Running skill of (B, N, P) forecasts over persistence ("the next P steps equal the last
+    observed value") and over the seasonal climatology (the node's mean training value at this
+    phase ``t mod period`` of the cycle), plus the anomaly correlation, per horizon and per node.
+    Both baseline forecasts are read out of the raw series ``series`` (a windows.WindowedSeries)
+    keeps on the device, inside the scoring launch (``skill_kernel``): nothing is materialised and
+    no prediction is copied to the host.
+
+    ``missing_value`` (a number, or NaN for the NaN values: ``mask_of``): a target equal to it
+    reaches no sum, a series element equal to it is not observed.  Persistence then takes the latest
+    observed value at any distance back, from an unlimited forward fill made once
+    (``series.filled`` when that was built with ``fill='ffill'`` and ``max_gap=None`` under the same
+    missing value, else one ``dstagnn::window_fill_forward``), and is undefined where there is none;
+    the climatology (``dstagnn::climatology``, once: the observed training steps
+    ``[0, labels['train'][-1] + P)`` only) is undefined at a (phase, node) never observed in training.
+    The model and a baseline are always summed over the same entries.
+
+    ``update(pred, target, split, idx)``: ``idx`` as ``WindowedSeries.batch`` takes it (a slice, a
+    sequence, or an int64 tensor of positions in ``split``); one launch, no sync.  A position outside
+    the split contributes nothing.  A (..., P, Q) quantile forecast is refused: pass its
+    ``point_index`` column.  ``table`` is (P, 13) fp64 on the device, ``node_table`` (num_nodes, 13)
+    or None (columns: include/dstagnn.h).
+
+    ``scores()``: float64 arrays of shape (P + 1,), the overall value last (from the column sums),
+    NaN wherever a divisor is 0; for b in persistence, climatology: ``count_b``, ``rmse_b`` /
+    ``mae_b`` (the baseline's own), ``model_rmse_b`` / ``model_mae_b`` (the model on that entry
+    set), ``mse_skill_b`` = 1 - sum e_m^2 / sum e_b^2, ``mae_skill_b`` = 1 - sum |e_m| / sum |e_b|;
+    and ``acc``.  ``node_scores()``: the same keys in shape (num_nodes,).  ``climatology()``: the
+    (period, N) fp64 table and its int32 counts as numpy arrays.  ``reset`` / ``merge`` /
+    ``all_reduce`` as ``ForecastMetrics``."""
+
+    def __init__(self, series, period, *, missing_value=None, num_nodes=None):
+        for name in ("L", "N", "F", "P", "labels", "device"):
+            if not hasattr(series, name):
+                raise TypeError(f"BaselineSkill: series must be a windows.WindowedSeries, got {type(series).__name__}")
+        self.period = check_period(period, series.L)
+        self._check_horizon(series.P)
+        if num_nodes is not None and int(num_nodes) != int(series.N):
+            raise ValueError(f"BaselineSkill: num_nodes is {num_nodes!r}, the series has {series.N} nodes")
+        if missing_value is not None:
+            from .windows import check_missing_options
+            check_missing_options(missing_value)  # (a marker float32 does not hold is refused)
+        self.N, self.L = int(series.N), int(series.L)
+        self.t_end = int(series.labels["train"][-1]) + self.P
+        self._init_tables(SKILL_COLS, series.device, missing_value, num_nodes)
+        self.series = series
+        ops = _lib.load()
+        masked = self.missing_value is not None
+        null = self.missing_value if masked else 0.0
+        self._src_mask = (masked, null)
+        self._clim, self._cnt = ops.climatology(series.series, self.period, self.t_end, masked, null)
+        if not masked:
+            self._pers = series.series
+        elif (getattr(series, "filled", None) is not None and series.fill == "ffill" and series.max_gap is None
+              and mask_of(series.missing_value) == self._mask):
+            self._pers = series.filled
+        else:
+            self._pers = ops.window_fill_forward(series.series, null, 0)[0]
+
+    def climatology(self):
+        return self._clim.cpu().numpy(), self._cnt.cpu().numpy()
+
+    def _positions(self, split, idx):
+        """(B,) int64 label positions on the device; -1 for a position outside the split."""
+        labels = getattr(self.series, "_labels", {}).get(split)
+        if labels is None:
+            raise KeyError(f"BaselineSkill: no split {split!r}")
+        S = labels.numel()
+        if isinstance(idx, slice):
+            return labels[idx].contiguous()  # (a view for a unit step: no launch)
+        if not torch.is_tensor(idx):
+            i = np.asarray(idx, dtype=np.int64).reshape(-1)
+            ok = (i >= 0) & (i < S)
+            pos = np.where(ok, self.series.labels[split][np.where(ok, i, 0)], -1)
+            return torch.from_numpy(np.ascontiguousarray(pos, dtype=np.int64)).to(labels.device)
+        if idx.dtype != torch.int64 or idx.dim() != 1:
+            raise ValueError("BaselineSkill.update: idx must be a 1-D int64 tensor")
+        idx = idx.to(labels.device)
+        ok = (idx >= 0) & (idx < S)
+        return torch.where(ok, labels[idx.clamp(0, S - 1)], torch.full_like(idx, -1))
+
+    def update(self, pred, target, split, idx):
+        if pred.dim() == target.dim() + 1 and tuple(pred.shape[:-1]) == tuple(target.shape):
+            raise ValueError(f"BaselineSkill: pred {tuple(pred.shape)} is a (..., P, Q) quantile forecast; pass its "
+                             "point_index column (pred[..., point_index])")
+        if pred.shape != target.shape or pred.dim() != 3 or pred.shape[-1] != self.P or pred.shape[-2] != self.N:
+            raise ValueError(f"BaselineSkill: pred {tuple(pred.shape)} / target {tuple(target.shape)} must be equal "
+                             f"(B, {self.N}, {self.P}) shapes")
+        if not (pred.is_cuda and target.is_cuda):
+            raise RuntimeError(HIP_ONLY)
+        pos = self._positions(split, idx)
+        if pos.numel() != pred.shape[0]:
+            raise ValueError(f"BaselineSkill: {pos.numel()} positions for {pred.shape[0]} samples")
+        if pred.numel() == 0:
+            return
+        _lib.load().skill_update(pred.detach().contiguous(), target.detach().contiguous(), self._mask[0],
+                                 self._mask[1], self._pers, self._src_mask[0], self._src_mask[1], pos, self._clim,
+                                 self._cnt, self.table, self.node_table)
+
+    @staticmethod
+    def scores_of_table(table, overall=True):
+        """The scores of a (K, 13) table of sums (a numpy array), one entry per row and, with
+        ``overall``, one more from the column sums.  NaN wherever a divisor is 0."""
+        tab = np.asarray(table, dtype=np.float64)
+        if tab.ndim != 2 or tab.shape[1] != SKILL_COLS:
+            raise ValueError(f"BaselineSkill: a table of sums is (K, {SKILL_COLS}), got {tab.shape}")
+        if overall:
+            tab = np.concatenate([tab, tab.sum(0, keepdims=True)], 0)
+
+        def over(a, b):
+            out = np.full(a.shape, np.nan)
+            np.divide(a, b, out=out, where=b != 0)
+            return out
+        out = {}
+        for name, c in BASELINES:
+            n = tab[:, c]
+            out[f"count_{name}"] = n.copy()
+            out[f"rmse_{name}"], out[f"mae_{name}"] = np.sqrt(over(tab[:, c + 2], n)), over(tab[:, c + 4], n)
+            out[f"model_rmse_{name}"], out[f"model_mae_{name}"] = np.sqrt(over(tab[:, c + 1], n)), over(tab[:, c + 3], n)
+            out[f"mse_skill_{name}"] = 1.0 - over(tab[:, c + 1], tab[:, c + 2])
+            out[f"mae_skill_{name}"] = 1.0 - over(tab[:, c + 3], tab[:, c + 4])
+        out["acc"] = over(tab[:, 10], np.sqrt(tab[:, 11] * tab[:, 12]))
+        return out
+
+    def scores(self):
+        return self.scores_of_table(self.table.cpu().numpy())
+
+    def _config(self):
+        return (self.P, self.N, self.L, self.period, self.t_end, self._mask[0], repr(self._mask[1]), self.num_nodes)

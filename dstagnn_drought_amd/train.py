@@ -223,7 +223,7 @@ def evaluate_on_test_masked(net, test_loader, test_target_tensor, sw, epoch, *, 
     return (excel_list, metrics.node_scores()) if per_node else excel_list
 
 
-def score_batches(net, x, y, batch_size, missing_value=None, per_node=False, quantiles=None):
+def score_batches(net, x, y, batch_size, missing_value=None, per_node=False, quantiles=None, skill=None):
     """The test-set scores of `net` over (x, y), batched and sharded as eval_batches does it
     (batches of `batch_size` cut with _cut, round-robin over the ranks), accumulated on the device
     and summed over the ranks at the end.  Returns the loss.ForecastMetrics: masked by
@@ -231,9 +231,15 @@ def score_batches(net, x, y, batch_size, missing_value=None, per_node=False, qua
     unmasked (P, 4) object.  x, y: tensors, or the arrays of a windows.WindowedSeries split.
     quantiles (the levels of a quantile model): the ForecastMetrics is fed the ``point_index`` column
     of the (B, N, P, Q) forecasts, and a loss.QuantileMetrics, fed all of them in the same pass, is
-    returned beside it: (ForecastMetrics, QuantileMetrics)."""
+    returned beside it: (ForecastMetrics, QuantileMetrics).
+    skill (a loss.BaselineSkill over the WindowedSeries whose split x and y are): fed in the same
+    pass with the same (b, e) cuts, one more launch per batch (the ``point_index`` column of a
+    quantile model), and all-reduced at the end; the returned value is unchanged.  None: nothing
+    is launched for it."""
     from .loss import ForecastMetrics, QuantileMetrics
     rank, world = _world()
+    if skill is not None and not (_is_streamed(y) and y.owner is skill.series):
+        raise ValueError("score_batches: skill needs the y of a split of the BaselineSkill's own WindowedSeries")
     nodes = y.shape[-2] if per_node else None
     metrics = ForecastMetrics(y.shape[-1], 0.0, x.device, missing_value=missing_value, num_nodes=nodes)
     qm = None
@@ -247,6 +253,10 @@ def score_batches(net, x, y, batch_size, missing_value=None, per_node=False, qua
                 qm.update(out, yb)
                 out = out[..., qm.point_index]
             metrics.update(out, yb)
+            if skill is not None:
+                skill.update(out, yb, y.name, slice(b, b + batch_size))
+    if skill is not None:
+        skill.all_reduce()
     return metrics.all_reduce() if qm is None else (metrics.all_reduce(), qm.all_reduce())
 
 
@@ -599,6 +609,20 @@ def scoring_options(tc):
     return tc.getboolean('test_metrics', fallback=False), tc.getboolean('node_scores', fallback=False)
 
 
+def skill_options(tc, dc=None):
+    """Optional [Training] keys of a configuration (a ConfigParser section): ``baseline_skill`` and
+    ``climatology_period`` -> (bool, int or None).  The period defaults to the [Data] key ``period``
+    (dc: that section) and is None where neither is there.  Absent: (False, ...), today's behaviour."""
+    period = tc.get('climatology_period', None)
+    if period is None and dc is not None:
+        period = dc.get('period', None)
+    try:
+        period = None if period is None or not str(period).strip() else int(str(period).strip())
+    except ValueError:
+        raise ValueError(f"climatology_period / [Data] period must be an int, got {period!r}") from None
+    return tc.getboolean('baseline_skill', fallback=False), period
+
+
 def model_options(tc):
     """Optional [Training] key ``multi_feature`` of a configuration (a ConfigParser section) -> bool.
     True: the first block takes all ``in_channels`` input features (model.make_model's
@@ -765,7 +789,7 @@ def load_best(net, path):
 def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches=None, root='myexperiments',
         log=print, max_grad_norm=None, weight_decay=None, loss=None, missing_value=None, stream_windows=None,
         input_fill=None, input_max_gap=None, test_metrics=None, node_scores=None, multi_feature=None,
-        quantiles=None):
+        quantiles=None, baseline_skill=None, climatology_period=None):
     """Whole script: data, graphs, model, training, best-checkpoint test loss.  The optional
     [Training] keys of training_options() switch clipping / weight decay on; max_grad_norm /
     weight_decay given here override them.  loss / missing_value override the keys of
@@ -798,7 +822,17 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
     loss name other than ``pinball`` beside it is a ValueError, raised before any data is read), and
     with test_metrics the existing scores are taken from the ``point_index`` column (same keys and
     files) while the result gains ``test_quantile_scores`` (and ``test_node_quantile_scores`` with
-    node_scores), written as ``test_quantile_scores.json`` (and ``test_node_quantile_scores.npz``)."""
+    node_scores), written as ``test_quantile_scores.json`` (and ``test_node_quantile_scores.npz``).
+    baseline_skill / climatology_period (None: the [Training] keys of skill_options(); the period
+    defaults to the [Data] key ``period``): in the same scoring pass the test split is also scored
+    against persistence and the seasonal climatology of the training steps (loss.BaselineSkill,
+    masked by the run's missing value; a quantile model's ``point_index`` column).  Implies
+    test_metrics and needs stream_windows (the materialised path keeps no raw series on the
+    device): ValueError otherwise, and for a missing period or one outside [1, L], before any data
+    is read where the configuration already shows it.  Rank 0 logs one line per horizon and one
+    overall (``mse_skill_persistence``, ``mse_skill_climatology``, ``acc``) and writes
+    ``test_skill.json`` (with node_scores also ``test_node_skill.npz``); the result gains
+    ``test_skill`` (and ``test_node_skill``)."""
     config = configparser.ConfigParser()
     config.read(config_path)
     dc, tc = config['Data'], config['Training']
@@ -820,6 +854,18 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
     cfg_scores, cfg_nodes = scoring_options(tc)
     node_scores = cfg_nodes if node_scores is None else bool(node_scores)
     test_metrics = (cfg_scores if test_metrics is None else bool(test_metrics)) or node_scores
+    cfg_skill, cfg_period = skill_options(tc, dc)
+    baseline_skill = cfg_skill if baseline_skill is None else bool(baseline_skill)
+    climatology_period = cfg_period if climatology_period is None else climatology_period
+    if baseline_skill:
+        test_metrics = True
+        if not stream_windows:
+            raise ValueError("baseline_skill needs stream_windows: the materialised path keeps no raw series on "
+                             "the device to read the baselines from")
+        if climatology_period is None or isinstance(climatology_period, bool) or \
+                climatology_period != int(climatology_period) or int(climatology_period) < 1:
+            raise ValueError("baseline_skill needs a climatology period >= 1 ([Training] climatology_period, [Data] "
+                             f"period or climatology_period=), got {climatology_period!r}")
     cfg_fill, cfg_gap = input_options(tc)
     input_fill = cfg_fill if input_fill is None else (None if str(input_fill).lower() == 'none' else input_fill)
     input_max_gap = cfg_gap if input_max_gap is None else input_max_gap
@@ -834,6 +880,9 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
         if input_fill is not None and rank == 0:
             log(f'Input gaps (fill {input_fill}, max_gap {input_max_gap}): missing per feature '
                 f'{ws.missing_count.tolist()}, filled per feature {ws.filled_count.tolist()}')
+        if baseline_skill:  # refused here, before the training it would otherwise follow
+            from .loss import check_period
+            climatology_period = check_period(climatology_period, ws.L, "baseline_skill")
         (train_x, train_y), (val_x, val_y), (test_x, test_y) = ((ws.split(k).x, ws.split(k).y)
                                                                 for k in ('train', 'val', 'test'))
         # the reference's one-batch probe (:59-61): its draws from the global RNG do not depend on the data
@@ -878,18 +927,25 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
     result = {"best_epoch": best_epoch, "best_val": best_val, "test_loss": test_loss, "history": history,
               "params_path": params_path, "net": net}
     if test_metrics:
+        skill = None
+        if baseline_skill:
+            from .loss import BaselineSkill
+            skill = BaselineSkill(ws, climatology_period, missing_value=missing_value,
+                                  num_nodes=ws.N if node_scores else None)
         result.update(_score_test_split(net, test_x, test_y, bs, missing_value, node_scores, params_path, log,
-                                        quantiles))
+                                        quantiles, skill))
     return result
 
 
-def _score_test_split(net, test_x, test_y, bs, missing_value, per_node, params_path, log, quantiles=None):
+def _score_test_split(net, test_x, test_y, bs, missing_value, per_node, params_path, log, quantiles=None, skill=None):
     """run()'s test-set scores: score_batches, rank 0's log lines and files, the result keys.  With
     quantiles the point scores come from the ``point_index`` column and the calibration scores are
-    logged (coverage per level and mean pinball, one line per horizon) and written beside them."""
+    logged (coverage per level and mean pinball, one line per horizon) and written beside them.
+    With skill (a loss.BaselineSkill, fed in the same pass): ``test_skill`` (and ``test_node_skill``),
+    one ``Test skill`` line per horizon and one overall, ``test_skill.json`` (``test_node_skill.npz``)."""
     import json
     rank, _ = _world()
-    metrics, qm = score_batches(net, test_x, test_y, bs, missing_value, per_node, quantiles), None
+    metrics, qm = score_batches(net, test_x, test_y, bs, missing_value, per_node, quantiles, skill), None
     if quantiles is not None:
         metrics, qm = metrics
     excel_list, scores = metrics.compute(), metrics.scores()
@@ -919,6 +975,19 @@ def _score_test_split(net, test_x, test_y, bs, missing_value, per_node, params_p
             if per_node:
                 np.savez(os.path.join(params_path, 'test_node_quantile_scores.npz'),
                          **out["test_node_quantile_scores"])
+    if skill is not None:
+        ss = out["test_skill"] = skill.scores()
+        if per_node:
+            out["test_node_skill"] = skill.node_scores()
+        if rank == 0:
+            for i in range(skill.P + 1):
+                log('Test skill %s: ' % ('overall' if i == skill.P else 'horizon %d' % i)
+                    + ' '.join('%s %.4f' % (k, ss[k][i]) for k in ('mse_skill_persistence', 'mse_skill_climatology',
+                                                                  'acc')))
+            with open(os.path.join(params_path, 'test_skill.json'), 'w') as f:
+                json.dump(dict({k: v.tolist() for k, v in ss.items()}, period=skill.period), f, indent=1)
+            if per_node:
+                np.savez(os.path.join(params_path, 'test_node_skill.npz'), **out["test_node_skill"])
     return out
 
 
@@ -984,6 +1053,13 @@ def arg_parser():
                     help="comma separated quantile levels, e.g. 0.1,0.5,0.9: a quantile head trained with the pinball "
                          "loss; --test-metrics then also reports coverage, pinball, interval width and crossing rate "
                          "(overrides [Training] quantiles)")
+    ap.add_argument("--baseline-skill", action="store_true", default=None,
+                    help="with --stream-windows: also score the test split against persistence and the seasonal "
+                         "climatology (MSE / MAE skill, anomaly correlation; test_skill.json; implies --test-metrics; "
+                         "overrides [Training] baseline_skill)")
+    ap.add_argument("--climatology-period", type=int, default=None,
+                    help="steps of the seasonal cycle of --baseline-skill (overrides [Training] climatology_period; "
+                         "default: [Data] period)")
     return ap
 
 
@@ -1001,7 +1077,7 @@ def main(argv=None):
             weight_decay=a.weight_decay, loss=a.loss, missing_value=a.missing_value,
             stream_windows=a.stream_windows, input_fill=a.input_fill, input_max_gap=a.input_max_gap,
             test_metrics=a.test_metrics, node_scores=a.node_scores, multi_feature=a.multi_feature,
-            quantiles=a.quantiles)
+            quantiles=a.quantiles, baseline_skill=a.baseline_skill, climatology_period=a.climatology_period)
     finally:
         if world > 1:
             dist.destroy_process_group()

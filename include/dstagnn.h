@@ -592,6 +592,64 @@ int dstagnn_window_gather_masked(int series_f64, const void* xsrc, const void* y
                                  float* y, dstagnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Skill against persistence and the seasonal climatology (windows.hip: the climatology table;
+ * loss.hip: the sums).  Both baseline forecasts are read straight out of the raw (L, N, F) series
+ * (type S: fp64 when series_f64, else fp32; the target feature is F - 1) inside the scoring launch:
+ * nothing is materialised.  A series element is missing by the windows section's rule (`masked` /
+ * `src_masked` = 0: nothing is; 1: null_val NaN -> v != v, a number -> v == S(null_val)); an fp32
+ * target is valid by the criterion's rule (mask_mode / null_val, DSTAGNN_MASK_*).
+ *
+ * dstagnn_climatology: clim (period, N) fp64 and cnt (period, N) int32 on the device:
+ * cnt[phi, n] = the observed s[t, n, F-1] over the steps t in [0, t_end) with t mod period == phi
+ * (the phase of the absolute series index), clim[phi, n] = their sum / cnt, each value converted to
+ * double and added in increasing t, one division; cnt == 0 gives clim = NaN (the climatology is
+ * undefined there).  Nothing at or beyond t_end is read.  One launch, one thread per (phi, n), n
+ * fastest.  L, N, F >= 1, L N F < 2^31, period N < 2^31, 1 <= period <= L and 1 <= t_end <= L,
+ * else DSTAGNN_E_SHAPE; a null series / clim / cnt, or a NaN null_val with masked = 0 ->
+ * DSTAGNN_E_ARG.
+ *
+ * dstagnn_skill_accumulate: pred, target (B, N, P) fp32 and pos (B) int64 on the device, pos[b] =
+ * the label position l_b of sample b (its targets are the steps l_b .. l_b + P - 1) -> htable
+ * (P, 13) and, unless NULL, ntable (N, 13) doubles on the device, RUNNING tables the call adds to
+ * (zero them to start).  pers_src (L, N, F) of type S is the series, or its unlimited forward fill
+ * (dstagnn_window_fill_forward, max_gap = 0) when it has gaps: the persistence value of (b, n) is
+ * pers_src[l_b - 1, n, F-1], undefined when l_b - 1 < 0 or when that element is (still) missing.
+ * clim / cnt: dstagnn_climatology's tables; the climatology of (b, n, p) is
+ * clim[(l_b + p) mod period, n], undefined where cnt is 0.  Per entry, with y the prediction, t the
+ * target, q = float(persistence), c = float(climatology), all differences in fp32:
+ * e_m = y - t, e_p = q - t, e_c = c - t, a_f = y - c, a_o = t - c.
+ * Over the entries where t is valid AND persistence is defined:
+ *   0 count   1 sum e_m e_m   2 sum e_p e_p   3 sum |e_m|   4 sum |e_p|
+ * over the entries where t is valid AND the climatology is defined:
+ *   5 count   6 sum e_m e_m   7 sum e_c e_c   8 sum |e_m|   9 sum |e_c|
+ *   10 sum a_f a_o   11 sum a_f^2   12 sum a_o^2
+ * the squares of columns 1, 2, 6, 7 in fp32 (as dstagnn_metrics_accumulate_masked forms e * e),
+ * the products of 10 - 12 as doubles (exact), every add in fp64 in a fixed order, no atomics on
+ * floats: the same bits on every call.  The model and a baseline are summed over the SAME entries.
+ * Entries are selected out, never multiplied by zero: a NaN target under DSTAGNN_MASK_NAN reaches
+ * no sum; a NaN prediction at a counted entry makes the sums NaN.  A sample with l_b < 0 or
+ * l_b + P > L contributes nothing and nothing outside the series is read.
+ * MSE skill over persistence = 1 - [1] / [2], over climatology = 1 - [6] / [7]; MAE skill =
+ * 1 - [3] / [4], 1 - [8] / [9]; anomaly correlation = [10] / sqrt([11] [12]).
+ * One launch of ceil(N / (256 / P)) workgroups, no host synchronisation.  1 <= P <= 256, B, N, L,
+ * F >= 1, B N P, L N F and period N < 2^31, 1 <= period <= L, else DSTAGNN_E_SHAPE; a null pred /
+ * target / pers_src / pos / clim / cnt / htable / scratch, an unknown mask mode, or a NaN src_null
+ * with src_masked = 0 -> DSTAGNN_E_ARG; scratch smaller than dstagnn_skill_scratch_bytes(B, N, P)
+ * (0 for a shape it rejects) -> DSTAGNN_E_SPACE.  All of it is checked before anything touches
+ * the device.
+ * ------------------------------------------------------------------------------------- */
+#define DSTAGNN_SKILL_COLS 13
+int dstagnn_climatology(int series_f64, const void* series, int64_t L, int64_t N, int64_t F, int64_t period,
+                        int64_t t_end, int masked, double null_val, double* clim, int32_t* cnt,
+                        dstagnn_stream_t stream);
+int64_t dstagnn_skill_scratch_bytes(int64_t B, int64_t N, int P);
+int dstagnn_skill_accumulate(int64_t B, int64_t N, int P, const float* pred, const float* target, int mask_mode,
+                             float null_val, int series_f64, const void* pers_src, int64_t L, int64_t F,
+                             int src_masked, double src_null, const int64_t* pos, const double* clim,
+                             const int32_t* cnt, int64_t period, double* htable, double* ntable /* may be NULL */,
+                             void* scratch, size_t scratch_bytes, dstagnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Graph builders (stag.hip).  fp64 throughout, like the reference's numpy/scipy code.
  * ------------------------------------------------------------------------------------- */
 
