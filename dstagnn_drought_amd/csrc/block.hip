@@ -113,56 +113,68 @@ struct SaveBufs {
   float *G, *tco, *r, *mu_c, *rs_c, *u_et, *mu_et, *rs_et;
 };
 
-SaveBufs plan_save(const Dims& m, Arena& a) {
-  SaveBufs s;
-  s.Wqkv = a.take(m.QW * m.N);
-  s.Wqkv_p = m.tfused ? a.take(m.QW * m.NP) : nullptr;
-  s.WfcT = m.tfused_bwd ? a.take(m.HV * m.NP) : nullptr;
-  s.WqT = m.tfused_bwd ? a.take(m.QW * m.NP) : nullptr;
-  for (int g = 0; g < 3; ++g) s.Wgt[g] = m.gfused ? a.take(2 * (int64_t)m.C * m.C * m.ks[g]) : nullptr;
-  s.Wqk = a.take(2 * m.KD * m.D);
-  s.Wp = a.take((int64_t)m.D * m.FT);
-  s.thcat = a.take((int64_t)m.F * m.KC);
-  for (int g = 0; g < 3; ++g) s.Wgf[g] = a.take(2 * (int64_t)m.C * m.C * m.ks[g]);
-  for (int g = 0; g < 3; ++g) s.Wgb[g] = a.take(2 * (int64_t)m.C * m.C * m.ks[g]);
-  s.E = a.take(m.BFT * m.N);
-  s.qkv = a.take(m.BFT * m.QW);
-  s.att = a.take(m.BFT * m.h * m.T);
-  s.ctx = a.take(m.BFT * m.HV);
-  s.u_tat = a.take(m.BFT * m.N);
-  s.mu_tat = a.take(m.BFT);
-  s.rs_tat = a.take(m.BFT);
-  s.O = a.take(m.BFT * m.N);
-  s.u_s = a.take(m.BN * m.D);
-  s.mu_s = a.take(m.BN);
-  s.rs_s = a.take(m.BN);
-  s.Zd = a.take(m.BN * m.D);
-  s.qk = a.take(m.BN * 2 * m.KD);
-  s.P = m.flash ? nullptr : a.take((int64_t)m.B * m.K * m.NN);
-  s.W = m.sparse ? nullptr : a.take((int64_t)m.B * m.K * m.NN);
-  s.lse = m.flash ? a.take((int64_t)m.B * m.K * m.N) : nullptr;
-  s.psupp = m.flash ? a.take((int64_t)m.B * m.K * m.nnz) : nullptr;
-  s.wsupp = m.flash ? a.take((int64_t)m.B * m.K * m.nnz) : nullptr;
-  s.am = m.fsmall ? a.take((int64_t)m.K * m.NN) : nullptr;
-  s.amt = m.fsmall ? a.take((int64_t)m.K * m.NN) : nullptr;
-  s.papa = m.fsmall ? a.take(std::max<int64_t>(1, (int64_t)m.B * m.K * m.apa_nnz)) : nullptr;
-  // (m.dth leaves the xth slot, and m.gfused && m.gbfused the G slot, unwritten: the slots stay so
-  // that dstagnn_block_sizes reports the save size the forward-only workspace bound is stated in)
-  s.xth = a.take(m.BN * m.KCT);
-  s.X = a.take(m.BN * m.CT);
-  for (int g = 0; g < 3; ++g) s.conv[g] = a.take(m.BN * 2 * m.C * std::max(m.Tg[g], 0));
-  s.G = a.take(m.BN * m.C * m.S);
-  s.tco = a.take(m.BN * m.CT);
-  s.r = a.take(m.BN * m.CT);
-  s.mu_c = a.take(m.BN * m.T);
-  s.rs_c = a.take(m.BN * m.T);
-  if (m.first) {
-    s.u_et = a.take(m.BFT * m.N);
-    s.mu_et = a.take(m.BFT);
-    s.rs_et = a.take(m.BFT);
-  } else {
-    s.u_et = s.mu_et = s.rs_et = nullptr;
-  }
+// The one plan of the save arena, for the training pair (train: forward + backward over `save`) and
+// for the forward-only workspace (dstagnn_block_forward_only).  One line per slot:
+//   slot(member, floats, fwd, bwd)   fwd: a LATER FORWARD kernel reads it; bwd: the backward reads it
+// The training plan takes a slot when either holds, the forward-only plan when fwd does; every other
+// member is null: the stage functions pass the nulls on, the launchers pick the kernels'
+// SAVE = false forms (neither the store nor the pointer), Fwd::stage_params skips the re-layout.
+// Who writes and who reads each slot, path by path: DESIGN.md §14.4.
+// Forward-only, one reuse: everything from E to xth is dead once X is written, and in an inner
+// block with the unfused TAt stage X takes E's place (both (B N, C T) floats): E's last reader is
+// the TAt LayerNorm on the caller's stream, X's writer the Chebyshev aggregation, later on that stream.
+SaveBufs plan_bufs(const Dims& m, Arena& a, bool train) {
+  SaveBufs s{};
+  auto slot = [&](float*& p, int64_t floats, bool fwd, bool bwd) {
+    if (fwd || (train && bwd)) p = a.take(floats);
+  };
+  const bool tf = m.tfused, tb = m.tfused_bwd, gf = m.gfused, gb = m.gbfused, e = m.first || !tf;
+  const int64_t BK = (int64_t)m.B * m.K;
+  slot(s.Wqkv, m.QW * m.N, !tf, !tb);
+  slot(s.Wqkv_p, m.QW * m.NP, tf, false);
+  slot(s.WfcT, m.HV * m.NP, false, tb);
+  slot(s.WqT, m.QW * m.NP, false, tb);
+  for (int g = 0; g < 3; ++g) slot(s.Wgt[g], 2 * (int64_t)m.C * m.C * m.ks[g], gf, false);
+  slot(s.Wqk, 2 * m.KD * m.D, true, true);
+  slot(s.Wp, (int64_t)m.D * m.FT, true, true);
+  slot(s.thcat, (int64_t)m.F * m.KC, true, true);
+  for (int g = 0; g < 3; ++g) slot(s.Wgf[g], 2 * (int64_t)m.C * m.C * m.ks[g], !gf, gb);  // (also the fused backward's)
+  for (int g = 0; g < 3; ++g) slot(s.Wgb[g], 2 * (int64_t)m.C * m.C * m.ks[g], false, !gb);
+  slot(s.E, m.BFT * m.N, e, e);  // (fused TAt, inner block: x is read in place, by tat_wqkv_grad too)
+  slot(s.qkv, m.BFT * m.QW, !tf, true);
+  slot(s.att, m.BFT * m.h * m.T, !tf, true);
+  slot(s.ctx, m.BFT * m.HV, !tf, true);
+  slot(s.u_tat, m.BFT * m.N, !tf, true);
+  slot(s.mu_tat, m.BFT, false, true);
+  slot(s.rs_tat, m.BFT, false, true);
+  slot(s.O, m.BFT * m.N, true, true);
+  slot(s.u_s, m.BN * m.D, true, true);
+  slot(s.mu_s, m.BN, false, true);
+  slot(s.rs_s, m.BN, false, true);
+  slot(s.Zd, m.BN * m.D, true, true);
+  slot(s.qk, m.BN * 2 * m.KD, true, true);
+  slot(s.P, BK * m.NN, !m.flash, !m.flash);
+  slot(s.W, BK * m.NN, !m.sparse, !m.sparse);
+  slot(s.lse, BK * m.N, m.flash && !m.fsmall, m.flash);
+  slot(s.psupp, BK * m.nnz, false, m.flash);
+  slot(s.wsupp, BK * m.nnz, m.flash, m.flash);
+  slot(s.am, (int64_t)m.K * m.NN, m.fsmall, m.fsmall);
+  slot(s.amt, (int64_t)m.K * m.NN, false, m.fsmall);
+  slot(s.papa, std::max<int64_t>(1, BK * m.apa_nnz), false, m.fsmall);
+  slot(s.xth, m.BN * m.KCT, !m.agg, !m.dth);  // x Theta (Theta-first) | agg_k (m.dth: they stay in LDS)
+  if (!train && !m.first && !tf) s.X = s.E;
+  else slot(s.X, m.BN * m.CT, true, true);
+  for (int g = 0; g < 3; ++g) slot(s.conv[g], m.BN * 2 * m.C * std::max(m.Tg[g], 0), !gf, true);
+  // (the fused backward recomputes the gates; the unfused forward tail's SAVE form stores G with
+  // tco, mu and rs whichever backward follows)
+  slot(s.G, m.BN * m.C * m.S, false, !gf || !gb);
+  slot(s.tco, m.BN * m.CT, false, true);
+  slot(s.r, m.BN * m.CT, false, true);
+  slot(s.mu_c, m.BN * m.T, false, true);
+  slot(s.rs_c, m.BN * m.T, false, true);
+  slot(s.u_et, m.BFT * m.N, false, m.first);
+  slot(s.mu_et, m.BFT, false, m.first);
+  slot(s.rs_et, m.BFT, false, m.first);
   return s;
 }
 
@@ -218,20 +230,9 @@ Scratch plan_scratch(const Dims& m, Arena& a) {
   return s;
 }
 
-// The forward-only workspace (dstagnn_block_forward_only): the tensors of plan_save that a LATER
-// FORWARD kernel reads, and the two GEMM workspaces (one per stream) — nothing the backward alone
-// reads.  Every other member stays null: the stage functions pass the nulls on and the launchers
-// pick the kernels' SAVE = false forms, which hold neither the store nor the pointer.
-//   parameters   Wqkv (unfused TAt) | Wqkv_p (fused TAt), Wgt (fused GTU) | Wgf (unfused), Wqk, Wp,
-//                thcat, am (small-graph flash)
-//   region A     E (first block, or unfused TAt), qkv / att / ctx / u_tat (unfused TAt), O, u_s, Zd,
-//                qk, P (no flash), W (dense T_k), lse (streamed flash), wsupp (flash), xth (Theta-first)
-//   after A      X, conv[0..2] (unfused GTU)
-// Region A is dead once X is written.  One reuse: in an inner block with the unfused TAt stage, X
-// takes E's place (both (B N, C T) floats): E's last reader is the TAt LayerNorm on the caller's
-// stream, X's writer the Chebyshev aggregation, later on the same stream.
-// The split GTU tail (long series: gates | fcmy GEMM | tail) has two intermediates of its own: G
-// goes through the main GEMM workspace a chunk of nodes at a time (Fwd::stage_tail; that
+// The forward-only workspace: plan_bufs' forward-only plan and the two GEMM workspaces (one per
+// stream).  The split GTU tail (long series: gates | fcmy GEMM | tail) has two intermediates of its
+// own: G goes through the main GEMM workspace a chunk of nodes at a time (Fwd::stage_tail; that
 // workspace is idle from the convolutions on), the fcmy output through the out buffer itself.
 struct WorkBufs {
   SaveBufs s;
@@ -240,36 +241,9 @@ struct WorkBufs {
 
 WorkBufs plan_work(const Dims& m, Arena& a) {
   WorkBufs k{};
-  SaveBufs& s = k.s;
-  s.Wqkv = m.tfused ? nullptr : a.take(m.QW * m.N);
-  s.Wqkv_p = m.tfused ? a.take(m.QW * m.NP) : nullptr;
-  for (int g = 0; g < 3; ++g) s.Wgt[g] = m.gfused ? a.take(2 * (int64_t)m.C * m.C * m.ks[g]) : nullptr;
-  s.Wqk = a.take(2 * m.KD * m.D);
-  s.Wp = a.take((int64_t)m.D * m.FT);
-  s.thcat = a.take((int64_t)m.F * m.KC);
-  for (int g = 0; g < 3; ++g) s.Wgf[g] = m.gfused ? nullptr : a.take(2 * (int64_t)m.C * m.C * m.ks[g]);
-  s.am = m.fsmall ? a.take((int64_t)m.K * m.NN) : nullptr;
+  k.s = plan_bufs(m, a, false);
   k.w.gemm_ws = a.take(kGemmWs);
   k.w.gemm_ws_side = a.take(kGemmWs);
-  if (m.first || !m.tfused) s.E = a.take(m.BFT * m.N);
-  if (!m.tfused) {
-    s.qkv = a.take(m.BFT * m.QW);
-    s.att = a.take(m.BFT * m.h * m.T);
-    s.ctx = a.take(m.BFT * m.HV);
-    s.u_tat = a.take(m.BFT * m.N);
-  }
-  s.O = a.take(m.BFT * m.N);
-  s.u_s = a.take(m.BN * m.D);
-  s.Zd = a.take(m.BN * m.D);
-  s.qk = a.take(m.BN * 2 * m.KD);
-  if (!m.flash) s.P = a.take((int64_t)m.B * m.K * m.NN);
-  if (!m.sparse) s.W = a.take((int64_t)m.B * m.K * m.NN);
-  if (m.flash && !m.fsmall) s.lse = a.take((int64_t)m.B * m.K * m.N);
-  if (m.flash) s.wsupp = a.take((int64_t)m.B * m.K * m.nnz);
-  if (!m.agg) s.xth = a.take(m.BN * m.KCT);
-  s.X = (!m.first && !m.tfused) ? s.E : a.take(m.BN * m.CT);
-  if (!m.gfused)
-    for (int g = 0; g < 3; ++g) s.conv[g] = a.take(m.BN * 2 * m.C * std::max(m.Tg[g], 0));
   return k;
 }
 
@@ -281,7 +255,7 @@ size_t plan_work_size(const Dims& m) {
 
 void plan_sizes(const Dims& m, size_t* save, size_t* scratch) {
   Arena a(nullptr);
-  plan_save(m, a);
+  plan_bufs(m, a, true);
   *save = a.off + 256;
   Arena b(nullptr);
   plan_scratch(m, b);
@@ -558,8 +532,8 @@ struct Fwd {
   bool e_side = false;           // E = x transposed is issued on the side stream (token e_ready)
   SyncTok e_ready;
   ChebFl fl;
-  // forward-only mode (dstagnn_block_forward_only): s and w come from plan_work, so every tensor
-  // only the backward reads is null, and the in-place LayerNorm inputs are not rewritten
+  // forward-only mode (dstagnn_block_forward_only): s and w come from plan_work; the in-place
+  // LayerNorm inputs are not rewritten, and the split GTU tail runs in chunks
   bool lean = false;
   // the TAt stage's first product (launch), and beside it the forward's side work: E (e_side)
   // and x Theta (xth non-null) need only x and the re-laid parameters, so the fork's flag rides
@@ -677,7 +651,7 @@ struct Fwd {
     PrepSeg spare;  // (a segment past the capacity lands here; the call then fails below)
     auto add = [&](int kind, const float* src, float* dst, int64_t n, int p0 = 0, int p1 = 0, int p2 = 0,
                    int64_t off = 0) -> PrepSeg& {
-      if (lean && !dst) return spare;  // forward-only: a re-layout only the backward reads
+      if (!dst) return spare;  // a re-layout nothing on this path reads (plan_bufs)
       full = full || pp.nseg >= kPrepSegsHost;
       PrepSeg& g = full ? spare : pp.seg[pp.nseg++];
       g.kind = kind; g.src = src; g.dst = dst; g.n = n; g.p0 = p0; g.p1 = p1; g.p2 = p2; g.dst_off = off;
@@ -691,7 +665,7 @@ struct Fwd {
       add(8, p.tat_wk, s.Wqkv_p, m.HQ * m.NP, m.N, m.NP, 0, m.HQ * m.NP);
       add(8, p.tat_wv, s.Wqkv_p, m.HV * m.NP, m.N, m.NP, 0, 2 * m.HQ * m.NP);
     }
-    if (m.tfused_bwd && !lean) {  // the fused backward's B operands (zero-padded transposes, kind 9)
+    if (m.tfused_bwd) {  // the fused backward's B operands (zero-padded transposes, kind 9)
       add(9, p.tat_fc, s.WfcT, m.HV * m.NP, m.NP, (int)m.HV, m.NP, 0).p3 = m.N;
       add(9, p.tat_wq, s.WqT, m.NP * m.HQ, (int)m.HQ, m.N, (int)m.QW, 0).p3 = (int)m.HQ;
       add(9, p.tat_wk, s.WqT, m.NP * m.HQ, (int)m.HQ, m.N, (int)m.QW, m.HQ).p3 = (int)m.HQ;
@@ -703,14 +677,14 @@ struct Fwd {
     for (int k = 0; k < m.K; ++k) add(2, p.theta[k], s.thcat, (int64_t)m.F * m.C, m.C, (int)m.KC, k);
     for (int g = 0; g < 3; ++g) {
       const int64_t n = 2 * (int64_t)m.C * m.C * m.ks[g];
-      if (m.gfused) add(3, p.gtu_w[g], s.Wgt[g], n, m.C, m.ks[g]);  // (o, j, c): the fused forward
-      if (!m.gfused || (m.gbfused && !lean)) add(7, p.gtu_w[g], s.Wgf[g], n, m.C, m.ks[g]);  // (j, c, o): also the fused bwd
-      if (!m.gbfused && !lean) add(4, p.gtu_w[g], s.Wgb[g], n, m.C, m.ks[g]);
+      add(3, p.gtu_w[g], s.Wgt[g], n, m.C, m.ks[g]);  // (o, j, c): the fused forward
+      add(7, p.gtu_w[g], s.Wgf[g], n, m.C, m.ks[g]);  // (j, c, o): the unfused forward, the fused backward
+      add(4, p.gtu_w[g], s.Wgb[g], n, m.C, m.ks[g]);  // (j', o, c) flipped: the unfused backward
     }
     if (m.fsmall)  // the dense A_pa o M_k of the small-graph attention kernels (:122)
       for (int k = 0; k < m.K; ++k) {
         add(5, p.mask[k], s.am + (int64_t)k * m.NN, m.NN).src2 = gr.adj_pa;
-        if (!lean) add(6, p.mask[k], s.amt + (int64_t)k * m.NN, m.NN, m.N).src2 = gr.adj_pa;
+        add(6, p.mask[k], s.amt ? s.amt + (int64_t)k * m.NN : nullptr, m.NN, m.N).src2 = gr.adj_pa;
       }
     if (full) {
       set_last_error("param_prep: more parameter re-layouts than kPrepSegsHost");
@@ -759,7 +733,7 @@ struct Fwd {
     ChebIO c;
     c.B = m.B; c.N = m.N; c.F = m.F; c.T = m.T; c.K = m.K; c.C = m.C;
     c.x = x; c.S = s.P; c.mask = p.mask; c.g = &gr; c.sparse = m.sparse; c.thcat = s.thcat;
-    c.P = s.P; c.W = s.W; c.xth = m.dth ? nullptr : s.xth; c.X = s.X;  // m.dth: agg_k stays in LDS (SAVE = false)
+    c.P = s.P; c.W = s.W; c.xth = s.xth; c.X = s.X;  // (null with m.dth: agg_k stays in LDS, SAVE = false)
     c.agg = m.agg;
     if (m.flash) {
       fl = make_fl(m, p, gr, s);
@@ -792,7 +766,7 @@ struct Fwd {
       g.ln_g = p.ln_g; g.ln_b = p.ln_b;
       if (drop_on(d)) { g.drop_p = d.drop_p; g.seed = d.seed; g.drop_off = drop_off(d, 1); }
       // G only for the unfused backward's fcmy weight gradient (the fused one recomputes the gates)
-      g.G = m.gbfused ? nullptr : s.G;
+      g.G = s.G;
       g.tco = s.tco; g.r = s.r; g.mu = s.mu_c; g.rs = s.rs_c; g.out = out;
       return op_gtu_fused_fwd(g, st);
     }
@@ -1104,7 +1078,7 @@ struct Bwd {
       // (One fork after the SDDMM for the side's SpMM, dTheta and mask gradient together
       // measured 0.705 vs 0.703 ms/step, same box: the SpMM then starts later.)
       ChebAg a = make_ag(B, N, K, F, C, m.T, &gr);
-      a.x = x; a.thcat = s.thcat; a.P = s.P; a.agg = m.dth ? nullptr : s.xth; a.g = w.gpre; a.dW = w.dW; a.dx = dx; a.dx_beta = 1.f;
+      a.x = x; a.thcat = s.thcat; a.P = s.P; a.agg = s.xth; a.g = w.gpre; a.dW = w.dW; a.dx = dx; a.dx_beta = 1.f;
       bool adjacent = gd.theta[0] != nullptr;
       for (int k = 1; k < K && adjacent; ++k) adjacent = gd.theta[k] == gd.theta[0] + (int64_t)k * F * C;
       if (m.flash) {
@@ -1593,7 +1567,7 @@ int dstagnn_block_save_offset(const dstagnn_block_dims* d, int which, size_t* of
   if (!offset_bytes || !count || which < 0 || which > 2) return DSTAGNN_E_ARG;
   const Dims m = mkdims(*d);
   Arena a((void*)(uintptr_t)256);  // the forward carves the 256-aligned save buffer the same way
-  SaveBufs s = plan_save(m, a);
+  SaveBufs s = plan_bufs(m, a, true);
   const float* t = which == 0 ? s.X : (which == 1 ? s.tco : s.r);
   *offset_bytes = (size_t)((const char*)t - (char*)(uintptr_t)256);
   *count = (size_t)(m.BN * m.CT);
@@ -1622,7 +1596,7 @@ int dstagnn_block_forward(const dstagnn_block_dims* d, const dstagnn_block_param
   DS_TRY(check_space(m, save_bytes, scratch_bytes));
   DS_TRY(check_graph(m, g));
   Arena a(align256(save)), b(align256(scratch));
-  SaveBufs s = plan_save(m, a);
+  SaveBufs s = plan_bufs(m, a, true);
   Scratch w = plan_scratch(m, b);
   Fwd f{m, *d, *p, *g, x, d->res_mode ? res_att : nullptr, out, re_at, s, w, (hipStream_t)stream};
   return f.run();
@@ -1668,7 +1642,7 @@ int dstagnn_block_backward(const dstagnn_block_dims* d, const dstagnn_block_para
   DS_TRY(check_space(m, save_bytes, scratch_bytes));
   DS_TRY(check_graph(m, g));
   Arena a(align256(save)), b(align256(scratch));
-  SaveBufs s = plan_save(m, a);
+  SaveBufs s = plan_bufs(m, a, true);
   Scratch w = plan_scratch(m, b);
   Bwd bw{m, *d, *p, *g, *grads, x, d_out, d_re_at, d_x, d->res_mode ? d_res_att : nullptr, s, w, (hipStream_t)stream};
   return bw.run();
@@ -1765,7 +1739,7 @@ int dstagnn_block_time_stage(const dstagnn_block_dims* d, const dstagnn_block_pa
   Dims m = mkdims(*d);
   DS_TRY(check_space(m, save_bytes, scratch_bytes));
   Arena a(align256(save)), b(align256(scratch));
-  SaveBufs s = plan_save(m, a);
+  SaveBufs s = plan_bufs(m, a, true);
   Scratch w = plan_scratch(m, b);
   hipStream_t st = (hipStream_t)stream;
   Fwd f{m, *d, *p, *g, x, d->res_mode ? res_att : nullptr, out, re_at, s, w, st};

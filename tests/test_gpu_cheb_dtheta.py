@@ -158,21 +158,24 @@ def test_dtheta_gemm_only_where_refused():
 # ---------------------------------------------------------------------------------------
 # the fold: the same bits every run
 # ---------------------------------------------------------------------------------------
-def _base_block(B, seed=3):
+def _base_block(B, seed=3, first=False, train=False):
     import dstagnn_drought_amd as D
     N, T, K, h, Dm, dk, C = GEOM["dth_base"]
-    ref, p, x, res, cheb, apa, dims, gen = _oracle_case(B, N, T, K, h, Dm, dk, C, False, 1, seed=seed)
-    blk = D.DSTAGNN_block("cpu", C, C, K, C, C, 1, cheb, apa, apa, N, T, Dm, dk, dk, h)
+    ref, p, x, res, cheb, apa, dims, gen = _oracle_case(B, N, T, K, h, Dm, dk, C, first, 0 if first else 1, seed=seed)
+    F = x.shape[2]
+    blk = D.DSTAGNN_block("cpu", F, F, K, C, C, 1, cheb, apa, apa, N, T, Dm, dk, dk, h)
     blk.load_state_dict(p)
     g_out = torch.randn(B, N, C, T, generator=gen).cuda()
-    g_re = torch.randn(B, C, h, T, T, generator=gen).cuda()
-    return blk.cuda().eval(), x.cuda(), res.cuda(), g_out, g_re
+    g_re = torch.randn(B, F, h, T, T, generator=gen).cuda()
+    return blk.cuda().train(train), x.cuda(), res.cuda() if torch.is_tensor(res) else res, g_out, g_re
 
 
 def _fwd_bwd(blk, x, res, g_out, g_re):
     for p in blk.parameters():
         p.grad = None
     xg = x.clone().requires_grad_(True)
+    if blk.training:
+        torch.manual_seed(P.TRAIN_SEED)  # the forward draws its dropout seed from the global generator
     out, re_at = blk(xg, res)
     torch.autograd.backward([out, re_at], [g_out, g_re])
     torch.cuda.synchronize()
@@ -200,16 +203,18 @@ def test_theta_gradients_bit_identical_over_reruns():
 
 
 # ---------------------------------------------------------------------------------------
-# the slots the forward leaves unwritten (agg_k; G with the fused GTU backward)
+# the slots the default path no longer has (agg_k; G with the fused GTU forward and backward)
 # ---------------------------------------------------------------------------------------
-def test_unwritten_save_slots_are_never_read():
-    """The save buffer keeps its agg_k and G slots; with both unwritten, a run whose buffers start
-    as NaN (block_fn._POISON) equals a plain run bit for bit and stays finite."""
+@pytest.mark.parametrize("first,B", [(False, 3), (True, 2)], ids=["inner-B3", "first-B2"])
+def test_dropped_save_slots_are_never_read(first, B):
+    """The save buffer has no agg_k, G, E (inner block) or unused weight re-layout slot on this
+    path: a run whose buffers start as NaN (block_fn._POISON) equals a plain run
+    bit for bit and stays finite."""
     P._need_gpu()
     from dstagnn_drought_amd import block_fn
-    args = _base_block(3)
+    args = _base_block(B, first=first)
     took = block_fn.block_paths(args[0], args[1].clone().requires_grad_(True), args[2])
-    assert {"cheb_agg", "gtu_fused_fwd", "gtu_fused_bwd"} <= took, sorted(took)
+    assert {"cheb_agg", "gtu_fused_fwd", "gtu_fused_bwd", "tat_fused_fwd", "tat_fused_bwd"} <= took, sorted(took)
     saved = block_fn._POISON
     try:
         block_fn._POISON = False
@@ -220,7 +225,7 @@ def test_unwritten_save_slots_are_never_read():
         block_fn._POISON = saved
     assert plain.keys() == poisoned.keys()
     for k in plain:
-        assert torch.isfinite(poisoned[k]).all(), f"{k}: NaN from an unwritten slot"
+        assert torch.isfinite(poisoned[k]).all(), f"{k}: NaN from a slot nothing wrote"
         assert torch.equal(plain[k], poisoned[k]), f"{k}: differs with poisoned buffers"
 
 
