@@ -10,7 +10,8 @@ from .data import load_graphdata_channel1, masked_mape_np, re_normalization, rea
 from .model import (DSTAGNN_block, DSTAGNN_submodule, Embedding, GTU, MultiHeadAttention, ScaledDotProductAttention,
                     SMultiHeadAttention, SScaledDotProductAttention, cheb_conv, cheb_conv_withSAt, make_model,
                     set_direct_grads, set_dropout, set_sample_base)
-from .loss import BaselineSkill, ForecastMetrics, HipLoss, QuantileLoss, QuantileMetrics
+from .loss import (BaselineSkill, EventScores, ForecastMetrics, HipLoss, QuantileLoss, QuantileMetrics,
+                   node_percentile_thresholds)
 from .windows import WindowedSeries
 
 __all__ = ["make_model", "DSTAGNN_block", "DSTAGNN_submodule", "cheb_conv_withSAt", "cheb_conv", "Embedding", "GTU",
@@ -19,7 +20,8 @@ __all__ = ["make_model", "DSTAGNN_block", "DSTAGNN_submodule", "cheb_conv_withSA
            "load_PA", "get_adjacency_matrix2", "load_graphdata_channel1", "read_and_generate_dataset",
            "masked_mape_np", "re_normalization", "set_dropout", "set_direct_grads", "set_sample_base",
            "HipAdam", "clip_grad_norm_", "HipLoss", "ForecastMetrics", "WindowedSeries",
-           "QuantileLoss", "QuantileMetrics", "BaselineSkill"]
+           "QuantileLoss", "QuantileMetrics", "BaselineSkill", "EventScores",
+           "node_percentile_thresholds"]
 
 
 def __getattr__(name):

@@ -48,6 +48,10 @@
 //                        seasonal climatology and the anomaly correlation: the masked kernel's strip
 //                        plan, both baselines read out of the series by each sample's label position
 //                        (a device array); fold_into_table.
+//   events_kernel        (B, N, P) and K thresholds (one set, or one per node) -> running
+//                        (P, 2 + (K + 1)^2) and optional (N, ...) tables of the class contingency counts
+//                        behind the drought event scores: the masked kernel's strip plan, the cells as
+//                        uint32 histograms in dynamic LDS under integer atomic adds; fold_into_table.
 //
 // In all four criterion kernels: 16-byte loads where every pointer of the launch is 16-byte aligned
 // and the tile is whole; scalar loads otherwise (a batch slice y[b:b+bs] of a contiguous tensor is
@@ -731,6 +735,109 @@ __global__ __launch_bounds__(kMetThreads) void skill_kernel(SkillArgs a, double*
   fold_into_table(part, P, kSkCols, htable);
 }
 
+// ---- drought event scores: the class contingency table --------------------------------------------
+// The counts of include/dstagnn.h's events section.  Unlike the sums above, an entry increments ONE
+// cell of the (K + 1) x (K + 1) table and which one is known only at run time: a register array
+// indexed that way would go to scratch, so the cells are uint32 histograms in (dynamic) LDS taking
+// integer atomic adds.  Integer adds commute: the same bits on every launch, and no floating-point
+// atomics here either.  A cell holds at most B N P < 2^31.
+constexpr int kEvMax = DSTAGNN_MAX_EVENT_LEVELS, kEvUnroll = 4, kEvMaxLds = 64 * 1024;
+
+// c(v) = the number of events v is: K fp32 compares (a NaN v is none of them)
+__device__ __forceinline__ int event_class(const float (&th)[kEvMax], int K, int above, float v) {
+  int c = 0;
+#pragma unroll
+  for (int k = 0; k < kEvMax; ++k)
+    if (k < K) c += (above ? v >= th[k] : v <= th[k]) ? 1 : 0;
+  return c;
+}
+
+// one entry: the valid count in a register (n), a NaN prediction into column 1, any other into its
+// cell 2 + co (K + 1) + cf, one LDS atomic add per histogram (hp: this thread's horizon row, hq: its
+// node row)
+__device__ __forceinline__ void event_entry(const float (&th)[kEvMax], int K, int above, int mask, float null_val,
+                                            float pv, float tv, unsigned& n, unsigned* hp, unsigned* hq) {
+  if (!is_valid(mask, null_val, tv)) return;  // selected out: an invalid target reaches no count
+  n += 1u;
+  const int cell = pv != pv ? 1 : 2 + event_class(th, K, above, tv) * (K + 1) + event_class(th, K, above, pv);
+  atomicAdd(hp + cell, 1u);
+  atomicAdd(hq + cell, 1u);
+}
+
+// metrics_masked_kernel's strip plan: a workgroup owns 256 / P nodes, thread nl P + p walks the
+// samples of element (n0 + nl, p) with the loads of kEvUnroll samples in flight; its node's K
+// thresholds sit in registers (the loops over k unrolled to kEvMax under the uniform k < K, so every
+// index is a constant).  The threads of a node whose thresholds are NaN skip the walk.  LDS:
+// hh[P][cols] then hn[TN][cols], zeroed first; after the walk hn goes straight into this workgroup's
+// own node rows and hh, as doubles, is the sc1 partial fold_into_table takes.
+__global__ __launch_bounds__(kMetThreads) void events_kernel(int B, int N, int P, int K, int above,
+                                                            const float* __restrict__ pred,
+                                                            const float* __restrict__ tg, int mask, float null_val,
+                                                            const float* __restrict__ thr, int per_node,
+                                                            double* __restrict__ part, int* ticket,
+                                                            double* __restrict__ htable, double* __restrict__ ntable) {
+  extern __shared__ unsigned ev_hist[];
+  __shared__ int last;
+  const int t = threadIdx.x;
+  const int cols = 2 + (K + 1) * (K + 1);
+  const int TN = kMetThreads / P;            // nodes of a whole strip
+  const int n0 = (int)blockIdx.x * TN;       // (the grid is ceil(N / TN): n0 < N)
+  const int tn = N - n0 < TN ? N - n0 : TN;  // nodes of this strip (the last one is partial)
+  unsigned* hh = ev_hist;
+  unsigned* hn = ev_hist + P * cols;
+  for (int i = t; i < (P + TN) * cols; i += kMetThreads) ev_hist[i] = 0u;
+  __syncthreads();
+  if (t < tn * P) {
+    const int nl = t / P, p = t - nl * P;
+    float th[kEvMax];
+    bool excluded = false;
+#pragma unroll
+    for (int k = 0; k < kEvMax; ++k) {
+      th[k] = k < K ? thr[per_node ? (int64_t)k * N + n0 + nl : k] : 0.f;
+      excluded = excluded || th[k] != th[k];
+    }
+    if (!excluded) {
+      // element (b, n0 + nl, p) sits at b N P + n0 P + t: for a fixed b the strip reads tn P
+      // contiguous floats
+      const int64_t step = (int64_t)N * P;
+      const float* __restrict__ pp = pred + (int64_t)n0 * P + t;
+      const float* __restrict__ tp = tg + (int64_t)n0 * P + t;
+      unsigned* hp = hh + p * cols;
+      unsigned* hq = hn + nl * cols;
+      unsigned n = 0u;
+      int b = 0;
+      for (; b + kEvUnroll <= B; b += kEvUnroll) {  // the loads of kEvUnroll samples in flight together
+        float pv[kEvUnroll], tv[kEvUnroll];
+#pragma unroll
+        for (int u = 0; u < kEvUnroll; ++u) pv[u] = pp[(b + u) * step], tv[u] = tp[(b + u) * step];
+#pragma unroll
+        for (int u = 0; u < kEvUnroll; ++u) event_entry(th, K, above, mask, null_val, pv[u], tv[u], n, hp, hq);
+      }
+      for (; b < B; ++b) event_entry(th, K, above, mask, null_val, pp[b * step], tp[b * step], n, hp, hq);
+      atomicAdd(hp, n);  // column 0: once per thread
+      atomicAdd(hq, n);
+    }
+  }
+  __syncthreads();
+  // per node: item = nl cols + c lands on ntable[(n0 + nl) cols + c].  This workgroup is the only one
+  // that ever touches these rows and launches on a stream are ordered: plain adds.
+  if (ntable != nullptr)
+    for (int item = t; item < tn * cols; item += kMetThreads) ntable[(int64_t)n0 * cols + item] += (double)hn[item];
+  // per horizon: item = c P + p, the layout fold_into_table reads
+  const int items = cols * P;
+  for (int item = t; item < items; item += kMetThreads) {
+    const int c = item / P, p = item - c * P;
+    st_agent(part + (int64_t)blockIdx.x * items + item, (double)hh[p * cols + c]);
+  }
+  if (!last_arrival(ticket, (int)gridDim.x, &last)) return;
+  fold_into_table(part, P, cols, htable);
+}
+
+// the dynamic LDS of events_kernel at (P, K), in bytes
+int64_t events_lds_bytes(int P, int K) {
+  return ((int64_t)P + kMetThreads / P) * (2 + (K + 1) * (K + 1)) * (int64_t)sizeof(unsigned);
+}
+
 int64_t loss_grid(int64_t n) {
   const int64_t tiles = (n + kLossTile - 1) / kLossTile;
   return tiles < 1 ? 1 : tiles > kLossMaxWg ? kLossMaxWg : tiles;
@@ -1053,6 +1160,51 @@ int dstagnn_skill_accumulate(int64_t B, int64_t N, int P, const float* pred, con
   else
     hipLaunchKernelGGL(skill_kernel<float>, dim3((unsigned)grid), dim3(kMetThreads), 0, st, a,
                        static_cast<double*>(scratch), ticket, htable, ntable);
+  DS_CHECK_LAUNCH();
+  return 0;
+}
+
+// 0 for a shape dstagnn_events_accumulate rejects
+int64_t dstagnn_events_scratch_bytes(int64_t B, int64_t N, int P, int K) {
+  if (K < 1 || K > kEvMax) return 0;
+  const int64_t grid = masked_grid(B, N, P);
+  if (grid == 0 || N > ((1ll << 31) - 1) / K || events_lds_bytes(P, K) > kEvMaxLds) return 0;
+  return grid * (2 + (int64_t)(K + 1) * (K + 1)) * P * (int64_t)sizeof(double);
+}
+
+int dstagnn_events_accumulate(int64_t B, int64_t N, int P, int K, int above, const float* pred, const float* target,
+                              int mask_mode, float null_val, const float* thr, int thr_per_node, double* htable,
+                              double* ntable, void* scratch, size_t scratch_bytes, dstagnn_stream_t stream) {
+  const std::string w("events_accumulate");
+  int64_t grid = 0;
+  if (int rc = horizon_arg(w, P, "last")) return rc;
+  if (K < 1 || K > kEvMax)
+    return fail(w + ": K (the number of thresholds) must be in [1, " + std::to_string(kEvMax) + "], got " +
+                    std::to_string(K),
+                DSTAGNN_E_SHAPE);
+  if (int rc = strip_arg(w, B, N, P, 1, "B * N * P", &grid)) return rc;
+  if (N > ((1ll << 31) - 1) / K) return fail(w + ": K * N must be below 2^31", DSTAGNN_E_SHAPE);
+  const int64_t lds = events_lds_bytes(P, K);
+  if (lds > kEvMaxLds)
+    return fail(w + ": the histograms of P = " + std::to_string(P) + ", K = " + std::to_string(K) + " need " +
+                    std::to_string(lds) + " bytes of LDS, more than " + std::to_string(kEvMaxLds),
+                DSTAGNN_E_SHAPE);
+  if (!pred || !target || !thr || !htable || !scratch)
+    return fail(w + ": null pred / target / thr / htable / scratch", DSTAGNN_E_ARG);
+  if (int rc = mask_arg(w, &mask_mode, null_val)) return rc;
+  if (above < 0 || above > 1 || thr_per_node < 0 || thr_per_node > 1)
+    return fail(w + ": above and thr_per_node must be 0 or 1, got " + std::to_string(above) + " and " +
+                    std::to_string(thr_per_node),
+                DSTAGNN_E_ARG);
+  if (int rc = scratch_arg(w, scratch_bytes, dstagnn_events_scratch_bytes(B, N, P, K),
+                           "dstagnn_events_scratch_bytes(B, N, P, K)"))
+    return rc;
+  hipStream_t st = (hipStream_t)stream;
+  int* ticket = ticket_arg(w, st);
+  if (!ticket) return DSTAGNN_E_ARG;
+  hipLaunchKernelGGL(events_kernel, dim3((unsigned)grid), dim3(kMetThreads), (size_t)lds, st, (int)B, (int)N, P, K,
+                     above, pred, target, mask_mode, null_val, thr, thr_per_node, static_cast<double*>(scratch), ticket,
+                     htable, ntable);
   DS_CHECK_LAUNCH();
   return 0;
 }

@@ -25,6 +25,7 @@
 //                           with gaps: statistics of the observed values, forward fill, in-gather imputation
 //   dstagnn::climatology / skill_update   the seasonal climatology table of the training steps, and the
 //                           sums of the skill over persistence / climatology and the anomaly correlation
+//   dstagnn::events_update  the class contingency counts behind the drought event scores
 //   dstagnn::gemm_f32      the strided f32-MFMA GEMM (tests / tools)
 //   dstagnn::colsum         the fixed-order column-sum reduction (bias / LayerNorm affine grads; tests)
 //   dstagnn::gtu_dw / gtu_dw_plan   the GTU convolution weight / bias gradients through gtu_dw_kernel and
@@ -1315,6 +1316,45 @@ void skill_update(const Tensor& pred, const Tensor& target, int64_t mask_mode, d
            "dstagnn_skill_accumulate");
 }
 
+// pred, target (..., N, P) taken as (B, N, P), thr (K) or (K, N) fp32 thresholds, mildest first: the
+// class contingency counts added into the running (P, 2 + (K + 1)^2) horizon table and, where given,
+// the running (N, ...) node table; one launch, no host sync
+void events_update(const Tensor& pred, const Tensor& target, int64_t mask_mode, double null_val, const Tensor& thr,
+                   bool above, Tensor htable, const c10::optional<Tensor>& ntable) {
+  check_loss_pair(pred, target, "events_update");
+  check_dev(thr, at::kFloat, "thr");
+  check_dev(htable, at::kDouble, "htable");
+  TORCH_CHECK(pred.dim() >= 2, "events_update: pred must have a node and a horizon axis");
+  const int64_t P = pred.size(-1), N = pred.size(-2), B = P > 0 && N > 0 ? pred.numel() / (N * P) : 0;
+  TORCH_CHECK(thr.dim() == 1 || (thr.dim() == 2 && thr.size(1) == N), "events_update: thr must be (K) or (K, ", N,
+              "), got ", thr.sizes());
+  const int64_t K = thr.size(0);
+  TORCH_CHECK(K >= 1 && K <= DSTAGNN_MAX_EVENT_LEVELS, "events_update: between 1 and ", DSTAGNN_MAX_EVENT_LEVELS,
+              " thresholds, got ", K);
+  const int64_t cols = 2 + (K + 1) * (K + 1);
+  // (a P outside [1, 256] is the library's DSTAGNN_E_SHAPE below)
+  TORCH_CHECK(P < 1 || P > 256 || (htable.dim() == 2 && htable.size(0) == P && htable.size(1) == cols),
+              "events_update: htable must be (", P, ", ", cols, "), got ", htable.sizes());
+  const bool nodes = ntable.has_value() && ntable->defined();
+  if (nodes) {
+    check_dev(*ntable, at::kDouble, "ntable");
+    TORCH_CHECK(ntable->dim() == 2 && ntable->size(0) == N && ntable->size(1) == cols,
+                "events_update: ntable must be (", N, ", ", cols, "), got ", ntable->sizes());
+  }
+  for (const Tensor* t : {&thr, static_cast<const Tensor*>(&htable)})
+    TORCH_CHECK(t->device() == pred.device(), "events_update: every tensor must be on pred's device");
+  TORCH_CHECK(!nodes || ntable->device() == pred.device(), "events_update: ntable on another device");
+  c10::DeviceGuard guard(pred.device());
+  const int Pi = (int)std::min<int64_t>(P, INT32_MAX);
+  const int64_t sb = std::max<int64_t>(dstagnn_events_scratch_bytes(B, N, Pi, (int)K), 16);
+  Tensor scratch = at::empty({sb / 8}, pred.options().dtype(at::kDouble));
+  check_rc(dstagnn_events_accumulate(B, N, Pi, (int)K, above ? 1 : 0, pred.data_ptr<float>(), target.data_ptr<float>(),
+                                     (int)mask_mode, (float)null_val, thr.data_ptr<float>(), thr.dim() == 2 ? 1 : 0,
+                                     htable.data_ptr<double>(), nodes ? ntable->data_ptr<double>() : nullptr,
+                                     scratch.data_ptr<double>(), (size_t)sb, stream_of(pred)),
+           "dstagnn_events_accumulate");
+}
+
 int64_t window_fill_chunk() { return dstagnn_window_fill_chunk(); }
 int64_t window_fill_cols() { return dstagnn_window_fill_cols(); }
 
@@ -1583,6 +1623,8 @@ TORCH_LIBRARY(dstagnn, m) {
   m.def("climatology(Tensor series, int period, int t_end, bool masked, float null_val) -> (Tensor, Tensor)");
   m.def("skill_update(Tensor pred, Tensor target, int mask_mode, float null_val, Tensor src, bool src_masked, "
         "float src_null, Tensor pos, Tensor clim, Tensor cnt, Tensor(a!) htable, Tensor(b!)? ntable) -> ()");
+  m.def("events_update(Tensor pred, Tensor target, int mask_mode, float null_val, Tensor thr, bool above, "
+        "Tensor(a!) htable, Tensor(b!)? ntable) -> ()");
   m.def("window_fill_chunk() -> int", window_fill_chunk);
   m.def("window_fill_cols() -> int", window_fill_cols);
   m.def("window_gather_masked(Tensor xsrc, Tensor ysrc, Tensor rel, Tensor labels, Tensor idx, Tensor mean, "
@@ -1644,6 +1686,7 @@ TORCH_LIBRARY_IMPL(dstagnn, CUDA, m) {
   m.impl("window_gather_masked", window_gather_masked);
   m.impl("climatology", climatology);
   m.impl("skill_update", skill_update);
+  m.impl("events_update", events_update);
   m.impl("stag_prep", stag_prep);
   m.impl("stag_emd_pairs", stag_emd_pairs);
   m.impl("stag_prep_masked", stag_prep_masked);

@@ -18,6 +18,11 @@ its calibration scores (coverage, pinball, interval width, crossing rate), on th
 the anomaly correlation, both baselines read out of a ``WindowedSeries``' raw series inside the
 scoring launch (``skill_kernel``, csrc/windows.hip ``climatology_kernel``).
 
+``EventScores``: the class contingency tables of a forecast against drought thresholds (fixed, or
+per node from ``node_percentile_thresholds``) and the categorical scores read from them (POD, FAR,
+CSI, frequency bias, Heidke and Gilbert skill, the class confusion matrix), per horizon and per node
+(``events_kernel``).
+
 HIP tensors only: there is no CPU fallback.
 """
 import math
@@ -636,3 +641,235 @@ class BaselineSkill(_RunningTables):
 
     def _config(self):
         return (self.P, self.N, self.L, self.period, self.t_end, self._mask[0], repr(self._mask[1]), self.num_nodes)
+
+
+# ---- drought event scores ------------------------------------------------------------------------
+MAX_EVENT_LEVELS = 7  # include/dstagnn.h DSTAGNN_MAX_EVENT_LEVELS
+DIRECTIONS = ("below", "above")
+_EVENT_MAX_LDS = 64 * 1024  # csrc/loss.hip kEvMaxLds
+
+
+def check_direction(direction, who="EventScores"):
+    """``below`` (event k is v <= thr_k) or ``above`` (v >= thr_k); ValueError otherwise."""
+    if direction not in DIRECTIONS:
+        raise ValueError(f"{who}: direction must be 'below' or 'above', got {direction!r}")
+    return direction
+
+
+def check_thresholds(thresholds, direction="below", who="EventScores"):
+    """The threshold rule (include/dstagnn.h, the events section), checked on the host on the fp32
+    values the kernel compares with.  A sequence, array or tensor of shape (K,) (one set for all
+    nodes) or (K, N) (one column per node), 1 <= K <= 7, mildest first, none infinite.  (K,): no NaN,
+    strictly decreasing for ``below`` / strictly increasing for ``above`` (two thresholds that round
+    to the same float are an error).  (K, N): every column either all NaN (the node is excluded) or
+    free of NaN and non-increasing / non-decreasing (ties are allowed).  Returns a C-contiguous
+    float32 array; a ValueError that names the broken rule otherwise.  No device."""
+    check_direction(direction, who)
+    if torch.is_tensor(thresholds):
+        thresholds = thresholds.detach().cpu().numpy()
+    try:
+        wide = np.asarray(thresholds, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: thresholds must be numbers in a (K,) or (K, N) array, got {thresholds!r}") from None
+    if wide.ndim not in (1, 2) or wide.size == 0:
+        raise ValueError(f"{who}: thresholds must have shape (K,) or (K, N), got {wide.shape}")
+    if not 1 <= wide.shape[0] <= MAX_EVENT_LEVELS:
+        raise ValueError(f"{who}: between 1 and {MAX_EVENT_LEVELS} thresholds, got {wide.shape[0]}")
+    with np.errstate(over="ignore"):
+        thr = np.ascontiguousarray(wide.astype(np.float32))  # what the kernel sees
+    if np.isinf(thr).any():
+        raise ValueError(f"{who}: an infinite threshold (as float32) defines no event class")
+    nan = np.isnan(thr)
+    if thr.ndim == 1:
+        if nan.any():
+            raise ValueError(f"{who}: a (K,) threshold set holds no NaN (only a node's whole column of a (K, N) table "
+                             "may, which excludes the node)")
+    elif (nan.any(0) & ~nan.all(0)).any():
+        n = int(np.flatnonzero(nan.any(0) & ~nan.all(0))[0])
+        raise ValueError(f"{who}: the threshold column of node {n} mixes NaN and numbers (all NaN excludes a node)")
+    d = np.diff(np.where(nan, 0.0, thr.astype(np.float64)), axis=0)
+    if direction == "above":
+        d = -d
+    if thr.ndim == 1 and not (d < 0).all():
+        raise ValueError(f"{who}: (K,) thresholds are listed mildest first: strictly "
+                         f"{'decreasing' if direction == 'below' else 'increasing'} for direction {direction!r} as "
+                         f"float32 (two that round to the same float are an error), got {thr.tolist()}")
+    if thr.ndim == 2 and not (d <= 0).all():
+        n = int(np.flatnonzero((d > 0).any(0))[0])
+        raise ValueError(f"{who}: the threshold column of node {n} must be "
+                         f"{'non-increasing' if direction == 'below' else 'non-decreasing'} (mildest first) for "
+                         f"direction {direction!r}, got {thr[:, n].tolist()}")
+    return thr
+
+
+def check_percentiles(percentiles, direction="below", who="node_percentile_thresholds"):
+    """1 to 7 percentiles strictly inside (0, 100), mildest first: strictly decreasing for ``below``,
+    strictly increasing for ``above``.  Returns a tuple of floats; ValueError otherwise."""
+    check_direction(direction, who)
+    try:
+        pct = [float(v) for v in percentiles]
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: a sequence of percentiles, got {percentiles!r}") from None
+    if not 1 <= len(pct) <= MAX_EVENT_LEVELS:
+        raise ValueError(f"{who}: between 1 and {MAX_EVENT_LEVELS} percentiles, got {len(pct)}")
+    for v in pct:
+        if not 0.0 < v < 100.0:  # (a NaN fails too)
+            raise ValueError(f"{who}: every percentile must be strictly inside (0, 100), got {v!r}")
+    for a, b in zip(pct, pct[1:]):
+        if not (a > b if direction == "below" else a < b):
+            raise ValueError(f"{who}: the percentiles are listed mildest first: strictly "
+                             f"{'decreasing' if direction == 'below' else 'increasing'} for direction {direction!r}, "
+                             f"got {a!r} before {b!r}")
+    return tuple(pct)
+
+
+def node_percentile_thresholds(series, percentiles, *, direction="below", missing_value=None):
+    """(K, N) fp32 thresholds on the series' device for ``EventScores``: per node the
+    ``percentiles[k]``-th percentile (linear interpolation, fp64, ``torch.nanquantile``) of the
+    observed target-feature values of ``series`` (a windows.WindowedSeries) over the training steps
+    ``[0, labels['train'][-1] + P)``, ``BaselineSkill``'s ``t_end``: nothing of validation or test
+    enters.  ``missing_value`` (a number, or NaN) marks the elements that are not observed, by the
+    series' own dtype; a node with no observed training value gets an all-NaN column, which excludes
+    it.  ``percentiles``: ``check_percentiles`` under ``direction``.  An init-time torch call over
+    L N values: no kernel of its own."""
+    pct = check_percentiles(percentiles, direction)
+    for name in ("series", "P", "labels"):
+        if not hasattr(series, name):
+            raise TypeError(f"node_percentile_thresholds: series must be a windows.WindowedSeries, got "
+                            f"{type(series).__name__}")
+    if missing_value is not None:
+        from .windows import check_missing_options
+        check_missing_options(missing_value)  # (a marker float32 does not hold is refused)
+    t_end = int(series.labels["train"][-1]) + int(series.P)
+    raw = series.series[:t_end, :, -1]
+    v = raw.to(torch.float64)
+    if missing_value is not None and not math.isnan(float(missing_value)):
+        v = torch.where(raw == float(missing_value), torch.full_like(v, float("nan")), v)
+    q = torch.tensor(pct, dtype=torch.float64, device=v.device) / 100.0
+    return torch.nanquantile(v, q, dim=0).to(torch.float32).contiguous()
+
+
+class EventScores(_RunningTables):
+    """Running class contingency tables of (B, N, P) forecasts against K thresholds on the index,
+    per horizon and per node, and the categorical scores drought verification reads from them.
+    ``update(pred, target)`` is one launch of ``events_kernel`` and no sync; no prediction is copied
+    to the host.
+
+    ``thresholds`` (``check_thresholds``): (K,) for all nodes or (K, N) per node (that form fixes
+    ``num_nodes`` at N; ``node_percentile_thresholds`` makes one), 1 <= K <= 7, mildest first, in the
+    units of the raw targets.  ``direction``: ``below`` (event k is v <= thr_k, e.g. SPI -1, -1.5, -2)
+    or ``above`` (v >= thr_k); every compare in fp32, a value equal to the threshold is an event.  The
+    class of a value is the number of its events, 0 .. K.  ``missing_value`` (a number, or NaN:
+    ``mask_of``): a target equal to it reaches no count.  A node whose column is all NaN is excluded
+    (``excluded``).
+
+    ``table`` is (P, 2 + (K + 1)^2) fp64 on the device, ``node_table`` (num_nodes, ...) or None, all
+    integers: column 0 the entries with a valid target on a node that is not excluded, 1 those among
+    them whose prediction is NaN (they reach no cell), 2 + co (K + 1) + cf the entries of observed
+    class co and forecast class cf.
+
+    ``scores()``: float64 arrays with one entry per horizon and a last, overall one from the column
+    sums, NaN wherever a divisor is 0.  ``count``, ``nan_pred`` (P + 1,); ``confusion``
+    (P + 1, K + 1, K + 1); ``observed_freq``, ``forecast_freq`` (P + 1, K + 1).  Per threshold k,
+    (P + 1, K), from a = sum over co > k, cf > k (hits), b = co <= k, cf > k (false alarms), c = co > k,
+    cf <= k (misses), d the rest, n = a + b + c + d: ``hits``, ``false_alarms``, ``misses``,
+    ``correct_negatives``, ``base_rate`` (a + c) / n, ``pod`` a / (a + c), ``far`` b / (a + b), ``pofd``
+    b / (b + d), ``csi`` a / (a + b + c), ``freq_bias`` (a + b) / (a + c), ``accuracy`` (a + d) / n,
+    ``ets`` (a - a_r) / (a + b + c - a_r) with a_r = (a + b)(a + c) / n, ``hss`` 2 (a d - b c) /
+    ((a + c)(c + d) + (a + b)(b + d)).  Multi-category, (P + 1,): ``class_accuracy`` and
+    ``hss_multi``.  ``node_scores()``: the same keys per node, without the overall entry.
+    ``reset`` / ``merge`` / ``all_reduce`` as ``ForecastMetrics``; ``merge`` refuses another
+    definition (thresholds, direction, mask)."""
+
+    def __init__(self, num_for_predict, thresholds, *, direction="below", missing_value=None, num_nodes=None,
+                 device=None):
+        self._check_horizon(num_for_predict)
+        self.direction = check_direction(direction)
+        thr = check_thresholds(thresholds, direction)
+        self.K = int(thr.shape[0])
+        if thr.ndim == 2:
+            if num_nodes is not None and int(num_nodes) != thr.shape[1]:
+                raise ValueError(f"EventScores: num_nodes is {num_nodes!r}, the thresholds are per node for "
+                                 f"{thr.shape[1]} nodes")
+            num_nodes = int(thr.shape[1])
+        if num_nodes is not None and int(num_nodes) < 1:  # (judged before the device is)
+            raise ValueError(f"EventScores: num_nodes must be >= 1, got {num_nodes!r}")
+        cols =2 + (self.K + 1) ** 2
+        if (self.P + 256 // self.P) * cols * 4 > _EVENT_MAX_LDS:
+            raise ValueError(f"EventScores: K = {self.K} thresholds with num_for_predict = {self.P} need more than "
+                             f"{_EVENT_MAX_LDS} bytes of LDS for the histograms (K = 7 takes 2 <= P <= 247)")
+        if missing_value is not None:
+            from .windows import check_missing_options
+            check_missing_options(missing_value)  # (a marker float32 does not hold is refused)
+        self._thr_host = thr
+        self._init_tables(cols, device, missing_value, num_nodes)
+        self._thr = torch.from_numpy(thr).to(self.table.device)
+
+    @property
+    def thresholds(self):
+        return self._thr_host.copy()
+
+    @property
+    def excluded(self):
+        return None if self._thr_host.ndim == 1 else np.isnan(self._thr_host).all(0)
+
+    def update(self, pred, target):
+        if pred.dim() == target.dim() + 1 and tuple(pred.shape[:-1]) == tuple(target.shape):
+            raise ValueError(f"EventScores: pred {tuple(pred.shape)} is a (..., P, Q) quantile forecast; pass its "
+                             "point_index column (pred[..., point_index])")
+        if pred.shape != target.shape or pred.dim() < 2 or pred.shape[-1] != self.P:
+            raise ValueError(f"EventScores: pred {tuple(pred.shape)} / target {tuple(target.shape)} must be "
+                             f"equal (..., N, {self.P}) shapes")
+        self._check_nodes(pred, -2)
+        if not (pred.is_cuda and target.is_cuda):
+            raise RuntimeError(HIP_ONLY)
+        if pred.numel() == 0:
+            return
+        _lib.load().events_update(pred.detach().contiguous(), target.detach().contiguous(), self._mask[0],
+                                  self._mask[1], self._thr, self.direction == "above", self.table, self.node_table)
+
+    @staticmethod
+    def scores_of_table(table, overall=True):
+        """The scores of a (R, 2 + (K + 1)^2) table of counts (a numpy array), one entry per row and,
+        with ``overall``, one more from the column sums.  NaN wherever a divisor is 0."""
+        tab = np.asarray(table, dtype=np.float64)
+        K1 = math.isqrt(tab.shape[1] - 2) if tab.ndim == 2 and tab.shape[1] >= 6 else 0
+        if not 2 <= K1 <= MAX_EVENT_LEVELS + 1 or K1 * K1 != tab.shape[1] - 2:
+            raise ValueError(f"EventScores: a table of counts is (R, 2 + (K + 1)^2) with 1 <= K <= "
+                             f"{MAX_EVENT_LEVELS}, got {tab.shape}")
+        if overall:
+            tab = np.concatenate([tab, tab.sum(0, keepdims=True)], 0)
+        R, K = tab.shape[0], K1 - 1
+        M = tab[:, 2:].reshape(R, K1, K1)
+
+        def over(a, b):
+            a, b = np.broadcast_arrays(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64))
+            out = np.full(a.shape, np.nan)
+            np.divide(a, b, out=out, where=(b != 0) & ~np.isnan(b))
+            return out
+        n = M.sum((1, 2))
+        out = {"count": tab[:, 0].copy(), "nan_pred": tab[:, 1].copy(), "confusion": M.copy(),
+               "observed_freq": over(M.sum(2), n[:, None]), "forecast_freq": over(M.sum(1), n[:, None])}
+        a = np.stack([M[:, k + 1:, k + 1:].sum((1, 2)) for k in range(K)], 1)
+        b = np.stack([M[:, :k + 1, k + 1:].sum((1, 2)) for k in range(K)], 1)
+        c = np.stack([M[:, k + 1:, :k + 1].sum((1, 2)) for k in range(K)], 1)
+        d = np.stack([M[:, :k + 1, :k + 1].sum((1, 2)) for k in range(K)], 1)
+        n2 = a + b + c + d
+        a_r = over((a + b) * (a + c), n2)  # NaN at n = 0: so is ets
+        out.update(hits=a, false_alarms=b, misses=c, correct_negatives=d, base_rate=over(a + c, n2),
+                   pod=over(a, a + c), far=over(b, a + b), pofd=over(b, b + d), csi=over(a, a + b + c),
+                   freq_bias=over(a + b, a + c), accuracy=over(a + d, n2), ets=over(a - a_r, a + b + c - a_r),
+                   hss=over(2.0 * (a * d - b * c), (a + c) * (c + d) + (a + b) * (b + d)))
+        p = over(M, n[:, None, None])
+        agree = np.trace(p, axis1=1, axis2=2)
+        chance = (p.sum(2) * p.sum(1)).sum(1)
+        out["class_accuracy"] = over(np.trace(M, axis1=1, axis2=2), n)
+        out["hss_multi"] = over(agree - chance, 1.0 - chance)
+        return out
+
+    def scores(self):
+        return self.scores_of_table(self.table.cpu().numpy())
+
+    def _config(self):
+        return (self.P, self.K, self.direction, self._thr_host.shape, self._thr_host.tobytes(), self._mask[0],
+                repr(self._mask[1]), self.num_nodes)

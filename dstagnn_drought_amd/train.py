@@ -223,7 +223,7 @@ def evaluate_on_test_masked(net, test_loader, test_target_tensor, sw, epoch, *, 
     return (excel_list, metrics.node_scores()) if per_node else excel_list
 
 
-def score_batches(net, x, y, batch_size, missing_value=None, per_node=False, quantiles=None, skill=None):
+def score_batches(net, x, y, batch_size, missing_value=None, per_node=False, quantiles=None, skill=None, events=None):
     """The test-set scores of `net` over (x, y), batched and sharded as eval_batches does it
     (batches of `batch_size` cut with _cut, round-robin over the ranks), accumulated on the device
     and summed over the ranks at the end.  Returns the loss.ForecastMetrics: masked by
@@ -235,7 +235,10 @@ def score_batches(net, x, y, batch_size, missing_value=None, per_node=False, qua
     skill (a loss.BaselineSkill over the WindowedSeries whose split x and y are): fed in the same
     pass with the same (b, e) cuts, one more launch per batch (the ``point_index`` column of a
     quantile model), and all-reduced at the end; the returned value is unchanged.  None: nothing
-    is launched for it."""
+    is launched for it.
+    events (a loss.EventScores): fed the same way (the same cuts, one more launch per batch, the
+    ``point_index`` column of a quantile model, all-reduced at the end); works on tensors and on a
+    streamed split alike.  None: nothing is launched for it and the returned value is unchanged."""
     from .loss import ForecastMetrics, QuantileMetrics
     rank, world = _world()
     if skill is not None and not (_is_streamed(y) and y.owner is skill.series):
@@ -255,8 +258,12 @@ def score_batches(net, x, y, batch_size, missing_value=None, per_node=False, qua
             metrics.update(out, yb)
             if skill is not None:
                 skill.update(out, yb, y.name, slice(b, b + batch_size))
+            if events is not None:
+                events.update(out, yb)
     if skill is not None:
         skill.all_reduce()
+    if events is not None:
+        events.all_reduce()
     return metrics.all_reduce() if qm is None else (metrics.all_reduce(), qm.all_reduce())
 
 
@@ -623,6 +630,51 @@ def skill_options(tc, dc=None):
     return tc.getboolean('baseline_skill', fallback=False), period
 
 
+def parse_event_levels(text, what="event_thresholds"):
+    """``"-1.0, -1.5, -2.0"`` (or a sequence of numbers) -> (-1.0, -1.5, -2.0); ValueError for
+    anything that is not a non-empty list of numbers.  The order and range rules are loss.py's
+    (check_thresholds / check_percentiles)."""
+    try:
+        parts = str(text).replace(';', ',').split(',') if isinstance(text, str) else list(text)
+        levels = tuple(float(v) for v in parts if not isinstance(v, str) or v.strip())
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: a comma separated list of numbers, got {text!r}") from None
+    if not levels:
+        raise ValueError(f"{what}: a comma separated list of numbers, got {text!r}")
+    return levels
+
+
+def event_options(tc):
+    """Optional [Training] keys of a configuration (a ConfigParser section) for the drought event
+    scores: ``event_thresholds`` (fixed thresholds in the units of the targets, e.g. ``-1.0, -1.5,
+    -2.0``), ``event_percentiles`` (per-node percentiles of the training steps, e.g. ``20, 10, 5``)
+    and ``event_direction`` (``below`` | ``above``) -> (tuple or None, tuple or None, str), each
+    list checked by loss.check_thresholds / loss.check_percentiles under the direction.  Both
+    threshold keys together is a ValueError.  Absent: (None, None, 'below'), today's behaviour."""
+    return resolve_events(*_event_keys(tc))
+
+
+def _event_keys(tc):
+    """The three keys as written (None where absent; the direction lower-cased, 'below' by default)."""
+    return (tc.get('event_thresholds', None), tc.get('event_percentiles', None),
+            tc.get('event_direction', 'below').strip().lower())
+
+
+def resolve_events(thresholds, percentiles, direction):
+    """The three event options, from the keys, the keywords or the flags, checked on the host."""
+    from .loss import check_direction, check_percentiles, check_thresholds
+    check_direction(direction, "event_direction")
+    if thresholds is not None and percentiles is not None:
+        raise ValueError("event_thresholds and event_percentiles are two ways to define the same classes: give one")
+    if thresholds is not None:
+        thresholds = parse_event_levels(thresholds, "event_thresholds")
+        check_thresholds(thresholds, direction, "event_thresholds")
+    if percentiles is not None:
+        percentiles = check_percentiles(parse_event_levels(percentiles, "event_percentiles"), direction,
+                                        "event_percentiles")
+    return thresholds, percentiles, direction
+
+
 def model_options(tc):
     """Optional [Training] key ``multi_feature`` of a configuration (a ConfigParser section) -> bool.
     True: the first block takes all ``in_channels`` input features (model.make_model's
@@ -789,7 +841,8 @@ def load_best(net, path):
 def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches=None, root='myexperiments',
         log=print, max_grad_norm=None, weight_decay=None, loss=None, missing_value=None, stream_windows=None,
         input_fill=None, input_max_gap=None, test_metrics=None, node_scores=None, multi_feature=None,
-        quantiles=None, baseline_skill=None, climatology_period=None):
+        quantiles=None, baseline_skill=None, climatology_period=None, event_thresholds=None, event_percentiles=None,
+        event_direction=None):
     """Whole script: data, graphs, model, training, best-checkpoint test loss.  The optional
     [Training] keys of training_options() switch clipping / weight decay on; max_grad_norm /
     weight_decay given here override them.  loss / missing_value override the keys of
@@ -832,7 +885,18 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
     is read where the configuration already shows it.  Rank 0 logs one line per horizon and one
     overall (``mse_skill_persistence``, ``mse_skill_climatology``, ``acc``) and writes
     ``test_skill.json`` (with node_scores also ``test_node_skill.npz``); the result gains
-    ``test_skill`` (and ``test_node_skill``)."""
+    ``test_skill`` (and ``test_node_skill``).
+    event_thresholds / event_percentiles / event_direction (None: the [Training] keys of
+    event_options()): in the same scoring pass the test split is also scored as a drought event
+    forecast (loss.EventScores, masked by the run's missing value; a quantile model's ``point_index``
+    column): fixed thresholds in the units of the targets, or per-node percentiles of the training
+    steps (loss.node_percentile_thresholds).  A threshold keyword replaces both threshold keys;
+    giving both is a ValueError.  Either implies test_metrics; the percentiles need stream_windows
+    (the materialised path keeps no raw series): ValueError before any data is read.  Rank 0 logs
+    one ``Test events`` line per horizon and one overall (pod / far / csi / hss per threshold and
+    ``hss_multi``) and the number of excluded nodes, and writes ``test_event_scores.json`` (with
+    node_scores also ``test_node_event_scores.npz``); the result gains ``test_event_scores`` (and
+    ``test_node_event_scores``)."""
     config = configparser.ConfigParser()
     config.read(config_path)
     dc, tc = config['Data'], config['Training']
@@ -866,6 +930,18 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
                 climatology_period != int(climatology_period) or int(climatology_period) < 1:
             raise ValueError("baseline_skill needs a climatology period >= 1 ([Training] climatology_period, [Data] "
                              f"period or climatology_period=), got {climatology_period!r}")
+    cfg_thr, cfg_pct, cfg_dir = _event_keys(tc)  # (checked below, under the direction that holds)
+    if event_thresholds is not None or event_percentiles is not None:
+        cfg_thr = cfg_pct = None  # a threshold keyword replaces the keys' definition
+    event_thresholds, event_percentiles, event_direction = resolve_events(
+        cfg_thr if event_thresholds is None else event_thresholds,
+        cfg_pct if event_percentiles is None else event_percentiles,
+        cfg_dir if event_direction is None else str(event_direction).strip().lower())
+    if event_thresholds is not None or event_percentiles is not None:
+        test_metrics = True
+        if event_percentiles is not None and not stream_windows:
+            raise ValueError("event_percentiles needs stream_windows: the materialised path keeps no raw series on "
+                             "the device to take the percentiles of (fixed event_thresholds work on both paths)")
     cfg_fill, cfg_gap = input_options(tc)
     input_fill = cfg_fill if input_fill is None else (None if str(input_fill).lower() == 'none' else input_fill)
     input_max_gap = cfg_gap if input_max_gap is None else input_max_gap
@@ -932,20 +1008,33 @@ def run(config_path, *, epochs=None, double_step=True, dropout=None, max_batches
             from .loss import BaselineSkill
             skill = BaselineSkill(ws, climatology_period, missing_value=missing_value,
                                   num_nodes=ws.N if node_scores else None)
+        events = None
+        if event_thresholds is not None or event_percentiles is not None:
+            from .loss import EventScores, node_percentile_thresholds
+            thr = event_thresholds if event_percentiles is None else node_percentile_thresholds(
+                ws, event_percentiles, direction=event_direction, missing_value=missing_value)
+            events = EventScores(test_y.shape[-1], thr, direction=event_direction, missing_value=missing_value,
+                                 num_nodes=test_y.shape[-2] if node_scores else None, device=device)
         result.update(_score_test_split(net, test_x, test_y, bs, missing_value, node_scores, params_path, log,
-                                        quantiles, skill))
+                                        quantiles, skill, events))
     return result
 
 
-def _score_test_split(net, test_x, test_y, bs, missing_value, per_node, params_path, log, quantiles=None, skill=None):
+def _score_test_split(net, test_x, test_y, bs, missing_value, per_node, params_path, log, quantiles=None, skill=None,
+                      events=None):
     """run()'s test-set scores: score_batches, rank 0's log lines and files, the result keys.  With
     quantiles the point scores come from the ``point_index`` column and the calibration scores are
     logged (coverage per level and mean pinball, one line per horizon) and written beside them.
     With skill (a loss.BaselineSkill, fed in the same pass): ``test_skill`` (and ``test_node_skill``),
-    one ``Test skill`` line per horizon and one overall, ``test_skill.json`` (``test_node_skill.npz``)."""
+    one ``Test skill`` line per horizon and one overall, ``test_skill.json`` (``test_node_skill.npz``).
+    With events (a loss.EventScores, fed in the same pass): ``test_event_scores`` (and
+    ``test_node_event_scores``), one ``Test events`` line per horizon and one overall, the number of
+    excluded nodes, ``test_event_scores.json`` (the scores, the direction, the thresholds; per-node
+    thresholds as their shape only) and ``test_node_event_scores.npz`` (with ``thresholds`` and
+    ``excluded``)."""
     import json
     rank, _ = _world()
-    metrics, qm = score_batches(net, test_x, test_y, bs, missing_value, per_node, quantiles, skill), None
+    metrics, qm = score_batches(net, test_x, test_y, bs, missing_value, per_node, quantiles, skill, events), None
     if quantiles is not None:
         metrics, qm = metrics
     excel_list, scores = metrics.compute(), metrics.scores()
@@ -988,6 +1077,28 @@ def _score_test_split(net, test_x, test_y, bs, missing_value, per_node, params_p
                 json.dump(dict({k: v.tolist() for k, v in ss.items()}, period=skill.period), f, indent=1)
             if per_node:
                 np.savez(os.path.join(params_path, 'test_node_skill.npz'), **out["test_node_skill"])
+    if events is not None:
+        es = out["test_event_scores"] = events.scores()
+        if per_node:
+            out["test_node_event_scores"] = events.node_scores()
+        if rank == 0:
+            thr, excluded = events.thresholds, events.excluded
+            names = ['%g' % v for v in thr] if thr.ndim == 1 else ['#%d' % k for k in range(events.K)]
+            for i in range(events.P + 1):
+                log('Test events %s: ' % ('overall' if i == events.P else 'horizon %d' % i)
+                    + ' '.join('%s[%s] %.4f' % (s, name, es[s][i, k]) for k, name in enumerate(names)
+                               for s in ('pod', 'far', 'csi', 'hss'))
+                    + ' hss_multi %.4f' % es["hss_multi"][i])
+            if excluded is not None:
+                log('Test events: %d of %d nodes excluded (no observed training value)'
+                    % (int(excluded.sum()), excluded.size))
+            with open(os.path.join(params_path, 'test_event_scores.json'), 'w') as f:
+                json.dump(dict({k: v.tolist() for k, v in es.items()}, direction=events.direction,
+                               thresholds=thr.tolist() if thr.ndim == 1 else {"shape": list(thr.shape)}), f, indent=1)
+            if per_node:
+                np.savez(os.path.join(params_path, 'test_node_event_scores.npz'), thresholds=thr,
+                         excluded=np.zeros(0, dtype=bool) if excluded is None else excluded,
+                         **out["test_node_event_scores"])
     return out
 
 
@@ -1060,6 +1171,17 @@ def arg_parser():
     ap.add_argument("--climatology-period", type=int, default=None,
                     help="steps of the seasonal cycle of --baseline-skill (overrides [Training] climatology_period; "
                          "default: [Data] period)")
+    ap.add_argument("--event-thresholds", default=None,
+                    help="comma separated drought thresholds in the units of the targets, mildest first, e.g. "
+                         "--event-thresholds=-1.0,-1.5,-2.0 (with '=': the list starts with a minus sign): also score the test split as an event forecast (POD, FAR, CSI, HSS, the class "
+                         "confusion matrix; test_event_scores.json; implies --test-metrics; overrides [Training] "
+                         "event_thresholds)")
+    ap.add_argument("--event-percentiles", default=None,
+                    help="with --stream-windows: the thresholds are these percentiles of each node's own training "
+                         "steps, mildest first, e.g. 20,10,5 (overrides [Training] event_percentiles)")
+    ap.add_argument("--event-direction", default=None, choices=("below", "above"),
+                    help="an event is a value at or below (default) or at or above its threshold (overrides "
+                         "[Training] event_direction)")
     return ap
 
 
@@ -1077,7 +1199,9 @@ def main(argv=None):
             weight_decay=a.weight_decay, loss=a.loss, missing_value=a.missing_value,
             stream_windows=a.stream_windows, input_fill=a.input_fill, input_max_gap=a.input_max_gap,
             test_metrics=a.test_metrics, node_scores=a.node_scores, multi_feature=a.multi_feature,
-            quantiles=a.quantiles, baseline_skill=a.baseline_skill, climatology_period=a.climatology_period)
+            quantiles=a.quantiles, baseline_skill=a.baseline_skill, climatology_period=a.climatology_period,
+            event_thresholds=a.event_thresholds, event_percentiles=a.event_percentiles,
+            event_direction=a.event_direction)
     finally:
         if world > 1:
             dist.destroy_process_group()

@@ -650,6 +650,41 @@ int dstagnn_skill_accumulate(int64_t B, int64_t N, int P, const float* pred, con
                              void* scratch, size_t scratch_bytes, dstagnn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Drought event scores (loss.hip): the class contingency counts of a forecast against K thresholds
+ * on the index, per horizon and per node.
+ *
+ * dstagnn_events_accumulate: pred, target (B, N, P) fp32 and thr fp32 on the device -> htable
+ * (P, cols) and, unless NULL, ntable (N, cols) doubles on the device, cols = 2 + (K + 1)^2, RUNNING
+ * tables the call adds to (zero them to start).  Every value in them is an integer, exact in fp64.
+ * thr is (K) when thr_per_node = 0 (one set for every node) or (K, N) row-major when 1, in the units
+ * of target, mildest first.  Event k of a value v is v <= thr_k (above = 0) or v >= thr_k
+ * (above = 1), every compare in fp32 (a value equal to the threshold is an event); the class of v
+ * is c(v) = the number of events that hold, 0 .. K.  A target is valid by the criterion's rule
+ * (mask_mode / null_val, DSTAGNN_MASK_*); an invalid one reaches no count.  A node one of whose
+ * thresholds is NaN is excluded: none of its entries reaches any count (callers make such a column
+ * all NaN; the library does not read the thresholds on the host).
+ *   column 0                   entries with a valid target on a node that is not excluded
+ *   column 1                   those among them whose prediction is NaN (they reach no cell)
+ *   column 2 + co (K + 1) + cf the entries of observed class co = c(target), forecast class cf = c(pred)
+ * so column 0 = column 1 + the sum of the cells.  +-inf predictions and targets are ordinary
+ * values; a NaN target that the mask lets through has class 0.
+ * One launch of ceil(N / (256 / P)) workgroups, no host synchronisation; the cells are uint32
+ * histograms in (P + 256 / P) cols 4 bytes of LDS under integer atomic adds (no floating-point
+ * atomics): the same bits on every call.  1 <= P <= 256, 1 <= K <= DSTAGNN_MAX_EVENT_LEVELS, B,
+ * N >= 1, B N P and K N < 2^31, the LDS bytes <= 64 KiB (refuses only K = 7 with P = 1 or P >= 248: 257 rows), else
+ * DSTAGNN_E_SHAPE; a null pred / target / thr / htable / scratch, an unknown mask mode, above or
+ * thr_per_node outside {0, 1} -> DSTAGNN_E_ARG; scratch smaller than
+ * dstagnn_events_scratch_bytes(B, N, P, K) (0 for a shape it rejects) -> DSTAGNN_E_SPACE.  All of
+ * it is checked before anything touches the device.
+ * ------------------------------------------------------------------------------------- */
+#define DSTAGNN_MAX_EVENT_LEVELS 7
+int64_t dstagnn_events_scratch_bytes(int64_t B, int64_t N, int P, int K);
+int dstagnn_events_accumulate(int64_t B, int64_t N, int P, int K, int above, const float* pred, const float* target,
+                              int mask_mode, float null_val, const float* thr, int thr_per_node, double* htable,
+                              double* ntable /* may be NULL */, void* scratch, size_t scratch_bytes,
+                              dstagnn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Graph builders (stag.hip).  fp64 throughout, like the reference's numpy/scipy code.
  * ------------------------------------------------------------------------------------- */
 
